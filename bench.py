@@ -15,16 +15,22 @@ offline).  Streams are sharded by contiguous range over ranks (weak scaling: fix
 the only collective is the gather of fp32 scores [S, n_labels] to rank 0 over RCCL (every step, or every
 --gather-every K steps).
 
-The JSON line carries, next to the contract fields:
+A plain run sets up, warms up, times exactly --steps steps and prints the JSON line (contract fields, config, scores_valid);
+`parity`, `roofline` and `cpu_baseline` are null in it.  With --full the line also carries:
   parity       64 probe streams x 16 frames placed at random ids of the SAME full-size engine, compared with the CPU
                oracle before the timed region (oracle/parity_sample.py; the timed configuration carries its own parity evidence)
-  roofline     dominant kernel, from hipEvents on the library's stream during the timed steps
+  roofline     dominant kernel, from hipEvents on the library's stream in a separate pass after the timed steps
   cpu_baseline the reference's algorithm on the host cores (torch-CPU port), timed by rank 0 before it joins the process group (every N)
   sustained    100 warm-up + 250 timed steps of the same configuration (N = 1 only)
   fp32_exact   the same workload on the exact-fp32 kernel family (use_mfma = 1), the reference's arithmetic type
   resident_1m  1,048,576 streams resident in ONE handle on one GPU (run in a child process): ms per step must stay < 80
+  (and the other BASELINE configurations, masked steps, host PCM, embed_clips; the --no-* switches thin a --full run out)
+
+--dump-outputs DIR writes the scores of the last timed step, all ranks' streams in global order, as DIR/scores.npy (fp32
+[streams x gpus, n_labels]; a fixed, seeded sample of rows when that exceeds 64 MB).  The inputs depend only on the arguments.
 
   python bench.py --gpus 1 --steps 50 --warmup 10
+  python bench.py --gpus 1 --steps 50 --warmup 10 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus 8 --steps 50 --warmup 10
 """
@@ -194,6 +200,27 @@ def timed_run(torch, dist, eng, pool, scores, steps, warmup, dev, world, gathere
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item()), kt
+
+
+def all_scores(torch, dist, scores, world, rank, backend):
+    """Every rank's scores [S, n_labels] of the last step, in global stream order, as a host array on rank 0 (None elsewhere)."""
+    if world == 1:
+        return scores.cpu().numpy()
+    local = scores if backend == "nccl" else scores.cpu()          # gloo gathers host tensors
+    blocks = [torch.empty_like(local) for _ in range(world)] if rank == 0 else None
+    dist.gather(local, blocks, dst=0)
+    return torch.cat(blocks).cpu().numpy() if rank == 0 else None
+
+
+def dump_scores(out_dir, rows, budget=60 << 20):
+    """out_dir/scores.npy, fp32 [rows, n_labels]; above `budget` bytes (64 MB with room to spare) a fixed, seeded sample of the
+    rows, kept in row order, so that two builds run with the same arguments compare output for output."""
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    if a.nbytes > budget:
+        keep = budget // (a.nbytes // a.shape[0])
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), a)
 
 
 def parity_check(torch, eng, pool, scores, dev, head_names, ref, rank, vad=False):
@@ -620,6 +647,9 @@ def main():
                     "host buffers and scores returned to the host every step through the pipelined oww_submit / oww_collect path "
                     "(upload of step t+1 overlaps the kernels of step t)")
     ap.add_argument("--host-pcm-blocking", action="store_true", help="the same through the blocking oww_step(host, host) call (no overlap)")
+    ap.add_argument("--full", action="store_true", help="besides the headline steps: CPU baseline, oracle-sampled parity, per-kernel "
+                    "timing pass and roofline, and the extra records (the --no-* switches thin these out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the scores of the last timed step to DIR/scores.npy")
     args = ap.parse_args()
 
     if args.leg == "resident_1m":
@@ -637,7 +667,7 @@ def main():
     head_names = [n for n in args.heads.split(",") if n]
     cpu_base = None
     t_pre = time.perf_counter()
-    if rank0 and not args.no_cpu_baseline:
+    if rank0 and args.full and not args.no_cpu_baseline:
         # forked single-threaded workers: must run before this process touches HIP.  Rank 0 times it at EVERY N (the other ranks sit
         # in the rendezvous below meanwhile, so the host cores are free): an N > 1 line without it would read "unmeasured".
         from oracle import cpu_baseline
@@ -645,7 +675,7 @@ def main():
     parity_ref = None
     family_ok = not (args.valu or args.lds_mfma)
     PS6 = ("alexa", "hey_mycroft", "hey_jarvis", "hey_rhasspy", "timer", "weather")        # (= oracle.parity_sample.HEADS6)
-    want_parity = (not args.no_parity and family_ok and set(head_names) <= set(PS6)
+    want_parity = (args.full and not args.no_parity and family_ok and set(head_names) <= set(PS6)
                    and not (args.host_pcm or args.host_pcm_blocking))
     vad_parity_ref = default6_ref = None
     if want_parity and rank0:
@@ -733,7 +763,8 @@ def main():
             parity["ok"] = bool(n[1].item()) and bool(parity["max_abs_err"] <= parity["tolerance"])
 
     host = args.host_pcm or args.host_pcm_blocking
-    timing = not args.no_kernel_timing and not args.graph
+    timing = args.full and not args.no_kernel_timing and not args.graph
+    extras_on = args.full and not args.no_extras
     kpass = None
     if host:
         host_pool = [torch.empty(S, 1280, dtype=torch.int16, pin_memory=True).copy_(t).numpy() for t in pool]
@@ -773,17 +804,21 @@ def main():
         # the timed K steps run WITHOUT per-kernel hipEvents (the optional block-pipelined step, OWW_BLOCKS > 1, is switched off by
         # the library while kernels are being timed one by one; the default is one block, so both passes run the same launches)
         dt_max, _ = timed_run(torch, dist, eng, pool, scores, args.steps, args.warmup, dev, world, gatherer, False)
-        ktimes, kpass = None, None
-        if timing:
-            n_k = max(4, min(args.steps, 10))
-            dt_k, ktimes = timed_run(torch, dist, eng, pool, scores, n_k, 2, dev, world, gatherer, True)
-            kpass = {"steps": n_k, "launches": int(sum(v["launches"] for v in ktimes.values())), "ms_per_step": round(1e3 * dt_k / n_k, 4),
-                     "note": "separate pass after the timed steps: per-kernel hipEvents on, block pipelining off (kernels run one after the other)"}
+        ktimes = None
+    if args.dump_outputs:                       # before any later pass overwrites the last timed step's scores
+        rows = all_scores(torch, dist, scores, world, rank, backend)
+        if rank0:
+            dump_scores(args.dump_outputs, rows)
+    if timing and not host:
+        n_k = max(4, min(args.steps, 10))
+        dt_k, ktimes = timed_run(torch, dist, eng, pool, scores, n_k, 2, dev, world, gatherer, True)
+        kpass = {"steps": n_k, "launches": int(sum(v["launches"] for v in ktimes.values())), "ms_per_step": round(1e3 * dt_k / n_k, 4),
+                 "note": "separate pass after the timed steps: per-kernel hipEvents on, block pipelining off (kernels run one after the other)"}
     ok = bool(torch.isfinite(scores).all().item()) and bool(((scores >= 0) & (scores <= 1)).all().item())
     range_flag = eng.range_status() if family == 3 else False
 
     extras = {}
-    if rank0 and world == 1 and not args.no_extras and not host:
+    if rank0 and world == 1 and extras_on and not host:
         # ---- c_abi_gather with ONE rank: the C ABI's RCCL exchange as a send-to-self on the handle's stream (what a 1-GPU box can show)
         if args.gather == "dist" and family == 3:
             try:
@@ -962,7 +997,7 @@ def main():
         out["pre_rendezvous_s"] = round(t_pre_done - t_pre, 1)      # rank 0: CPU baseline + oracle reference, before HIP / the process group
     else:
         out = None
-    if world > 1 and args.gather == "dist" and backend == "nccl" and not one_gpu and not args.no_extras and not host and eng is not None:
+    if world > 1 and args.gather == "dist" and backend == "nccl" and not one_gpu and extras_on and not host and eng is not None:
         # ---- c_abi_gather: the same steps delivered through the library's own RCCL exchange (the binder-without-torch path), every rank.
         #      Under a watchdog: a collective that never completes cannot be cancelled, and the headline line must survive it.
         def lost():

@@ -88,3 +88,19 @@ def test_composite_roofline_is_priced_only_from_a_counter_pass_of_the_loaded_bui
     out = b.issue_bound("stageA", 131072, 1.5, args)
     assert out["wave_instructions_per_stream_step"] == {"valu": 2635.0, "mfma": 512.0, "lds": 682.0} and have in out["source"] and "r06_instr" in out["source"]
     assert b.pmc_traffic("stageA", 131072, args) is None                # no traffic pass of this build
+
+
+def test_dumped_scores_are_fp32_and_a_fixed_sample_above_the_budget(tmp_path):
+    """--dump-outputs: the whole [rows, n_labels] block in fp32 when it fits, else the same seeded sample of rows on every run,
+    kept in row order."""
+    import numpy as np
+    b = _bench()
+    rows = np.arange(4000 * 3, dtype=np.float64).reshape(4000, 3)
+    b.dump_scores(str(tmp_path / "all"), rows)
+    got = np.load(tmp_path / "all" / "scores.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rows)
+    for d in ("s1", "s2"):
+        b.dump_scores(str(tmp_path / d), rows, budget=1200)                # 100 rows of 12 bytes
+    s1, s2 = np.load(tmp_path / "s1" / "scores.npy"), np.load(tmp_path / "s2" / "scores.npy")
+    assert s1.shape == (100, 3) and np.array_equal(s1, s2)
+    assert (np.diff(s1[:, 0]) > 0).all() and np.array_equal(s1, rows[(s1[:, 0] // 3).astype(int)])

@@ -14,7 +14,7 @@ if python -c "import sys; sys.exit(0 if float('$ms') > 0.42 else 1)"; then
   PMC_EXTRA="TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum" PMC_EXTRA2="SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_WAVES SQ_INSTS_SMEM SQ_WAIT_ANY SQ_WAVE_CYCLES" tools/pmc.sh r06c1_class2 --streams 4096 --heads hey_jarvis > gpurun_out/class2/pmc.log 2>&1
   cp gpurun_out/r06c1_class2/summary.txt gpurun_out/class2/pmc_c1_summary.txt 2>/dev/null
   for sw in 512 0; do
-    OWW_SMALL_WGS=$sw python bench.py --streams 4096 --heads hey_jarvis --steps 1000 --warmup 300 --no-cpu-baseline --no-parity --no-extras 2>/dev/null | \
+    OWW_SMALL_WGS=$sw python bench.py --streams 4096 --heads hey_jarvis --steps 1000 --warmup 300 --full --no-cpu-baseline --no-parity --no-extras 2>/dev/null | \
       python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('OWW_SMALL_WGS=$sw', d['ms_per_step'], d['kernel_ms'])" | tee -a gpurun_out/class2/ring_ab.txt
   done
 fi

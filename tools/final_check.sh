@@ -8,7 +8,7 @@ bash tools/pmc.sh ${tag}pmc > $out/pmc.log 2>&1; tail -4 $out/pmc.log | cut -c1-
 cp gpurun_out/${tag}pmc/instr.json profiles/_instr_tmp.json; cp gpurun_out/${tag}pmc/traffic.json profiles/_traffic_tmp.json
 # (the bench run below must find the fresh passes under profiles/: copy them in place on the box)
 cp gpurun_out/${tag}pmc/instr.json profiles/r05_instr.json; cp gpurun_out/${tag}pmc/traffic.json profiles/r05_traffic.json; rm -f profiles/_instr_tmp.json profiles/_traffic_tmp.json
-timeout 400 python bench.py > $out/bench_default.json 2> $out/bench_default.err
+timeout 400 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 python - $out/bench_default.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).readline())

@@ -8,8 +8,8 @@ cd $GRAFT_REPO_ROOT
 ulimit -n 65535 2>/dev/null
 (time timeout 900 python -m pytest tests -m gpu -x -q --durations=8) > $out/pytest_gpu_final.log 2>&1
 tail -14 $out/pytest_gpu_final.log
-timeout 400 python bench.py > $out/bench_default.json 2> $out/bench_default.err
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_20x5.json 2> $out/bench_driver.err
+timeout 400 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_driver_20x5.json 2> $out/bench_driver.err
 python - $out/bench_default.json $out/bench_driver_20x5.json <<'PY'
 import json, sys
 for f in sys.argv[1:]:

@@ -8,12 +8,12 @@ out=$GRAFT_REPO_ROOT/gpurun_out/$tag; mkdir -p $out; cd $GRAFT_REPO_ROOT; ulimit
 grep -E "passed|failed|error" $out/pytest_gpu_selected.log | tail -2
 if ! grep -qE "^[0-9]+ passed" $out/pytest_gpu_selected.log || grep -qE "failed|error" $out/pytest_gpu_selected.log; then tail -30 $out/pytest_gpu_selected.log; echo "TESTS NOT GREEN: stopping"; exit 1; fi
 for H in timer alexa,timer; do
-  timeout 100 python bench.py --streams 131072 --heads $H --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-parity 2>/dev/null | head -1 | python -c "
+  timeout 100 python bench.py --streams 131072 --heads $H --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras --no-parity 2>/dev/null | head -1 | python -c "
 import sys, json; d = json.loads(sys.stdin.readline()); print('$H', d['ms_per_step'], d['kernel_ms']['heads'])"
 done 2>&1 | tee $out/generic_heads_full_batch.txt
 bash tools/pmc.sh ${tag}pmc > $out/pmc.log 2>&1
 cp gpurun_out/${tag}pmc/instr.json profiles/r05_instr.json; cp gpurun_out/${tag}pmc/traffic.json profiles/r05_traffic.json
-timeout 300 python bench.py > $out/bench_default.json 2> $out/bench_default.err
+timeout 300 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 python - $out/bench_default.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).readline())

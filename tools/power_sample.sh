@@ -3,7 +3,7 @@
 out=gpurun_out/power; mkdir -p $out; tag=$1; shift
 (while true; do rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Power|sclk"; sleep 0.3; done) > $out/smi_$tag.log &
 sm=$!
-python bench.py "$@" --no-extras --no-cpu-baseline --no-parity > $out/bench_$tag.json 2> $out/bench_$tag.err
+python bench.py "$@" --full --no-extras --no-cpu-baseline --no-parity > $out/bench_$tag.json 2> $out/bench_$tag.err
 kill $sm; wait $sm 2>/dev/null
 python - "$out" "$tag" <<'PY'
 import json, re, sys

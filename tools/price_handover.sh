@@ -8,7 +8,7 @@
 out=${1:-gpurun_out/price}; mkdir -p $out
 for rep in 1 2 3; do
   for L in libowwhip.so libowwhip_priceA.so libowwhip_priceB.so libowwhip_priceAB.so; do
-    OWW_LIB=$PWD/openwakeword_amd/$L python bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-parity --no-extras 2>/dev/null | \
+    OWW_LIB=$PWD/openwakeword_amd/$L python bench.py --steps 30 --warmup 10 --full --no-cpu-baseline --no-parity --no-extras 2>/dev/null | \
       python -c "import sys,json; d=json.loads(sys.stdin.readline()); k=d['kernel_ms']; print('$rep $L step %.4f  A %.4f B %.4f C %.4f D %.4f E %.4f heads %.4f' % (d['ms_per_step'], k['stageA'], k['stageB'], k['stageC'], k['stageD'], k['stageE'], k['heads']))" | tee -a $out/price_handover.txt
   done
 done

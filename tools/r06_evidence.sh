@@ -16,8 +16,8 @@ cp gpurun_out/${tag}pmc/summary.txt $out/pmc_summary.txt
 find gpurun_out/${tag}pmc/trace -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} $out/kernel_stats.csv
 (time timeout 1200 python -m pytest tests -m gpu -x -q --durations=8) > $out/pytest_gpu_final.log 2>&1
 tail -14 $out/pytest_gpu_final.log
-timeout 600 python bench.py > $out/bench_default.json 2> $out/bench_default.err
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_20x5.json 2> $out/bench_driver.err
+timeout 600 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_driver_20x5.json 2> $out/bench_driver.err
 python - $out/bench_default.json $out/bench_driver_20x5.json <<'PY'
 import json, sys
 for f in sys.argv[1:]:
