@@ -235,6 +235,48 @@ int  oww_get_raw(oww_ctx* h, float* out);
 int  oww_resample(oww_ctx* h, const int16_t* in, int in_on_device, int32_t n_in, int32_t p, int32_t q, const float* taps, int32_t n_taps,
                   int16_t* out, int out_on_device, int32_t n_out);
 
+/* ---- head bank: each stream scored only by the wake-word models it subscribed to -----------------------------------------------------
+ * openWakeWord's training pipeline (train.py, examples/custom_model.yml) yields one small binary head per phrase; a server that carries
+ * many users' own phrases scores each connection with ITS heads, not with every head of the handle.  The embedding CNN (~94 % of a step)
+ * is shared; the bank adds a device-resident set of heads, a per-stream subscription to up to K of them, and ONE routed heads launch per
+ * hidden width (<= 64 and <= 128 units) that evaluates every (stream, subscribed head) pair once.
+ *   oww_bank_configure  before oww_commit: K slots per stream (1..8) and the bank's capacity.  Allocates the subscription table [S][K]
+ *                       (all slots empty), bank scores [S][K], score rings [S][K][30] and slot counters.  use_mfma = 3 only (OWW_ESTATE
+ *                       otherwise).  A handle that never calls it allocates and launches nothing new.
+ *   oww_bank_add        after commit, streams may be live: a head blob in the layout of oww_add_head -> bank id >= 0.  Accepted: kind 0
+ *                       (binary sigmoid, n_out = 1), ungated, extra_blocks = 0, hidden <= 128, with or without LayerNorm, T <= the handle's
+ *                       feature ring; anything else OWW_EINVAL naming the reason (such heads stay available as fixed heads).  The head
+ *                       is packed like a fixed net of its width and self-tested on windows of oww_commit's probe embeddings against a
+ *                       float64 evaluation: beyond 1e-3 it is refused with OWW_ERANGE, as oww_commit refuses weights.  A full bank:
+ *                       OWW_EINVAL.
+ *   oww_bank_remove     the slots subscribed to `id` become empty.
+ *   oww_bank_set_postproc  patience / threshold of one bank head (model.py:340-359; patience <= 0 off, threshold NaN = none); the
+ *                       debounce frames are the handle's (oww_set_postproc).  Default: off.
+ *   oww_subscribe       bank_ids[n][K] for streams stream_ids[n]; -1 = empty slot.  A slot whose head changes restarts its prediction
+ *                       count and ring (that model newly loaded into the stream's Model); the stream's audio, mel and feature state is
+ *                       untouched.  oww_reset restarts the bank rings and counters of the streams it resets and keeps the subscriptions
+ *                       (model.py:226-230).  Unknown ids or stream ids out of range: OWW_EINVAL, nothing changed.
+ *   oww_bank_scores     syncs and copies the post-processed bank scores, host fp32 [S][K] (empty slot: 0.0); oww_bank_scores_dev: the
+ *                       same on the device, valid until the next step.  Valid after oww_step / oww_step_masked / oww_collect.
+ *   oww_bank_routing    info = {tiles, waves per tile, entries} of the <= 64-unit launch, then of the <= 128-unit launch;
+ *                       weight_bytes = first-layer weight bytes one step streams.
+ * Semantics per (stream, slot): the raw score is the head's sigmoid output on the stream's last T feature rows (max over the chunks of a
+ * multi-chunk call), bit for bit what the same net scores as a fixed head; then model.py:330-381 with the slot's own prediction count
+ * (first-5 zeroing), the head's patience / threshold, a 30-deep ring per slot and the stream's VAD gate.  Masked steps leave every bit of a
+ * sitting-out stream's bank state alone.  Every subscription or bank change re-captures the oww_use_graph graph on the next step.
+ * Cost model: one workgroup per tile (1 or 4 waves = 32 or 128 entries of one head, chosen from the mean group size; largest tiles
+ * first) streams that head's first-layer weights (T x 96 x 64 or 128 units, as f16 hi / lo halves: 0.39 / 0.79 MB at T = 16) once and
+ * gathers each listed stream's ring rows (T x 384 bytes), so a step reads ~ tiles x weight bytes + entries x 6 KB.  Launches are counted
+ * under kernel class 6 (heads) and the bank's post-processing under class 7; a bank without subscribers launches nothing. */
+int  oww_bank_configure(oww_ctx* h, int32_t slots, int32_t capacity);
+int  oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes);
+int  oww_bank_remove(oww_ctx* h, int32_t id);
+int  oww_bank_set_postproc(oww_ctx* h, int32_t id, int32_t patience, float threshold);
+int  oww_subscribe(oww_ctx* h, const int32_t* stream_ids, int32_t n, const int32_t* bank_ids);
+int  oww_bank_scores(oww_ctx* h, float* out);
+const float* oww_bank_scores_dev(const oww_ctx* h);
+int  oww_bank_routing(oww_ctx* h, int32_t info[6], double* weight_bytes);
+
 /* ---- multi-GPU: delivery of the scores to one rank over RCCL (xGMI), for binders without torch.distributed ----------------------
  * Streams are independent, so N GPUs = N handles in N processes, each owning a contiguous range of the global streams (the
  * reference's only scale-out, utils.py:502-536 bulk_predict, splits FILES over processes the same way); nothing in the data path

@@ -70,6 +70,14 @@ SYMBOLS = {
     "oww_enable_timing": (C.c_int, [_P, C.c_int]),
     "oww_kernel_times": (C.c_int, [_P, _P, _P]),
     "oww_use_graph": (C.c_int, [_P, C.c_int]),
+    "oww_bank_configure": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "oww_bank_add": (C.c_int, [_P, _P, C.c_size_t]),
+    "oww_bank_remove": (C.c_int, [_P, C.c_int32]),
+    "oww_bank_set_postproc": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_float]),
+    "oww_subscribe": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "oww_bank_scores": (C.c_int, [_P, _P]),
+    "oww_bank_scores_dev": (_P, [_P]),
+    "oww_bank_routing": (C.c_int, [_P, _P, _P]),
     "oww_comm_id": (C.c_int, [_P]),
     "oww_comm_init": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "oww_gather_scores": (C.c_int, [_P, _P, _P]),

@@ -564,6 +564,29 @@ struct oww_ctx {
     bool want_graph = false;
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
+    // head bank (oww_bank_*): routed f16-split heads, each stream subscribed to up to bank_K of them (owh::heads_bank_kernel)
+    struct BankHead {
+        bool live = false;
+        int T = 0, hidden = 0, has_ln = 0, ht = 4, patience = 0;
+        float threshold = NAN;
+        float* d_img = nullptr;                  // w1hx | w2hx | padded per-unit arrays (| w3hx): the packing of a fixed net of the same width
+        size_t w1_bytes = 0;                     // first-layer weight bytes one tile streams
+        owh::BankHeadDev dev{};
+    };
+    int bank_K = 0, bank_cap = 0;                // 0 = no bank (oww_bank_configure)
+    std::vector<BankHead> bank;
+    std::vector<int> bank_sub;                   // host copy of d_bank_sub: [S][K] bank head per slot, -1 = empty
+    int* d_bank_sub = nullptr; int* d_bank_idx = nullptr;
+    float *d_bank_raw = nullptr, *d_bank_scores = nullptr, *d_bank_ring = nullptr;
+    uint32_t* d_bank_npred = nullptr;
+    owh::BankHeadDev* d_bank_heads = nullptr; int* d_bank_pat = nullptr; float* d_bank_thr = nullptr;
+    owh::BankTile* d_bank_tiles = nullptr; int* d_bank_entries = nullptr; size_t bank_tiles_cap = 0;
+    // routing table, per width class (0: <= 64 hidden units, 1: <= 128): tiles [tile0, tile0 + ntiles) of d_bank_tiles, WG waves each
+    int bank_ntiles[2] = {}, bank_tile0[2] = {}, bank_wg[2] = {1, 1}, bank_entries_n[2] = {};
+    std::vector<std::pair<int, int>> bank_head_tiles[2];   // OWH_BANK_PER_HEAD builds: [first tile, count] of every subscribed head
+    double bank_wbytes = 0.0;                    // first-layer weight bytes one step streams over all tiles
+    std::vector<float> probe_emb;                // oww_commit's fp32 probe embeddings [nb * 16][32][96]: oww_bank_add's self-test
+    int probe_nb = 0;
 };
 
 namespace {
@@ -1025,7 +1048,61 @@ void free_all(oww_ctx* h) {
     h->ev.clear();
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
     if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    for (auto& b : h->bank) fr(b.d_img);
+    fr(h->d_bank_sub); fr(h->d_bank_idx); fr(h->d_bank_raw); fr(h->d_bank_scores); fr(h->d_bank_ring); fr(h->d_bank_npred);
+    fr(h->d_bank_heads); fr(h->d_bank_pat); fr(h->d_bank_thr); fr(h->d_bank_tiles); fr(h->d_bank_entries);
+    h->bank_tiles_cap = 0;
     comm_release(h);
+}
+
+// ---- head bank: the routed heads launch (one per width class that has subscribers) and its post-processing
+bool bank_active(const oww_ctx* h) { return h->bank_ntiles[0] + h->bank_ntiles[1] > 0; }
+
+void launch_bank_tiles(oww_ctx* h, owh::BankParams q, int c, int tile0, int ntiles) {
+    q.tiles = h->d_bank_tiles + tile0;
+    const dim3 grid(ntiles), block(64 * h->bank_wg[c]);
+    if (c == 0) {
+        if (h->bank_wg[c] == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 4>), grid, block, 0, h->stream, q);
+        else hipLaunchKernelGGL((owh::heads_bank_kernel<1, 4>), grid, block, 0, h->stream, q);
+    } else {
+        if (h->bank_wg[c] == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 8>), grid, block, 0, h->stream, q);
+        else hipLaunchKernelGGL((owh::heads_bank_kernel<1, 8>), grid, block, 0, h->stream, q);
+    }
+}
+
+// nfeat_adv = 1: the step's ring counter advance has already run (block-pipelined step: the bank launch follows the join)
+int run_bank(oww_ctx* h, bool accumulate_max, int nfeat_adv) {
+    owh::BankParams q{};
+    q.feat = h->d_feat; q.ext = 0; q.TR = h->TR; q.nfeat = h->d_nfeat; q.nfeat_adv = nfeat_adv;
+    q.entries = h->d_bank_entries; q.heads = h->d_bank_heads; q.K = h->bank_K;
+    q.raw = h->d_bank_raw; q.accumulate_max = accumulate_max ? 1 : 0; q.range_flag = h->d_range; q.stream_on = h->on_now;
+    q.fscale = std::ldexp(1.0f, h->hx_efeat);
+    for (int c = 0; c < 2; ++c) {
+        if (!h->bank_ntiles[c]) continue;
+#if OWH_BANK_PER_HEAD
+        for (const auto& [t0, nt] : h->bank_head_tiles[c]) { Timed t(h, 6); launch_bank_tiles(h, q, c, t0, nt); }   // (d) of tools/bench_head_bank.py
+#else
+        Timed t(h, 6);
+        launch_bank_tiles(h, q, c, h->bank_tile0[c], h->bank_ntiles[c]);
+#endif
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int launch_bank_post(oww_ctx* h) {
+    if (!bank_active(h)) return 0;
+    owh::BankPostParams pp{};
+    pp.raw = h->d_bank_raw; pp.scores = h->d_bank_scores; pp.ring = h->d_bank_ring; pp.npred = h->d_bank_npred; pp.sub = h->d_bank_sub;
+    pp.patience = h->d_bank_pat; pp.threshold = h->d_bank_thr; pp.debounce_frames = h->debounce_frames;
+    pp.S = h->S; pp.K = h->bank_K;
+    pp.vad_ring = h->d_vadring; pp.n_vad = h->d_nvad; pp.vad_threshold = h->vad_threshold; pp.stream_on = h->on_now;
+    {
+        Timed t(h, 7);
+        hipLaunchKernelGGL(owh::bank_post_kernel, dim3((h->S * h->bank_K + 255) / 256), dim3(256), 0, h->stream, pp);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // one chunk of the streaming step on device-resident mel rows
@@ -1034,6 +1111,8 @@ int step_chunk(oww_ctx* h, int k, int c, bool first, bool last, bool single);
 int step_chunk(oww_ctx* h, int k, int c) { return step_chunk(h, k, c, c == 0, c == k - 1, k == 1); }
 int step_chunk(oww_ctx* h, int k, int c, bool first, bool last, bool single) {
     if (int rc = run_cnn(h, h->Spad, 8 * k * 32, c * 8 * 32)) return rc;
+    // the bank reads this chunk's ring rows before the fixed heads launch (which may advance the ring counters: post_in_heads)
+    if (bank_active(h) && h->blk_s1 == 0) if (int rc = run_bank(h, !first, 0)) return rc;
     h->post_in_heads_now = h->post_in_heads && single && h->n_verifiers == 0;
     const int rc = run_heads(h, h->Spad, !first, nullptr, -1, h->d_raw, 0);
     const bool done_in_heads = h->post_in_heads_now;
@@ -1173,6 +1252,7 @@ int launch_step(oww_ctx* h, const int16_t* d_pcm, int k) {
                     rc = fail(OWW_EHIP, "block join failed");
             }
             h->stream = main_stream; h->blk_s0 = h->blk_s1 = 0;
+            if (!rc && bank_active(h)) rc = run_bank(h, false, 1);       // after the join: every block's ring rows are in place
         } else rc = step_chunk(h, 1, 0);
         h->fuse_pcm = nullptr;
         if (rc) return rc;
@@ -1181,8 +1261,9 @@ int launch_step(oww_ctx* h, const int16_t* d_pcm, int k) {
         for (int c = 0; c < k; ++c)
             if (int rc = step_chunk(h, k, c)) return rc;
     }
-    if (h->post_in_heads && k == 1 && h->n_verifiers == 0) { HIPCHK(hipGetLastError()); return 0; }      // post-processing already ran inside the heads launch
-    return launch_postproc(h);
+    if (h->post_in_heads && k == 1 && h->n_verifiers == 0) { HIPCHK(hipGetLastError()); return launch_bank_post(h); }      // post-processing already ran inside the heads launch
+    if (int rc = launch_postproc(h)) return rc;
+    return launch_bank_post(h);
 }
 
 // A call of more chunks than the handle's mel buffer holds (n_chunks > max_chunks; the reference takes any length: model.py:287-298,
@@ -1202,7 +1283,8 @@ int launch_step_long(oww_ctx* h, const int16_t* d_pcm, int K) {
             if (int rc = step_chunk(h, ks, c, o + c == 0, o + c == K - 1, false)) return rc;
         h->k_last = ks;
     }
-    return launch_postproc(h);
+    if (int rc = launch_postproc(h)) return rc;
+    return launch_bank_post(h);
 }
 
 int launch_postproc(oww_ctx* h) {
@@ -1488,6 +1570,105 @@ int selftest_hx(oww_ctx* h, const HxCalib& cal) {
                     "use_mfma = 1", (double)err, (double)ref, (double)serr, (double)tol);
     }
     return 0;
+}
+
+// ---- head bank helpers (oww_bank_*) ---------------------------------------------------------------------------------------------------
+// every queued launch of the handle has finished: the routing table, the bank images and the slot state may change
+int bank_quiesce(oww_ctx* h) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (hipStream_t st : {h->blk_stream[0], h->blk_stream[1], h->blk_stream[2], h->blk_stream[3]}) if (st) HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// restart the listed slots (index stream * K + slot): prediction count, ring, raw and final score
+int bank_clear(oww_ctx* h, std::vector<int> slots) {
+    std::sort(slots.begin(), slots.end());
+    slots.erase(std::unique(slots.begin(), slots.end()), slots.end());
+    if (slots.empty()) return 0;
+    HIPCHK(copy_async(h->d_bank_idx, slots.data(), slots.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(owh::bank_clear_kernel, dim3((unsigned)((slots.size() + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->d_bank_idx,
+                       (int)slots.size(), h->d_bank_raw, h->d_bank_scores, h->d_bank_ring, h->d_bank_npred);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));     // (the host list is the copy's source)
+    return 0;
+}
+
+// Routing table from the subscriptions: per width class, each subscribed head's entries (stream * K + slot, ascending) cut into tiles
+// of 32 WG entries; WG = 4 waves (128 entries, one weight stream per 128) when the class's mean group holds >= 96 entries, else one
+// wave (32).  Tiles largest first.  One upload per change; the captured step graph is invalidated (its launches bake the tile count).
+int bank_route(oww_ctx* h) {
+    const int K = h->bank_K, cap = h->bank_cap;
+    std::vector<std::vector<int>> lists(cap);
+    for (int i = 0; i < h->S * K; ++i) if (h->bank_sub[i] >= 0) lists[h->bank_sub[i]].push_back(i);
+    std::vector<int> entries;
+    std::vector<owh::BankTile> tiles;
+    h->bank_wbytes = 0.0;
+    for (int c = 0; c < 2; ++c) {
+        long long n_ent = 0; int n_grp = 0;
+        for (int b = 0; b < cap; ++b)
+            if (h->bank[b].live && (h->bank[b].ht == 8) == (c == 1) && !lists[b].empty()) { n_ent += (long long)lists[b].size(); ++n_grp; }
+        int wg = n_grp > 0 && n_ent >= 96LL * n_grp ? 4 : 1;
+        if (const char* e = getenv("OWW_BANK_WG")) { const int v = atoi(e); if (v == 1 || v == 4) wg = v; }   // (A/B aid)
+        h->bank_wg[c] = wg;
+        h->bank_tile0[c] = (int)tiles.size();
+        h->bank_entries_n[c] = (int)n_ent;
+        h->bank_head_tiles[c].clear();
+        std::vector<owh::BankTile> ct;
+        for (int b = 0; b < cap; ++b) {
+            if (!h->bank[b].live || (h->bank[b].ht == 8) != (c == 1) || lists[b].empty()) continue;
+            const int base = (int)entries.size(), n = (int)lists[b].size();
+            entries.insert(entries.end(), lists[b].begin(), lists[b].end());
+            h->bank_head_tiles[c].push_back({h->bank_tile0[c] + (int)ct.size(), (n + 32 * wg - 1) / (32 * wg)});
+            for (int o = 0; o < n; o += 32 * wg) ct.push_back(owh::BankTile{b, base + o, std::min(32 * wg, n - o), 0});
+            h->bank_wbytes += (double)((n + 32 * wg - 1) / (32 * wg)) * (double)h->bank[b].w1_bytes;
+        }
+#if !OWH_BANK_PER_HEAD
+        std::stable_sort(ct.begin(), ct.end(), [](const owh::BankTile& a, const owh::BankTile& b) { return a.n > b.n; });
+#endif
+        tiles.insert(tiles.end(), ct.begin(), ct.end());
+        h->bank_ntiles[c] = (int)ct.size();
+    }
+    if (tiles.size() > h->bank_tiles_cap) {
+        if (h->d_bank_tiles) (void)dev_free(h->d_bank_tiles);
+        h->d_bank_tiles = nullptr; h->bank_tiles_cap = 0;
+        HIPCHK(dev_alloc(&h->d_bank_tiles, tiles.size() * sizeof(owh::BankTile)));
+        h->bank_tiles_cap = tiles.size();
+    }
+    if (!tiles.empty()) HIPCHK(copy_sync(h->d_bank_tiles, tiles.data(), tiles.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice));
+    if (!entries.empty()) HIPCHK(copy_sync(h->d_bank_entries, entries.data(), entries.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }     // the launch list changed
+    return 0;
+}
+
+// float64 evaluation of a binary one-block net (blob after the header) on one window x[T][96]: the bank self-test's reference
+double bank_eval_f64(const float* q, int T, int H, int has_ln, const float* x) {
+    const size_t K = (size_t)T * 96;
+    const float *w1 = q, *b1 = w1 + K * H, *g1 = b1 + H, *e1 = g1 + H;
+    const float* w2 = has_ln ? e1 + H : b1 + H;
+    const float *b2 = w2 + (size_t)H * H, *g2 = b2 + H, *e2 = g2 + H;
+    const float* w3 = has_ln ? e2 + H : b2 + H;
+    const float* b3 = w3 + H;
+    std::vector<double> a(H), z(H);
+    auto ln_relu = [&](std::vector<double>& v, const float* g, const float* be) {
+        if (has_ln) {
+            double mu = 0.0, var = 0.0;
+            for (int i = 0; i < H; ++i) mu += v[i];
+            mu /= H;
+            for (int i = 0; i < H; ++i) var += (v[i] - mu) * (v[i] - mu);
+            const double rs = 1.0 / std::sqrt(var / H + 1e-5);
+            for (int i = 0; i < H; ++i) v[i] = (v[i] - mu) * rs * g[i] + be[i];
+        }
+        for (int i = 0; i < H; ++i) v[i] = std::max(v[i], 0.0);
+    };
+    for (int i = 0; i < H; ++i) a[i] = b1[i];
+    for (size_t k = 0; k < K; ++k) for (int i = 0; i < H; ++i) a[i] += (double)x[k] * w1[k * H + i];
+    ln_relu(a, g1, e1);
+    for (int i = 0; i < H; ++i) z[i] = b2[i];
+    for (int k = 0; k < H; ++k) for (int i = 0; i < H; ++i) z[i] += a[k] * w2[(size_t)k * H + i];
+    ln_relu(z, g2, e2);
+    double o = b3[0];
+    for (int i = 0; i < H; ++i) o += z[i] * w3[i];
+    return 1.0 / (1.0 + std::exp(-o));
 }
 
 void comm_release(oww_ctx* h) {
@@ -2188,6 +2369,26 @@ int oww_commit(oww_ctx* h) {
             clk.lap("self-test replay + reset");
         }
     }
+    if (h->hx) { h->probe_emb = cal.ref_emb; h->probe_nb = cal.nb; }      // (oww_bank_add's self-test inputs)
+    if (h->bank_K > 0) {
+        const size_t SK = (size_t)h->S * h->bank_K;
+        if (int rc = dalloc(h->stream, &h->d_bank_sub, SK, false)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_bank_idx, SK)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_bank_raw, SK)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_bank_scores, SK)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_bank_ring, SK * OWW_SCORE_RING)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_bank_npred, SK)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_bank_entries, SK)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_bank_heads, (size_t)h->bank_cap)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_bank_pat, (size_t)h->bank_cap)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_bank_thr, (size_t)h->bank_cap, false)) return rc;
+        h->bank.assign(h->bank_cap, oww_ctx::BankHead{});
+        h->bank_sub.assign(SK, -1);
+        std::vector<float> nanv(h->bank_cap, NAN);
+        HIPCHK(copy_async(h->d_bank_sub, h->bank_sub.data(), SK * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(copy_async(h->d_bank_thr, nanv.data(), nanv.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
     h->committed = true;
     return OWW_OK;
     OWW_GUARD_END
@@ -2216,6 +2417,12 @@ int oww_reset(oww_ctx* h, const int32_t* stream_ids, int32_t n, const float* ini
         }
         HIPCHK(copy_async(h->d_ids, stream_ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
         if (int rc = do_reset(h, h->d_ids, n, d_init)) return rc;
+    }
+    std::vector<int> slots;                      // head bank: Model.reset() empties every prediction buffer, the subscriptions stay
+    if (h->bank_K > 0) {
+        if (!stream_ids) for (int i = 0; i < h->S * h->bank_K; ++i) slots.push_back(i);
+        else for (int i = 0; i < n; ++i) for (int k = 0; k < h->bank_K; ++k) slots.push_back(stream_ids[i] * h->bank_K + k);
+        if (int rc = bank_clear(h, slots)) return rc;
     }
     HIPCHK(hipStreamSynchronize(h->stream));     // host buffers may be reused by the caller
     return OWW_OK;
@@ -2900,6 +3107,250 @@ int oww_use_graph(oww_ctx* h, int on) {
 }
 
 // ---- multi-GPU delivery of results over RCCL, without torch.distributed -----------------------------------------------------------
+// ---- head bank ------------------------------------------------------------------------------------------------------------------------
+int oww_bank_configure(oww_ctx* h, int32_t slots, int32_t capacity) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    if (h->committed) return fail(OWW_ESTATE, "oww_bank_configure: call before oww_commit");
+    if (!h->hx) return fail(OWW_ESTATE, "oww_bank_configure: the head bank runs on the fp16-split heads kernels (use_mfma = 3) only");
+    if (slots < 1 || slots > 8) return fail(OWW_EINVAL, "oww_bank_configure: slots = %d (1..8)", slots);
+    if (capacity < 1 || capacity > 65536) return fail(OWW_EINVAL, "oww_bank_configure: capacity = %d (1..65536)", capacity);
+    h->bank_K = slots; h->bank_cap = capacity;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
+    OWW_GUARD_BEGIN
+    if (!h || !blob || nbytes < 32) return fail(OWW_EINVAL, "oww_bank_add: bad argument");
+    if (!h->hx) return fail(OWW_ESTATE, "oww_bank_add: the head bank runs on the fp16-split heads kernels (use_mfma = 3) only");
+    if (!h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_bank_add: needs oww_bank_configure before oww_commit, and a committed handle");
+    const int32_t* hdr = (const int32_t*)blob;
+    const int kind = hdr[0], T = hdr[1], H = hdr[2], O = hdr[3], has_ln = hdr[4], extra = hdr[5];
+    if (kind == 1) return fail(OWW_EINVAL, "oww_bank_add: gated heads are not accepted in the bank (load them as fixed heads)");
+    if (kind == 2) return fail(OWW_EINVAL, "oww_bank_add: multiclass heads are not accepted in the bank (load them as fixed heads)");
+    if (kind == 3) return fail(OWW_EINVAL, "oww_bank_add: recurrent heads are not accepted in the bank (load them as fixed heads)");
+    if (kind != 0) return fail(OWW_EINVAL, "oww_bank_add: unknown head kind %d", kind);
+    if (O != 1) return fail(OWW_EINVAL, "oww_bank_add: a bank head has one sigmoid output (n_out = %d)", O);
+    if (extra != 0) return fail(OWW_EINVAL, "oww_bank_add: a bank head has exactly one hidden block (extra_blocks = %d)", extra);
+    if (H < 1 || H > 128) return fail(OWW_EINVAL, "oww_bank_add: hidden = %d (a bank head has 1..128 hidden units)", H);
+    if (T < 1 || T > h->TR) return fail(OWW_EINVAL, "oww_bank_add: T = %d exceeds the handle's feature ring (%d rows)", T, h->TR);
+    if (has_ln != 0 && has_ln != 1) return fail(OWW_EINVAL, "oww_bank_add: has_layernorm = %d", has_ln);
+    const size_t K = (size_t)T * 96;
+    const size_t per_net = K * H + H + (has_ln ? 2 * H : 0) + ((size_t)H * H + H + (has_ln ? 2 * H : 0)) + H + 1;
+    if (nbytes != 32 + per_net * 4) return fail(OWW_EINVAL, "oww_bank_add: blob is %zu bytes, expected %zu", nbytes, 32 + per_net * 4);
+    const float* q = (const float*)((const char*)blob + 32);
+    for (size_t i = 0; i < per_net; ++i)
+        if (!std::isfinite(q[i])) return fail(OWW_EINVAL, "oww_bank_add: head weights are not finite (float %zu of the blob)", i);
+    int id = -1;
+    for (int b = 0; b < h->bank_cap && id < 0; ++b) if (!h->bank[b].live) id = b;
+    if (id < 0) return fail(OWW_EINVAL, "oww_bank_add: the bank is full (capacity %d)", h->bank_cap);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    // ---- pack exactly as oww_commit packs a fixed net of the same width (ht 4: <= 64 units, ht 8: <= 128)
+    const float *w1 = q, *b1 = w1 + K * H, *ln1g = has_ln ? b1 + H : nullptr, *ln1b = has_ln ? b1 + 2 * H : nullptr;
+    const float* w2 = b1 + H + (has_ln ? 2 * H : 0);
+    const float *b2 = w2 + (size_t)H * H, *ln2g = has_ln ? b2 + H : nullptr, *ln2b = has_ln ? b2 + 2 * H : nullptr;
+    const float* w3 = b2 + H + (has_ln ? 2 * H : 0);
+    const float* b3 = w3 + H;
+    const int ht = H <= 64 ? 4 : 8, HP = 16 * ht;
+    const int e1 = hx_weight_exp(w1, K * H), e2 = hx_weight_exp(w2, (size_t)H * H), e3 = ht == 8 ? hx_weight_exp(w3, (size_t)H) : 0;
+    if (e1 == -1000 || e2 == -1000 || e3 == -1000) return fail(OWW_EINVAL, "oww_bank_add: head weights are not finite");
+    HostBuf hb;
+    std::vector<float> wcat(K * HP, 0.f), pk;
+    for (size_t k = 0; k < K; ++k) memcpy(&wcat[k * HP], w1 + k * H, H * sizeof(float));
+    std::vector<double> colmul(HP, std::ldexp(1.0, e1));
+    pack_hx_w1(wcat.data(), (int)K, HP, colmul.data(), pk);
+    const size_t o_w1 = hb.add(pk);
+    const size_t w1_floats = pk.size();
+    std::vector<double> cm2(HP, std::ldexp(1.0, e2));
+    HxFold f2; f2.colmul = cm2.data();
+    std::vector<float> w2p((size_t)HP * HP, 0.f);
+    for (int i = 0; i < H; ++i) memcpy(&w2p[(size_t)i * HP], w2 + (size_t)i * H, H * sizeof(float));
+    pack_hx(w2p.data(), 1, HP, HP, pk, &f2);
+    const size_t o_w2 = hb.add(pk);
+    size_t o_w3 = 0;
+    std::vector<float> pad;
+    if (ht == 4) {                                       // b1, ln1g, ln1b, b2, ln2g, ln2b, w3 | b3
+        pad.assign(7 * 64 + 4, 0.f);
+        const float* src[7] = {b1, ln1g, ln1b, b2, ln2g, ln2b, w3};
+        for (int a = 0; a < 7; ++a) if (src[a]) memcpy(&pad[a * 64], src[a], H * sizeof(float));
+        pad[7 * 64] = b3[0];
+    } else {                                             // b1, ln1g, ln1b, b2, ln2g, ln2b | b3 padded to 16
+        pad.assign(6 * HP + 16, 0.f);
+        const float* src[6] = {b1, ln1g, ln1b, b2, ln2g, ln2b};
+        for (int a = 0; a < 6; ++a) if (src[a]) memcpy(&pad[a * HP], src[a], H * sizeof(float));
+        pad[6 * HP] = b3[0];
+        std::vector<double> cm3(16, std::ldexp(1.0, e3));
+        HxFold f3; f3.colmul = cm3.data();
+        std::vector<float> w3p((size_t)HP * 16, 0.f);
+        for (int i = 0; i < H; ++i) w3p[(size_t)i * 16] = w3[i];
+        pack_hx(w3p.data(), 1, HP, 16, pk, &f3);
+        o_w3 = hb.add(pk);
+    }
+    const size_t o_pad = hb.add(pad);
+    float* d_img = nullptr;
+    HIPCHK(dev_alloc(&d_img, hb.data.size() * sizeof(float)));
+    if (copy_sync(d_img, hb.data.data(), hb.data.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)dev_free(d_img);
+        return fail(OWW_EHIP, "oww_bank_add: weight upload failed");
+    }
+    owh::BankHeadDev dv{};
+    dv.w1hx = d_img + o_w1; dv.T = T; dv.ht = ht;
+    owh::HeadHxNet& o = dv.net;
+    const float* pd = d_img + o_pad;
+    o.w2hx = d_img + o_w2; o.b1 = pd; o.ln1g = pd + HP; o.ln1b = pd + 2 * HP; o.b2 = pd + 3 * HP; o.ln2g = pd + 4 * HP; o.ln2b = pd + 5 * HP;
+    o.has_ln = has_ln; o.role = 0; o.head = 0; o.out_col = 0; o.hidden = H; o.inv_hidden = 1.0f / (float)H;
+    o.u1 = std::ldexp(1.0f, -(h->hx_efeat + e1)); o.u2 = std::ldexp(1.0f, -e2);
+    o.n_out = 1; o.final_act = 0;
+    if (ht == 4) { o.w3 = pd + 6 * HP; o.b3 = pd + 7 * 64; }
+    else { o.w3 = nullptr; o.b3 = pd + 6 * HP; o.w3hx = d_img + o_w3; o.u3 = std::ldexp(1.0f, -e3); }
+    // ---- self-test: the routed kernel on windows of the commit's probe embeddings against float64, the tolerance oww_commit holds
+    //      fixed heads to (1e-3)
+    const int NP = 32, CT = 16;
+    const int B = std::min(64, std::max(1, h->probe_nb) * NP);      // (64 windows: ~10 ms of float64 per head)
+    std::vector<float> win((size_t)B * K, 0.f);
+    for (int w = 0; w < B && !h->probe_emb.empty(); ++w) {
+        const int bt0 = (w / NP) * CT, pr = w % NP;
+        for (int r = 0; r < T; ++r) {
+            const int fr = CT - T + r;                  // window ends on the batch's last frame; rows before its first frame stay 0
+            if (fr < 0) continue;
+            memcpy(&win[((size_t)w * T + r) * 96], &h->probe_emb[(((size_t)bt0 + fr) * NP + pr) * 96], 96 * sizeof(float));
+        }
+    }
+    float *d_win = nullptr, *d_out = nullptr; int* d_ent = nullptr; owh::BankTile* d_til = nullptr; owh::BankHeadDev* d_hd = nullptr;
+    std::vector<int> ent(B);
+    for (int i = 0; i < B; ++i) ent[i] = i;
+    std::vector<owh::BankTile> til;
+    for (int o0 = 0; o0 < B; o0 += 128) til.push_back(owh::BankTile{0, o0, std::min(128, B - o0), 0});
+    std::vector<float> got(B, 0.f);
+    int rc = 0;
+    if (dev_alloc(&d_win, win.size() * sizeof(float)) != hipSuccess || dev_alloc(&d_out, (size_t)B * sizeof(float)) != hipSuccess ||
+        dev_alloc(&d_ent, (size_t)B * sizeof(int)) != hipSuccess || dev_alloc(&d_til, til.size() * sizeof(owh::BankTile)) != hipSuccess ||
+        dev_alloc(&d_hd, sizeof(owh::BankHeadDev)) != hipSuccess) rc = fail(OWW_ENOMEM, "oww_bank_add: out of device memory (self-test)");
+    if (!rc && (copy_sync(d_win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+                copy_sync(d_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+                copy_sync(d_til, til.data(), til.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice) != hipSuccess ||
+                copy_sync(d_hd, &dv, sizeof dv, hipMemcpyHostToDevice) != hipSuccess)) rc = fail(OWW_EHIP, "oww_bank_add: self-test upload failed");
+    const int flag_before = h->h_range ? *(volatile int*)h->h_range : 0;
+    if (!rc) {
+        if (int r2 = bank_quiesce(h)) rc = r2;
+    }
+    if (!rc) {
+        owh::BankParams bp{};
+        bp.feat = d_win; bp.ext = 1; bp.TR = T; bp.tiles = d_til; bp.entries = d_ent; bp.heads = d_hd; bp.K = 1;
+        bp.raw = d_out; bp.range_flag = h->d_range; bp.fscale = std::ldexp(1.0f, h->hx_efeat);
+        if (ht == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 4>), dim3((unsigned)til.size()), dim3(256), 0, h->stream, bp);
+        else hipLaunchKernelGGL((owh::heads_bank_kernel<4, 8>), dim3((unsigned)til.size()), dim3(256), 0, h->stream, bp);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+            copy_sync(got.data(), d_out, (size_t)B * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(OWW_EHIP, "oww_bank_add: self-test run failed");
+    }
+    for (void* ptr : {(void*)d_win, (void*)d_out, (void*)d_ent, (void*)d_til, (void*)d_hd}) if (ptr) (void)dev_free(ptr);
+    double err = 0.0;
+    bool finite = true;
+    for (int w = 0; w < B && !rc; ++w) {
+        finite = finite && std::isfinite(got[w]);
+        err = std::max(err, std::fabs((double)got[w] - bank_eval_f64(q, T, H, has_ln, &win[(size_t)w * K])));
+    }
+    const bool raised = h->h_range && *(volatile int*)h->h_range && !flag_before;
+    if (raised) *(volatile int*)h->h_range = 0;                 // (the self-test's own overflow is not the streams')
+    if (!rc && (!finite || err > 1e-3 || raised))
+        rc = fail(OWW_ERANGE, "oww_bank_add: with these weights the fp16-split heads kernel differs from a float64 evaluation by %.3g on the "
+                  "commit's probe embeddings (tolerance 1e-3)%s: load the head as a fixed head of a use_mfma = 1 handle", err,
+                  raised ? ", an activation left the f16 range" : "");
+    if (rc) { (void)dev_free(d_img); return rc; }
+    HIPCHK(copy_sync(h->d_bank_heads + id, &dv, sizeof dv, hipMemcpyHostToDevice));
+    oww_ctx::BankHead& bh = h->bank[id];
+    bh = oww_ctx::BankHead{};
+    bh.live = true; bh.T = T; bh.hidden = H; bh.has_ln = has_ln; bh.ht = ht; bh.d_img = d_img; bh.dev = dv;
+    bh.w1_bytes = w1_floats * sizeof(float);
+    const int pat0 = 0; const float thr0 = NAN;
+    HIPCHK(copy_sync(h->d_bank_pat + id, &pat0, sizeof pat0, hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(h->d_bank_thr + id, &thr0, sizeof thr0, hipMemcpyHostToDevice));
+    return id;
+    OWW_GUARD_END
+}
+
+int oww_bank_remove(oww_ctx* h, int32_t id) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_bank_remove: no bank on this handle");
+    if (id < 0 || id >= h->bank_cap || !h->bank[id].live) return fail(OWW_EINVAL, "oww_bank_remove: %d is not a bank head", id);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = bank_quiesce(h)) return rc;
+    std::vector<int> changed;
+    for (int i = 0; i < h->S * h->bank_K; ++i) if (h->bank_sub[i] == id) { h->bank_sub[i] = -1; changed.push_back(i); }
+    if (!changed.empty()) HIPCHK(copy_sync(h->d_bank_sub, h->bank_sub.data(), h->bank_sub.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (int rc = bank_clear(h, changed)) return rc;
+    (void)dev_free(h->bank[id].d_img);
+    h->bank[id] = oww_ctx::BankHead{};
+    return bank_route(h);
+    OWW_GUARD_END
+}
+
+int oww_bank_set_postproc(oww_ctx* h, int32_t id, int32_t patience, float threshold) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_bank_set_postproc: no bank on this handle");
+    if (id < 0 || id >= h->bank_cap || !h->bank[id].live) return fail(OWW_EINVAL, "oww_bank_set_postproc: %d is not a bank head", id);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(copy_async(h->d_bank_pat + id, &patience, sizeof patience, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(copy_async(h->d_bank_thr + id, &threshold, sizeof threshold, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->bank[id].patience = patience; h->bank[id].threshold = threshold;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_subscribe(oww_ctx* h, const int32_t* stream_ids, int32_t n, const int32_t* bank_ids) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_subscribe: no bank on this handle");
+    if (n < 0 || (n > 0 && (!stream_ids || !bank_ids))) return fail(OWW_EINVAL, "oww_subscribe: bad argument");
+    const int K = h->bank_K;
+    for (int i = 0; i < n; ++i) {
+        if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return fail(OWW_EINVAL, "oww_subscribe: stream id %d out of range (0..%d)", stream_ids[i], h->S - 1);
+        for (int k = 0; k < K; ++k) {
+            const int b = bank_ids[(size_t)i * K + k];
+            if (b != -1 && (b < 0 || b >= h->bank_cap || !h->bank[b].live))
+                return fail(OWW_EINVAL, "oww_subscribe: %d is not a bank head (stream %d, slot %d)", b, stream_ids[i], k);
+        }
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = bank_quiesce(h)) return rc;
+    std::vector<int> changed;
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < K; ++k) {
+            const size_t at = (size_t)stream_ids[i] * K + k;
+            const int b = bank_ids[(size_t)i * K + k];
+            if (h->bank_sub[at] != b) { h->bank_sub[at] = b; changed.push_back((int)at); }    // a new head in the slot starts afresh
+        }
+    if (changed.empty()) return OWW_OK;
+    HIPCHK(copy_sync(h->d_bank_sub, h->bank_sub.data(), h->bank_sub.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (int rc = bank_clear(h, changed)) return rc;
+    return bank_route(h);
+    OWW_GUARD_END
+}
+
+int oww_bank_scores(oww_ctx* h, float* out) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_bank_scores: no bank on this handle");
+    if (!out) return fail(OWW_EINVAL, "oww_bank_scores: null output");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(copy_sync(out, h->d_bank_scores, (size_t)h->S * h->bank_K * sizeof(float), hipMemcpyDeviceToHost));
+    return range_check(h, "oww_bank_scores");
+    OWW_GUARD_END
+}
+
+const float* oww_bank_scores_dev(const oww_ctx* h) { return h && h->committed ? h->d_bank_scores : nullptr; }
+
+int oww_bank_routing(oww_ctx* h, int32_t info[6], double* weight_bytes) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_bank_routing: no bank on this handle");
+    if (info)
+        for (int c = 0; c < 2; ++c) { info[3 * c] = h->bank_ntiles[c]; info[3 * c + 1] = h->bank_wg[c]; info[3 * c + 2] = h->bank_entries_n[c]; }
+    if (weight_bytes) *weight_bytes = h->bank_wbytes;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
 int oww_comm_id(void* id) {
     OWW_GUARD_BEGIN
     if (!id) return fail(OWW_EINVAL, "oww_comm_id: null argument");

@@ -2152,4 +2152,388 @@ __global__ __launch_bounds__(64 * WG, (NBUF > 2 ? 1 : 2)) void heads_hx_kernel(H
     }
 }
 
+// The routed bank kernel's first GEMM: K = 96 T features (k-steps of 32) x NCT hidden tiles of 16, weights w1hx streamed through the
+// LDS ring (chunk 0 already issued by the caller, into hslot<CHUNK, 0>), each lane's features fetched by load_raw(k-step, regs) and split
+// into hi / lo halves once scaled by fsc.  This, net64_score and wide_net_eval are heads_hx_kernel's k loop and net tails as functions:
+// the same MFMAs and fp32 operations in the same order, so a bank head scores bit for bit what the same net scores as a fixed head
+// (tests/test_head_bank_gpu.py).  heads_hx_kernel itself keeps its inline body: moved onto these functions its register allocation
+// changed (SGPR spills to VGPR lanes, +150..340 instructions per instantiation) and the flagship launch is not to move.
+template <int NCT, int NBUF, int WG, class LoadRaw>
+__device__ __forceinline__ void heads_gemm1(const float* __restrict__ w1hx, const int KST, const float fsc, LoadRaw&& load_raw,
+                                            f32x4 (&acc)[NCT][2], const int wave, const int lane) {
+    using namespace owr;
+    constexpr int NBLK = NCT * 2;               // 1 KB blocks per k-step chunk
+    constexpr int CHUNK = NBLK * 256;           // floats
+    constexpr int D = NBUF - 1;                 // chunks in flight ahead of the one being consumed
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) { acc[ct][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[ct][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    Op bcur[2];
+    f32x4 raw[NBUF][2][2];                      // feature rows of the k-steps in flight (slot = k-step mod NBUF, static after unrolling)
+#pragma unroll
+    for (int c = 0; c < D; ++c)
+        if (c < KST) {
+            if (c > 0) issue_chunk<NBLK, WG>(w1hx + (size_t)c * CHUNK, hslot_at<CHUNK, NBUF - 1>(c), wave, lane);     // (chunk 0: issued at kernel start)
+            asm volatile("" ::: "memory");      // program order = issue order: chunk c, then the features of k-step c
+            load_raw(c, raw[c]);
+        }
+    bcur[0] = split_pair<false>(raw[0][0][0] * fsc, raw[0][0][1] * fsc);
+    bcur[1] = split_pair<false>(raw[0][1][0] * fsc, raw[0][1][1] * fsc);    // (waiting for these features = chunk 0 has landed: in-order return)
+    pin_op(bcur[0]); pin_op(bcur[1]);
+    __syncthreads();
+    // one k-step: ring slot u (static), prefetch of k-step ks + D into slot (u + D) % NBUF, MFMAs, hand-over to k-step ks + 1
+    auto kstep = [&](int ks, auto uc, auto always) {
+        constexpr int u = decltype(uc)::value;
+        constexpr bool ALWAYS = decltype(always)::value;        // main loop: every k-step of the group prefetches and has a successor
+        const float* cur = hslot_at<CHUNK, NBUF - 1>(u);
+        if (ALWAYS || ks + D < KST) {                           // slot of k-step ks-1: every wave passed the last barrier, its features are split
+            constexpr int un = (u + D) % NBUF;
+            issue_chunk<NBLK, WG>(w1hx + (size_t)(ks + D) * CHUNK, hslot_at<CHUNK, NBUF - 1>(un), wave, lane);
+            asm volatile("" ::: "memory");
+            load_raw(ks + D, raw[un]);
+        }
+#if OWH_HEADS_APIPE
+        // A operands (four 1 KB weight blocks per pair of hidden tiles) one pair AHEAD of the MFMAs that consume them: left alone the
+        // compiler issues a pair's four ds_read_b128 next to the last MFMA of the pair before and waits lgkmcnt(0) in front of the next
+        // twelve -- ~100 cycles of LDS latency in the open per 192 MFMA cycles.  LDS reads return in order, so the wait in front of a
+        // pair is lgkmcnt(4): its own reads done, the next pair's in flight.  Same MFMAs in the same order: bit-identical.
+        f16x8 A[2][4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) A[0][b] = lds_h(cur, b, lane);
+#pragma unroll
+        for (int c2 = 0; c2 < NCT; c2 += 2) {
+            const int pc = (c2 / 2) & 1;
+            if (c2 + 2 < NCT) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b) A[pc ^ 1][b] = lds_h(cur, (c2 + 2) * 2 + b, lane);
+            }
+            __builtin_amdgcn_sched_barrier(0);                  // (the reads stay in front of this pair's MFMAs)
+#pragma unroll
+            for (int part = 0; part < 3; ++part) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    acc[c2][t] = OWH_MFMA(part == 2 ? A[pc][1] : A[pc][0], part == 1 ? bcur[t].l : bcur[t].h, acc[c2][t]);
+                    acc[c2 + 1][t] = OWH_MFMA(part == 2 ? A[pc][3] : A[pc][2], part == 1 ? bcur[t].l : bcur[t].h, acc[c2 + 1][t]);
+                }
+            }
+        }
+#else
+#pragma unroll
+        for (int c2 = 0; c2 < NCT; c2 += 2) {
+            const f16x8 ah0 = lds_h(cur, c2 * 2 + 0, lane), al0 = lds_h(cur, c2 * 2 + 1, lane);
+            const f16x8 ah1 = lds_h(cur, c2 * 2 + 2, lane), al1 = lds_h(cur, c2 * 2 + 3, lane);
+#pragma unroll
+            for (int part = 0; part < 3; ++part) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    acc[c2][t] = OWH_MFMA(part == 2 ? al0 : ah0, part == 1 ? bcur[t].l : bcur[t].h, acc[c2][t]);
+                    acc[c2 + 1][t] = OWH_MFMA(part == 2 ? al1 : ah1, part == 1 ? bcur[t].l : bcur[t].h, acc[c2 + 1][t]);
+                }
+            }
+        }
+#endif
+        if (ALWAYS || ks + 1 < KST) {
+            // k-step ks+1: its features are younger than its weight chunk, so the split's wait covers this wave's part of the chunk;
+            // the barrier covers the other waves' parts.  Everything issued for k-steps ks+2 .. ks+D stays in flight.
+            constexpr int u1 = (u + 1) % NBUF;
+            __builtin_amdgcn_sched_barrier(0);                  // the split (and the wait for its features) stays BEHIND this k-step's MFMAs
+            bcur[0] = split_pair<false>(raw[u1][0][0] * fsc, raw[u1][0][1] * fsc);
+            bcur[1] = split_pair<false>(raw[u1][1][0] * fsc, raw[u1][1][1] * fsc);
+            pin_op(bcur[0]); pin_op(bcur[1]);                   // (the split -- and with it the wait -- stays in front of the barrier)
+            // a bare s_barrier: __syncthreads() carries a workgroup-scope release fence, which on this target is s_waitcnt vmcnt(0) --
+            // it would drain every prefetch in flight at every k-step.  What the barrier has to order is already ordered: this wave's
+            // part of chunk ks+1 has landed (the wait above), its LDS reads of chunk ks have returned (they fed the MFMAs above), and
+            // the memory clobber keeps the compiler from moving LDS accesses across it.
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // (lgkmcnt(0): this wave's reads of the slot have returned)
+        }
+    };
+    auto group = [&](int ks0, auto always) {                    // NBUF consecutive k-steps, slots 0 .. NBUF-1
+        constexpr bool ALWAYS = decltype(always)::value;
+        static_for_while<0, NBUF>([&](auto uc) {
+            constexpr int U = decltype(uc)::value;
+            if (!ALWAYS && ks0 + U >= KST) return false;
+            kstep(ks0 + U, uc, always);
+            return true;
+        });
+    };
+    int ks0 = 0;
+    // main loop: straight-line groups (no conditional issue: the compiler's wait counts stay exact, nothing waits for the newest prefetch)
+    for (; ks0 + NBUF - 1 + D < KST; ks0 += NBUF) group(ks0, std::true_type{});
+    for (; ks0 < KST; ks0 += NBUF) group(ks0, std::false_type{});        // the last D .. NBUF + D - 1 k-steps
+}
+
+// one 64-unit net behind its first GEMM (heads_hx_kernel's tail for one net) (h1: its four hidden tiles of one stream tile): bias, LayerNorm, ReLU, 64 x 64, bias, LayerNorm,
+// ReLU, dot, sigmoid -> the score of this lane's stream (every lane group j holds it)
+template <int NN>
+__device__ __forceinline__ float net64_score(const HeadHxNet& net, f32x4 (&h1)[4], lanemask_t& bad, const int j, const int lane) {
+    ln_relu<NN>(h1, net.b1, net.ln1g, net.ln1b, net.has_ln, j, net.u1, net.hidden, net.inv_hidden);
+    Op ho[2];
+    to_ops<4>(h1, ho);
+    f32x4 h2[4];
+#pragma unroll
+    for (int oct = 0; oct < 4; ++oct) {
+        f32x4 a2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+            const f16x8 wh = *reinterpret_cast<const f16x8*>(net.w2hx + (((oct * 2 + k2) * 2 + 0) * 64 + lane) * 4);
+            const f16x8 wl = *reinterpret_cast<const f16x8*>(net.w2hx + (((oct * 2 + k2) * 2 + 1) * 64 + lane) * 4);
+            a2 = OWH_MFMA(wh, ho[k2].h, a2);
+            a2 = OWH_MFMA(wh, ho[k2].l, a2);
+            a2 = OWH_MFMA(wl, ho[k2].h, a2);
+        }
+        h2[oct] = a2;
+        if (oct == 0) nan_guard(bad, a2[0]);
+    }
+    ln_relu<NN>(h2, net.b2, net.ln2g, net.ln2b, net.has_ln, j, net.u2, net.hidden, net.inv_hidden);
+    float z = 0.f;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        const f32x4 w3 = *reinterpret_cast<const f32x4*>(net.w3 + ct * 16 + 4 * j);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) z = fmaf(h2[ct][e], w3[e], z);
+    }
+    z = xsum4(z) + net.b3[0];
+    return 1.0f / (1.0f + expf(-z));
+}
+
+// one wide net (HT hidden tiles, up to 8 outputs) behind its first GEMM (acc[HT n0 ..][t]) for both stream tiles of the wave:
+// v[t][e] = output 4j + e of this lane's stream in tile t
+// one wide net (HT hidden tiles, up to 8 outputs) behind its first GEMM (acc[HT n0 ..][t]) for both stream tiles of the wave:
+// v[t][e] = output 4j + e of this lane's stream in tile t
+template <int HT, int NCT>
+__device__ __forceinline__ void wide_net_eval(const HeadHxNet& net, const f32x4 (&acc)[NCT][2], const int n0, float (&v)[2][4], lanemask_t& bad,
+                                              const int j, const int lane) {
+    constexpr int KS = HT / 2;                  // k-steps of a hidden vector
+    const int n = n0;
+    Op ho[2][KS];
+    int ex[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        f32x4 h1[HT];
+#pragma unroll
+        for (int ct = 0; ct < HT; ++ct) h1[ct] = acc[HT * n + ct][t];
+        ln_relu_w<HT>(h1, net.b1, net.ln1g, net.ln1b, net.has_ln, j, net.u1, 0, net.hidden, net.inv_hidden);
+        ex[t] = scale_own<HT>(h1);
+        to_ops<HT>(h1, ho[t]);
+    }
+    // ---- hidden block: 128 x 128, one output tile at a time, each weight block read once for both stream tiles
+    f32x4 h2[2][HT];
+#pragma unroll
+    for (int oct = 0; oct < HT; ++oct) {
+        f32x4 a2[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int k2 = 0; k2 < KS; ++k2) {
+            const f16x8 wh = *reinterpret_cast<const f16x8*>(net.w2hx + (((oct * KS + k2) * 2 + 0) * 64 + lane) * 4);
+            const f16x8 wl = *reinterpret_cast<const f16x8*>(net.w2hx + (((oct * KS + k2) * 2 + 1) * 64 + lane) * 4);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                a2[t] = OWH_MFMA(wh, ho[t][k2].h, a2[t]);
+                a2[t] = OWH_MFMA(wh, ho[t][k2].l, a2[t]);
+                a2[t] = OWH_MFMA(wl, ho[t][k2].h, a2[t]);
+            }
+        }
+        h2[0][oct] = a2[0]; h2[1][oct] = a2[1];
+        if (oct == 0) { nan_guard(bad, a2[0][0]); nan_guard(bad, a2[1][0]); }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        ln_relu_w<HT>(h2[t], net.b2, net.ln2g, net.ln2b, net.has_ln, j, net.u2, -ex[t], net.hidden, net.inv_hidden);
+        ex[t] = scale_own<HT>(h2[t]);
+        to_ops<HT>(h2[t], ho[t]);
+    }
+    // ---- output layer: 16 rows (n_out real ones) x 128 -- lane (pos, j), register e <-> output 4j + e of stream pos
+    f32x4 z[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int k2 = 0; k2 < KS; ++k2) {
+        const f16x8 wh = *reinterpret_cast<const f16x8*>(net.w3hx + ((k2 * 2 + 0) * 64 + lane) * 4);
+        const f16x8 wl = *reinterpret_cast<const f16x8*>(net.w3hx + ((k2 * 2 + 1) * 64 + lane) * 4);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            z[t] = OWH_MFMA(wh, ho[t][k2].h, z[t]);
+            z[t] = OWH_MFMA(wh, ho[t][k2].l, z[t]);
+            z[t] = OWH_MFMA(wl, ho[t][k2].h, z[t]);
+        }
+    }
+    const f32x4 b3 = *reinterpret_cast<const f32x4*>(net.b3 + 4 * j);
+    const int O = net.n_out;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        nan_guard(bad, z[t][0]);
+        if (net.final_act == 1) {                                   // ReLU, then softmax over the n_out outputs (rows 0..7: lane groups 0, 1)
+            float mx = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[t][e] = fmaxf(ldexpf(z[t][e] * net.u3, -ex[t]) + b3[e], 0.f);
+                if (4 * j + e < O) mx = fmaxf(mx, v[t][e]);
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            float sum = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[t][e] = 4 * j + e < O ? expf(v[t][e] - mx) : 0.f; sum += v[t][e]; }
+            sum += __shfl_xor(sum, 16);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[t][e] /= sum;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[t][e] = 1.0f / (1.0f + expf(-(ldexpf(z[t][e] * net.u3, -ex[t]) + b3[e])));
+        }
+    }
+}
+
+// ---- head bank: routed f16-split heads (oww_bank_*) ---------------------------------------------------------------------------------
+// A bank head is a binary, ungated, one-block net packed exactly like a fixed net of the same width (one net per launch slot: its own
+// w1hx chunk ring, w2hx, padded per-unit arrays).  The work list is a table of tiles, each (bank head, offset and count into an entry list
+// sorted by head); an entry is stream * K + slot, the index of the (stream, slot) pair in the bank's [S][K] arrays.  One workgroup runs
+// one tile: the head's first-layer weights stream L2 -> LDS once per tile (heads_gemm1), the listed streams' ring rows are gathered, and
+// the net's tail is net64_score / wide_net_eval -- the code the fixed heads kernel runs, so a bank head scores bit for bit what the same
+// net scores as a fixed head.  Tiles are ordered largest first (no lone large tile ends the launch); WG is chosen per launch from the
+// group sizes (oww_bank_*: 4 waves = 128 entries for large groups, 1 wave = 32 for small ones).
+#ifndef OWH_BANK_PER_HEAD
+#define OWH_BANK_PER_HEAD 0    // 1: the routed launch issued as one launch per bank head (tools/bench_head_bank.py, setting d)
+#endif
+struct BankTile { int head, off, n, pad; };
+struct BankHeadDev {
+    const float* w1hx;       // [T*3 ksteps][HT ct][2 part][64][8 halves]
+    HeadHxNet net;
+    int T, ht;
+};
+struct BankParams {
+    const float* feat;       // ring [S][TR][96], or external [B][T][96] (ext != 0: the self-test of oww_bank_add)
+    int ext, TR;
+    const uint32_t* nfeat;   // ring row counters; nfeat_adv = 1 when this step's counter advance has already run (block-pipelined step)
+    int nfeat_adv;
+    const BankTile* tiles;
+    const int* entries;
+    const BankHeadDev* heads;
+    int K;
+    float* raw;              // [S][K]
+    int accumulate_max;
+    int* range_flag;
+    const uint8_t* stream_on;
+    float fscale;
+};
+template <int WG, int HT, int NBUF = HX_NBUF>
+__global__ __launch_bounds__(64 * WG, 2) void heads_bank_kernel(BankParams p) {
+    using namespace owr;
+    constexpr int NCT = HT;
+    constexpr int NBLK = NCT * 2;
+    constexpr int CHUNK = NBLK * 256;
+    const int lane = threadIdx.x & 63, pos = lane & 15, j = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const BankTile tile = p.tiles[blockIdx.x];
+    const BankHeadDev* hd = p.heads + tile.head;
+    const float* w1hx = hd->w1hx;
+    const int T = hd->T;
+    issue_chunk<NBLK, WG>(w1hx, hslot<CHUNK, 0>(), wave, lane);
+    int e[2], s[2];
+    const float* frow[2];
+    uint32_t slot0[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int idx = wave * 32 + t * 16 + pos;
+        e[t] = p.entries[tile.off + min(idx, tile.n - 1)];
+        s[t] = e[t] / p.K;
+        if (p.ext) { frow[t] = p.feat + (size_t)s[t] * T * 96; slot0[t] = 0; }
+        else { frow[t] = p.feat + (size_t)s[t] * p.TR * 96; slot0[t] = p.nfeat[s[t]] + (uint32_t)(2 * p.TR - T + 1 - p.nfeat_adv); }
+    }
+    auto load_raw = [&](int ks, f32x4 (&r)[2][2]) {
+        const int tr = ks / 3, c0 = (ks % 3) * 32 + 8 * j;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const uint32_t slot = p.ext ? (uint32_t)tr : (slot0[t] + (uint32_t)tr) % (uint32_t)p.TR;
+            const float* src = frow[t] + (size_t)slot * 96 + c0;
+            r[t][0] = *reinterpret_cast<const f32x4*>(src);
+            r[t][1] = *reinterpret_cast<const f32x4*>(src + 4);
+        }
+    };
+    f32x4 acc[NCT][2];
+    heads_gemm1<NCT, NBUF, WG>(w1hx, T * 3, p.fscale, load_raw, acc, wave, lane);
+    lanemask_t bad = 0;
+    nan_guard(bad, acc[0][0][0]);
+    nan_guard(bad, acc[0][1][0]);
+    const HeadHxNet net = hd->net;
+    float score[2];
+    if constexpr (HT == 4) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            f32x4 h1[4] = {acc[0][t], acc[1][t], acc[2][t], acc[3][t]};
+            score[t] = net64_score<1>(net, h1, bad, j, lane);
+        }
+    } else {
+        float v[2][4];
+        wide_net_eval<HT, NCT>(net, acc, 0, v, bad, j, lane);
+        score[0] = v[0][0]; score[1] = v[1][0];             // (one output: row 0 = lane group 0, register 0)
+    }
+    if (j == 0) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int idx = wave * 32 + t * 16 + pos;
+            if (idx >= tile.n) continue;
+            if (p.stream_on && !p.stream_on[s[t]]) continue;          // sits this step out: its bank state stays as it is
+            float* o = p.raw + e[t];
+            *o = p.accumulate_max ? fmaxf(*o, score[t]) : score[t];
+        }
+    }
+    raise_range_flag(bad, p.range_flag);
+}
+
+// Model.predict's post-processing (model.py:330-381) per (stream, slot) of the bank, the rules of owk::postproc_kernel in the same
+// order: first-5 zeroing on the slot's own prediction count, patience / debounce over the slot's 30-deep ring (per bank head; debounce
+// frames shared with the handle), ring append, the stream's VAD gate.  An empty slot (head -1) scores 0.
+struct BankPostParams {
+    const float* raw; float* scores; float* ring; uint32_t* npred;
+    const int* sub;                   // [S][K] bank head of each slot, -1 = empty
+    const int* patience; const float* threshold; int debounce_frames;
+    int S, K;
+    const float* vad_ring; const uint32_t* n_vad; float vad_threshold;
+    const uint8_t* stream_on;
+};
+__global__ void bank_post_kernel(BankPostParams p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.S * p.K) return;
+    const int s = i / p.K;
+    if (p.stream_on && !p.stream_on[s]) return;
+    const int hd = p.sub[i];
+    if (hd < 0) { p.scores[i] = 0.0f; return; }
+    const uint32_t cnt = p.npred[i];
+    const int have = cnt < 30u ? (int)cnt : 30;
+    float sc = p.raw[i];
+    float* ring = p.ring + (size_t)i * 30;
+    if (cnt < 5u) sc = 0.0f;                                                // model.py:331-333
+    if (sc != 0.0f) {
+        const int pat = p.patience[hd];
+        const float thr = p.threshold[hd];
+        if (pat > 0) {                                                      // model.py:349-352
+            const int look = pat < have ? pat : have;
+            int n_ok = 0;
+            for (int k = 1; k <= look; ++k) n_ok += ring[(cnt - k) % 30u] >= thr ? 1 : 0;
+            if (n_ok < pat) sc = 0.0f;
+        } else if (p.debounce_frames > 0 && thr == thr) {                   // model.py:353-359
+            const int look = p.debounce_frames < have ? p.debounce_frames : have;
+            int n_hit = 0;
+            for (int k = 1; k <= look; ++k) n_hit += ring[(cnt - k) % 30u] >= thr ? 1 : 0;
+            if (sc >= thr && n_hit > 0) sc = 0.0f;
+        }
+    }
+    ring[cnt % 30u] = sc;                                                   // model.py:362-363
+    p.npred[i] = cnt + 1u;
+    if (p.vad_threshold > 0.0f) {                                           // model.py:375-381
+        const uint32_t L = p.n_vad[s];
+        float vmax = 0.0f;
+        if (L >= 5u) {
+            vmax = -INFINITY;
+            for (uint32_t k = (L >= 7u ? L - 7u : 0u); k + 5u <= L; ++k) vmax = fmaxf(vmax, p.vad_ring[(size_t)s * 8 + (k & 7u)]);
+        }
+        if (vmax < p.vad_threshold) sc = 0.0f;
+    }
+    p.scores[i] = sc;
+}
+// restart of bank slots (a new head subscribed, oww_reset): prediction count, ring, raw and final score of each listed slot index
+__global__ void bank_clear_kernel(const int* idx, int n, float* raw, float* scores, float* ring, uint32_t* npred) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int k = idx[i];
+    raw[k] = 0.0f; scores[k] = 0.0f; npred[k] = 0u;
+    for (int r = 0; r < 30; ++r) ring[(size_t)k * 30 + r] = 0.0f;
+}
+
 }  // namespace owh

@@ -141,12 +141,14 @@ class StreamEngine:
     def __init__(self, n_streams: int, heads: Dict[str, dict], embedding: Optional[dict] = None,
                  device: int = 0, max_chunks: int = 1, use_mfma: int = 3, debug_layers: bool = False,
                  feature_ring: int = 0, hip_stream: int = 0, vad: Optional[dict] = None, vad_threshold: float = 0.0,
-                 calibration_pcm: Union[np.ndarray, str, None] = "default"):
+                 calibration_pcm: Union[np.ndarray, str, None] = "default", bank_slots: int = 0, bank_capacity: int = 0):
         """`vad`: weights of the on-device voice-activity stand-in network (weights.synthetic_vad layout); when given, every
         step also runs it on the frame's two 640-sample sub-frames and gates the scores with `vad_threshold` (model.py:366-381).
         `calibration_pcm` (use_mfma = 3): audio of the deployment's domain, int16 [n, k * 1280], that oww_commit adds to its built-in
         probes when it calibrates the activation scales and holds the fp16-split kernels to the exact-fp32 ones; "default" = speech
-        (default_calibration_pcm), None = the synthetic probes only."""
+        (default_calibration_pcm), None = the synthetic probes only.
+        `bank_slots` > 0 (use_mfma = 3): a head bank of `bank_capacity` heads, every stream subscribed to up to `bank_slots` of them
+        (oww_bank_configure; bank_add / subscribe / bank_scores below)."""
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self._inflight: List[np.ndarray] = []
@@ -190,6 +192,9 @@ class StreamEngine:
                 n_frames = cal.shape[1] // CHUNK
                 cal = np.ascontiguousarray(cal[:, :n_frames * CHUNK])
                 _lib.check(self._lib.oww_set_calibration(self._h, _ptr(cal), cal.shape[0], n_frames))
+            self.bank_slots = int(bank_slots)
+            if self.bank_slots > 0:
+                _lib.check(self._lib.oww_bank_configure(self._h, self.bank_slots, int(bank_capacity) or 1024))
             _lib.check(self._lib.oww_commit(self._h))
             if vad_threshold:
                 _lib.check(self._lib.oww_set_vad_threshold(self._h, float(vad_threshold)))
@@ -431,6 +436,42 @@ class StreamEngine:
         Model.reset() leaves Model.vad alone (model.py:226-230); call this when a stream slot is handed to a new caller."""
         ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32)
         _lib.check(self._lib.oww_reset_vad(self._h, _ptr(ids), 0 if ids is None else ids.size))
+
+    # ---- head bank (include/owwhip.h: oww_bank_*) ----
+    def bank_add(self, head: dict) -> int:
+        """Add a head (weights.synthetic_head / onnx_ingest.load_head layout) to the bank -> bank id."""
+        blob = pack_head_blob(head)
+        rc = self._lib.oww_bank_add(self._h, _ptr(blob), blob.nbytes)
+        _lib.check(rc)
+        return int(rc)
+
+    def bank_remove(self, bank_id: int) -> None:
+        _lib.check(self._lib.oww_bank_remove(self._h, int(bank_id)))
+
+    def bank_set_postproc(self, bank_id: int, patience: int = 0, threshold: float = float("nan")) -> None:
+        _lib.check(self._lib.oww_bank_set_postproc(self._h, int(bank_id), int(patience), float(threshold)))
+
+    def subscribe(self, stream_ids: Sequence[int], bank_ids: np.ndarray) -> None:
+        """bank_ids: int [n, bank_slots] (-1 = empty slot) for the n streams of stream_ids."""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32).ravel()
+        b = np.ascontiguousarray(bank_ids, dtype=np.int32).reshape(ids.size, self.bank_slots)
+        _lib.check(self._lib.oww_subscribe(self._h, _ptr(ids), ids.size, _ptr(b)))
+
+    def bank_scores(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        if out is None:
+            out = np.empty((self.n_streams, self.bank_slots), dtype=np.float32)
+        _lib.check(self._lib.oww_bank_scores(self._h, _ptr(out)))
+        return out
+
+    def bank_scores_dev_ptr(self) -> int:
+        return int(self._lib.oww_bank_scores_dev(self._h) or 0)
+
+    def bank_routing(self) -> Dict[str, object]:
+        info = np.zeros(6, dtype=np.int32)
+        wb = C.c_double(0.0)
+        _lib.check(self._lib.oww_bank_routing(self._h, _ptr(info), C.byref(wb)))
+        return {"tiles": [int(info[0]), int(info[3])], "waves_per_tile": [int(info[1]), int(info[4])],
+                "entries": [int(info[2]), int(info[5])], "weight_bytes": float(wb.value)}
 
     def sync(self):
         _lib.check(self._lib.oww_sync(self._h))

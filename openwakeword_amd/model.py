@@ -319,6 +319,25 @@ class AudioFeatures:
         return buf[int(-1 * n_feature_frames):, :][None, ].astype(np.float32)
 
 
+def check_bank_head(head: dict, feature_ring: int) -> None:
+    """The forms the head bank's routed kernel takes (include/owwhip.h: oww_bank_add), checked before the library is touched."""
+    kind = head.get("kind")
+    if kind == "rnn":
+        raise ValueError("recurrent heads cannot go into the head bank; load them as fixed heads (wakeword_models)")
+    if kind == "gated":
+        raise ValueError("gated heads cannot go into the head bank; load them as fixed heads (wakeword_models)")
+    if kind == "multiclass" or int(head["n_out"]) != 1:
+        raise ValueError("multiclass heads cannot go into the head bank (a bank head has one sigmoid output); load them as fixed heads")
+    if kind != "binary":
+        raise ValueError(f"unknown head kind {kind!r}")
+    if len(W.net_blocks(head["net"])) != 1:
+        raise ValueError("a bank head has exactly one hidden block (train.py:73 n_blocks = 1); load other nets as fixed heads")
+    if not 1 <= int(head["hidden"]) <= 128:
+        raise ValueError(f"a bank head has at most 128 hidden units (got {head['hidden']})")
+    if not 1 <= int(head["T"]) <= int(feature_ring):
+        raise ValueError(f"the bank head's T = {head['T']} exceeds the handle's feature ring ({feature_ring} rows)")
+
+
 def make_engine(n_streams: int, heads: dict, embedding: dict, use_mfma: Optional[int] = None, **kw) -> StreamEngine:
     """The engine behind Model / BatchedModel.  `use_mfma` None = the default fp16-split family (3), and -- when oww_commit refuses
     these weights for it (OWW_ERANGE: the commit-time comparison with the exact-fp32 kernels failed, i.e. the weights' range cannot be
@@ -577,7 +596,13 @@ class BatchedModel:
     def __init__(self, n_streams: int, wakeword_models: Sequence[str], weights: Union[str, dict, None] = None,
                  device: int = 0, max_chunks: int = 1, hip_stream: int = 0, vad_weights: Optional[dict] = None,
                  vad_threshold: float = 0.0, use_mfma: Optional[int] = None, calibration_pcm="default",
-                 embedding_model_path: str = "", melspec_model_path: str = ""):
+                 embedding_model_path: str = "", melspec_model_path: str = "", bank_slots: int = 0, bank_capacity: int = 1024):
+        # bank_slots > 0: a head bank (bank_add / subscribe / bank_scores): every stream is scored by the bank heads it subscribed to,
+        # up to bank_slots of them, beside the fixed `wakeword_models` (which may then be empty)
+        if not wakeword_models and int(bank_slots) <= 0:
+            raise ValueError("BatchedModel needs wakeword_models, or a head bank (bank_slots > 0)")
+        self._weights = weights
+        self._debounce_frames = 0
         # same weight resolution as Model: real .onnx files (heads AND the shared embedding network) unless synthetic
         # weights are asked for explicitly -- never a random-init embedding under real heads
         seed, emb, given = resolve_weights(weights)
@@ -605,7 +630,9 @@ class BatchedModel:
         # calibration_pcm: audio of the deployment's domain for the commit-time calibration / self-test of the fp16-split kernels
         # (StreamEngine); "default" = speech shipped with the package
         self.engine = make_engine(n_streams, heads, emb, use_mfma, device=device, max_chunks=max_chunks, hip_stream=hip_stream,
-                                  vad=vad_weights, vad_threshold=vad_threshold, calibration_pcm=calibration_pcm)
+                                  vad=vad_weights, vad_threshold=vad_threshold, calibration_pcm=calibration_pcm,
+                                  bank_slots=int(bank_slots), bank_capacity=int(bank_capacity))
+        self.bank_slots = int(bank_slots)
         self.labels: List[str] = []
         self._keep: List[int] = []
         col = 0
@@ -639,6 +666,57 @@ class BatchedModel:
         thr = [float(threshold.get(self._parent[c], np.nan)) for c in range(NL)]
         frames = int(np.ceil(debounce_time / (chunk_samples / 16000))) if debounce_time > 0 else 0
         self.engine.set_postproc(pat, thr, frames)
+        self._debounce_frames = frames
+
+    # ---- head bank: per-stream subscriptions to wake-word heads (include/owwhip.h: oww_bank_*) ----
+    def bank_add(self, model: Union[str, dict], weights: Union[str, dict, None] = None) -> int:
+        """Add a head to the bank while the streams run -> bank id.  `model` is resolved like an entry of `wakeword_models`: a
+        pretrained name, an .onnx path (onnx_ingest.load_head), or a head dict; `weights` as in the constructor (default: the
+        constructor's).  A bank head is binary (one sigmoid output), ungated, with one hidden block of <= 128 units and T <= the
+        handle's feature ring; other forms raise ValueError (they remain available as fixed heads)."""
+        if isinstance(model, dict):
+            head = model
+        else:
+            seed, _, given = resolve_weights(self._weights if weights is None else weights)
+            head = given[model] if model in given else _load_head(model, seed)[1]
+        check_bank_head(head, self.engine.feature_ring)
+        return self.engine.bank_add(head)
+
+    def bank_remove(self, bank_id: int) -> None:
+        """Drop a bank head; the slots subscribed to it become empty (score 0)."""
+        self.engine.bank_remove(bank_id)
+
+    def subscribe(self, stream_ids: Sequence[int], bank_ids) -> None:
+        """bank_ids [len(stream_ids), bank_slots]: the bank heads of each listed stream, -1 = empty slot.  A slot whose head changes
+        starts afresh (an empty prediction buffer, as a model newly loaded into that stream's Model); nothing else of the stream moves."""
+        if self.bank_slots <= 0:
+            raise ValueError("this BatchedModel has no head bank (bank_slots = 0)")
+        ids = np.asarray(stream_ids)
+        b = np.asarray(bank_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise ValueError("stream_ids must be a 1-D integer sequence")
+        if b.dtype.kind not in "iu" or b.shape != (ids.size, self.bank_slots):
+            raise ValueError(f"bank_ids must be an integer array of shape ({ids.size}, {self.bank_slots}), got {b.dtype} {b.shape}")
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= self.n_streams):
+            raise ValueError(f"stream ids must lie in 0 .. {self.n_streams - 1}")
+        if b.size and int(b.min()) < -1:
+            raise ValueError("bank ids are >= 0, or -1 for an empty slot")
+        self.engine.subscribe(ids, b)
+
+    def set_bank_postproc(self, bank_id: int, patience: int = 0, threshold: Optional[float] = None) -> None:
+        """Model.predict's `patience` / `threshold` for one bank head, with the same errors (model.py:340-345); the debounce time
+        is the one of set_postproc, shared with the fixed heads."""
+        if patience and threshold is None:
+            raise ValueError("Error! When using the `patience` argument, threshold "
+                             "values must be provided via the `threshold` argument!")
+        if patience and self._debounce_frames > 0:
+            raise ValueError("Error! The `patience` and `debounce_time` arguments cannot be used together!")
+        self.engine.bank_set_postproc(bank_id, int(patience), float("nan") if threshold is None else float(threshold))
+
+    def bank_scores(self) -> np.ndarray:
+        """float32 [n_streams, bank_slots]: the post-processed bank scores of the last predict_batch / predict_active /
+        collect_batch (an empty slot reads 0.0)."""
+        return self.engine.bank_scores()
 
     def reset(self, stream_ids: Optional[Sequence[int]] = None, init_features: Optional[np.ndarray] = None,
               reset_vad: bool = False):
