@@ -492,7 +492,6 @@ struct oww_ctx {
     } slot[2];
     hipStream_t up_stream = nullptr, down_stream = nullptr;
     uint64_t n_submit = 0, n_collect = 0;
-    const float* mel_src = nullptr;   // when set: the CNN reads its mel rows from here instead of d_mel (oww_embed_clips)
     float* d_featinit = nullptr;
     float* d_dbg = nullptr;
     long long* d_prof = nullptr;     // [4 stages][16 waves][16 marks], allocated when OWW_PROF_BLOCK is set
@@ -513,12 +512,9 @@ struct oww_ctx {
     void* d_rs = nullptr; size_t rs_bytes = 0;     // oww_resample scratch: [taps | in | out] as needed
     std::vector<float> rs_taps;                    // the padded filter bank of the last oww_resample call (upload source)
     uint8_t* d_on = nullptr;         // oww_step_masked: [Spad] participation mask of the step being launched (pad streams 0)
-    const uint8_t* on_now = nullptr; // = d_on (or the caller's device mask) while a masked step is being launched, else nullptr
-    // masked step with few participants (host-resident mask, <= half of the streams): lists of the participating streams and of the
-    // stage groups (2 / 4 / 8 / 16 streams) that hold one; the launches of stages B..E, the heads and the VAD LSTM then cover only
-    // those (build_active_lists).  [0] = stream ids (stage B's groups and the heads' positions), [1] C, [2] D, [3] E, [4] VAD LSTM
+    // masked step with few participants: the device copy of the group lists (StepArgs::gl) and its two page-locked staging buffers,
+    // used in turn (build_active_lists)
     int* d_lists = nullptr; int* h_lists[2] = {nullptr, nullptr}; hipEvent_t lists_ev[2] = {nullptr, nullptr}; size_t lists_cap = 0; unsigned lists_turn = 0;
-    const int* gl_now[5] = {}; int gn_now[5] = {}; bool lists_now = false;
     int k_last = 1;                  // n_chunks of the last step (row stride of d_mel)
     // f16-split family: the output of layer l is carried multiplied by 2^hx_e[l], its input arrives multiplied by 2^hx_ein[l]
     // (oww_commit: calibrate_hx; owwhip_hx.h act1).  Inside a stage hx_ein[l] = hx_e[l - 1]; the pooled hand-over between two stages
@@ -526,32 +522,21 @@ struct oww_ctx {
     int hx_e[20] = {}, hx_ein[20] = {}, hx_xexp[5] = {};
     float hx_absmax[20] = {};        // largest |activation| of each layer in the calibration run (exact-fp32 kernels)
     std::vector<int16_t> cal_user;   // oww_set_calibration: caller's calibration audio as [n_seg][CAL_T * 1280] segments
-    // builds with -DOWH_DEEP_RING only (round 6 experiment, profiles/r06_deep_ring_c1.txt: bit-identical, no faster at 4,096 / 16,384 streams):
-    // launches of at most this many workgroups run a weight ring of NS = 4 / 5 slots, three / four chunks in flight; OWW_DEEP_WGS
-    int deep_wgs = 0;
     int small_wgs = kSmallLaunchWgs, small_wgs_heads = kSmallLaunchWgs;   // A/B aids: OWW_SMALL_WGS / OWW_SMALL_WGS_HEADS (0 = never the deep rings)
-    bool ring3_always[4] = {};       // A/B aid (OWW_RING3_ALWAYS="BCDE"): the three-slot weight ring of stages B..E at any launch size
     int hx_efeat = 0;                // heads: the features enter the first GEMM multiplied by 2^hx_efeat (largest probe |embedding| at 2^9..2^10)
     float hx_selftest_err = 0.f, hx_selftest_ref = 0.f, hx_selftest_score_err = 0.f;   // commit-time f16-split vs exact-fp32 comparison
     bool fuse = false;               // f16-split family: mel front end fused into stage A for one-chunk streaming steps (owwhip_fused.h)
-    const int16_t* fuse_pcm = nullptr;   // set by launch_step for the duration of a fused step
     // custom verifiers on the device (oww_set_verifier)
     float *d_verw = nullptr, *d_verb = nullptr, *d_verthr = nullptr; int* d_verT = nullptr;
     int ver_stride = 0, n_verifiers = 0;
     std::vector<int> ver_T;
     bool post_in_heads = false;          // one group of sigmoid heads covers every label: post-processing + counter advance ride in the heads launch
-    bool post_in_heads_now = false;      // ... for the step being launched (one-chunk steps only)
     float* d_save = nullptr; size_t save_floats = 0;      // streaming state parked by oww_embed / oww_embed_clips
     int* d_ids = nullptr;
     int ids_cap = 0;
     int *d_patience = nullptr;
     float* d_threshold = nullptr;
     int debounce_frames = 0;
-    // block-pipelined step: the one-chunk fused step of a large handle is launched as n_blocks stream ranges on their own HIP streams
-    // (forked from / joined to the handle's stream with events), so that one block's latency-bound phases and partly filled last
-    // wave rounds overlap the other block's kernels.  blk_s0 / blk_s1 = the range being launched (0 / 0 = everything).
-    int n_blocks = 1; hipStream_t blk_stream[4] = {}; hipEvent_t blk_fork = nullptr, blk_done[4] = {};
-    int blk_s0 = 0, blk_s1 = 0;
     // RCCL communicator of oww_comm_init (multi-GPU delivery of results without Python)
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;
     // timing
@@ -590,6 +575,24 @@ struct oww_ctx {
 };
 
 namespace {
+
+// What the launches of one step (or embedding / probe run) need beyond the handle.  The entry points build it and pass it down by
+// const reference; no launch helper reads a mode that a caller left behind in the handle.
+struct StepArgs {
+    const uint8_t* on = nullptr;          // masked step: participation mask (d_on, pad streams 0); nullptr = every stream
+    // masked step with few participants (build_active_lists): the launches of stages B..E, the heads and the VAD LSTM cover only the
+    // listed groups.  gl[0] = stream ids (stage B's groups and the heads' positions), [1] C, [2] D, [3] E, [4] VAD LSTM; gn = lengths
+    bool lists = false;
+    const int* gl[5] = {};
+    int gn[5] = {};
+    const int16_t* fused_pcm = nullptr;   // fused one-chunk step: stage A computes its mel rows from this PCM (owwhip_fused.h)
+    bool post_in_heads = false;           // post-processing + counter advance ride in the heads launch (one-chunk steps only)
+    const float* mel = nullptr;           // the CNN reads its mel rows from here (oww_embed_clips); nullptr = d_mel
+    bool dbg = false;                     // per-layer dump into d_dbg (debug_layers handles)
+};
+
+// a step over every stream, mel rows from d_mel, per-layer dumps where the handle keeps them
+StepArgs step_args(const oww_ctx* h) { StepArgs a; a.dbg = h->d_dbg != nullptr; return a; }
 
 int flush_events(oww_ctx* h) {
     if (!h->ev_used) return 0;
@@ -632,15 +635,15 @@ int set_lds(K kernel, int bytes) {
 
 // ---- CNN over the first n_active streams, mel rows at d_mel + s*mel_stride + mel_off ----------------
 template <bool MFMA>
-int run_cnn_t(oww_ctx* h, int n_active, int mel_stride, int mel_off) {
+int run_cnn_t(oww_ctx* h, const StepArgs& a, int n_active, int mel_stride, int mel_off) {
     hipStream_t st = h->stream;
-    const bool dbg = h->d_dbg != nullptr;
+    const bool dbg = a.dbg;
     int off = 0;
     int dbg_off[20];
     for (int l = 0; l < 20; ++l) { dbg_off[l] = off; off += kLayerOut[l][0] * kLayerOut[l][1] * kLayerOut[l][2]; }
     {
         StageAParams p{};
-        p.mel = h->mel_src ? h->mel_src : h->d_mel; p.mel_stride = mel_stride; p.mel_off = mel_off;
+        p.mel = a.mel ? a.mel : h->d_mel; p.mel_stride = mel_stride; p.mel_off = mel_off;
         p.hist_mel = h->d_state[0]; p.hist2 = h->d_state[1];
         p.w0 = h->d_conv[0]; p.w1 = h->d_conv[1]; p.w2 = h->d_conv[2];
         for (int i = 0; i < 3; ++i) { p.scale[i] = h->d_scale[i]; p.shift[i] = h->d_shift[i]; p.dbg_off[i] = dbg_off[i]; }
@@ -684,16 +687,29 @@ int run_cnn_t(oww_ctx* h, int n_active, int mel_stride, int mel_off) {
     return 0;
 }
 
+// one of stages B..E of the register-resident kernels (config CR; Timed class cls = 2..5), in the f16-split form (config CH, WG waves
+// per workgroup) when HX: a launch whose workgroups are (nearly) alone on their CUs runs the three-slot weight ring (owwhip_hx.h
+// WRing): same results
+template <class CR, class CH, int WG, bool LAST, bool DBG, bool HX>
+void launch_rstage(oww_ctx* h, const owr::RStageParams& p, int cls) {
+    hipStream_t st = h->stream;
+    Timed t(h, cls);
+    const int nwg = (p.n_groups + WG - 1) / WG;
+    if (HX && !DBG && nwg <= h->small_wgs) hipLaunchKernelGGL((owh::hstage_kernel<CH, LAST, false, WG, 3>), dim3(nwg), dim3(64 * WG), 0, st, p);
+    else if (HX) hipLaunchKernelGGL((owh::hstage_kernel<CH, LAST, DBG, WG>), dim3(nwg), dim3(64 * WG), 0, st, p);
+    else hipLaunchKernelGGL((owr::rstage_kernel<CR, LAST, DBG>), dim3((p.n_groups + 3) / 4), dim3(256), 0, st, p);
+}
+
 // register-resident kernels (owwhip_rr.h): every wave independent, groups of 1 / 1 / 2 / 4 / 8 streams per wave
 template <bool DBG, bool HX>
-int run_cnn_rr(oww_ctx* h, int n_active, int mel_stride, int mel_off) {
+int run_cnn_rr(oww_ctx* h, const StepArgs& a, int n_active, int mel_stride, int mel_off) {
     using namespace owr;
     hipStream_t st = h->stream;
     int off = 0, dbg_off[20];
     for (int l = 0; l < 20; ++l) { dbg_off[l] = off; off += kLayerOut[l][0] * kLayerOut[l][1] * kLayerOut[l][2]; }
     {
         RAParams p{};
-        p.mel = h->mel_src ? h->mel_src : h->d_mel; p.mel_stride = mel_stride; p.mel_off = mel_off;
+        p.mel = a.mel ? a.mel : h->d_mel; p.mel_stride = mel_stride; p.mel_off = mel_off;
         p.hist_mel = h->d_state[0]; p.hist2 = h->d_state[1];
         p.w0 = h->d_conv[0]; p.w1 = h->d_conv[1]; p.w2 = h->d_conv[2];
         for (int i = 0; i < 3; ++i) { p.scale[i] = h->d_scale[i]; p.shift[i] = h->d_shift[i]; p.dbg_off[i] = dbg_off[i]; }
@@ -702,15 +718,14 @@ int run_cnn_rr(oww_ctx* h, int n_active, int mel_stride, int mel_off) {
         for (int i = 0; i < 3; ++i) { p.clampv[i] = -0.4f * ldexpf(1.f, h->hx_e[i]); p.dbg_mul[i] = ldexpf(1.f, -h->hx_e[i]); }
         p.xmul = ldexpf(1.f, h->hx_xexp[0]);
         p.range_flag = HX ? h->d_range : nullptr;
-        p.stream_on = h->on_now;
+        p.stream_on = a.on;
         const int grid = std::min((n_active + 3) / 4, 768);           // persistent: 3 workgroups of 4 waves per CU
         Timed t(h, 1);
-        if (HX && h->fuse_pcm) {
+        if (HX && a.fused_pcm) {
             // mel front end + stage A in one launch: PCM in, pooled stage-A activations out (BASELINE configs[2] "mel+embedding fused")
             owf::MelAParams q{};
             q.a = p; q.a.mel = nullptr; q.a.n_streams = h->S;          // the PCM buffer holds the S real streams only
-            if (h->blk_s1 > 0) { q.a.s_base = h->blk_s0; q.a.n_streams = std::min(h->S, h->blk_s1) - h->blk_s0; }
-            q.pcm = h->fuse_pcm; q.tail = h->d_tail; q.nfeat = h->d_nfeat; q.hann = h->d_hann; q.mel_start = h->d_mstart; q.mel_taps = h->d_taps; q.mel_off = h->d_meloff; q.mel_dst = h->d_meldst;
+            q.pcm = a.fused_pcm; q.tail = h->d_tail; q.nfeat = h->d_nfeat; q.hann = h->d_hann; q.mel_start = h->d_mstart; q.mel_taps = h->d_taps; q.mel_off = h->d_meloff; q.mel_dst = h->d_meldst;
             q.mel_out = h->cfg.debug_layers ? h->d_mel : nullptr;
             const int per_cu = std::max(1, std::min(12 / owf::FA_WG, 163840 / owf::FA_LDS_BYTES));     // persistent: 12 waves per CU
             const int g2 = std::max(1, std::min((q.a.n_streams + owf::FA_WG - 1) / owf::FA_WG, 256 * per_cu));
@@ -719,7 +734,8 @@ int run_cnn_rr(oww_ctx* h, int n_active, int mel_stride, int mel_off) {
         else if (HX) hipLaunchKernelGGL(owh::hstageA_kernel<DBG>, dim3(std::min((n_active + 3) / 4, 256 * OWH_WPS_A)), dim3(256), 0, st, p);
         else hipLaunchKernelGGL(rstageA_kernel<DBG>, dim3(grid), dim3(256), 0, st, p);
     }
-    auto fill = [&](RStageParams& p, const float* xin, float* xout, int first_layer, int sb, int sd, int spt) {
+    auto fill = [&](const float* xin, float* xout, int first_layer, int sb, int sd, int spt) {
+        RStageParams p{};
         p.xin = xin; p.xout = xout; p.hist_b = h->d_state[sb]; p.hist_d = h->d_state[sd];
         for (int i = 0; i < 4; ++i) {
             p.w[i] = h->d_conv[first_layer + i]; p.scale[i] = h->d_scale[first_layer + i];
@@ -732,73 +748,30 @@ int run_cnn_rr(oww_ctx* h, int n_active, int mel_stride, int mel_off) {
         p.n_groups = (n_active + spt - 1) / spt; p.S = h->Spad;
         p.dbg = DBG ? h->d_dbg : nullptr; p.dbg_stride = DBG_FLOATS;
         p.range_flag = HX ? h->d_range : nullptr;
-        p.stream_on = h->on_now;
-        if (HX && h->blk_s1 > 0) { p.g_base = h->blk_s0 / spt; p.n_groups = (h->blk_s1 - h->blk_s0 + spt - 1) / spt; }
-        if (HX && h->lists_now) {                                   // spt 1, 2, 4, 8 -> list 0, 1, 2, 3
+        p.stream_on = a.on;
+        if (HX && a.lists) {                                        // spt 1, 2, 4, 8 -> list 0, 1, 2, 3
             const int k = spt == 1 ? 0 : spt == 2 ? 1 : spt == 4 ? 2 : 3;
-            p.glist = h->gl_now[k]; p.n_groups = h->gn_now[k];
+            p.glist = a.gl[k]; p.n_groups = a.gn[k];
         }
+        return p;
     };
-    {
-        RStageParams p{}; fill(p, h->d_xA, h->d_xB, 3, 2, 3, RB::SPT);
-        Timed t(h, 2);
-        // a launch whose workgroups are (nearly) alone on their CUs runs the three-slot weight ring (owwhip_hx.h WRing): same results
-        const int nwg = (p.n_groups + OWH_WG_B - 1) / OWH_WG_B;
-#ifdef OWH_DEEP_RING
-        if (HX && !DBG && nwg <= h->deep_wgs) { hipLaunchKernelGGL((owh::hstage_kernel<owh::HB, false, false, OWH_WG_B, 4>), dim3(nwg), dim3(64 * OWH_WG_B), 0, st, p); } else
-#endif
-        if (HX && !DBG && (nwg <= h->small_wgs || h->ring3_always[0])) hipLaunchKernelGGL((owh::hstage_kernel<owh::HB, false, false, OWH_WG_B, 3>), dim3(nwg), dim3(64 * OWH_WG_B), 0, st, p);
-        else if (HX) hipLaunchKernelGGL((owh::hstage_kernel<owh::HB, false, DBG, OWH_WG_B>), dim3(nwg), dim3(64 * OWH_WG_B), 0, st, p);
-        else hipLaunchKernelGGL((rstage_kernel<RB, false, DBG>), dim3((p.n_groups + 3) / 4), dim3(256), 0, st, p);
-    }
-    {
-        RStageParams p{}; fill(p, h->d_xB, h->d_xC, 7, 4, 5, RC::SPT);
-        Timed t(h, 3);
-        // a launch whose workgroups are (nearly) alone on their CUs runs the three-slot weight ring (owwhip_hx.h WRing): same results
-        const int nwg = (p.n_groups + OWH_WG_C - 1) / OWH_WG_C;
-#ifdef OWH_DEEP_RING
-        if (HX && !DBG && nwg <= h->deep_wgs) { hipLaunchKernelGGL((owh::hstage_kernel<owh::HC, false, false, OWH_WG_C, 5>), dim3(nwg), dim3(64 * OWH_WG_C), 0, st, p); } else
-#endif
-        if (HX && !DBG && (nwg <= h->small_wgs || h->ring3_always[1])) hipLaunchKernelGGL((owh::hstage_kernel<owh::HC, false, false, OWH_WG_C, 3>), dim3(nwg), dim3(64 * OWH_WG_C), 0, st, p);
-        else if (HX) hipLaunchKernelGGL((owh::hstage_kernel<owh::HC, false, DBG, OWH_WG_C>), dim3(nwg), dim3(64 * OWH_WG_C), 0, st, p);
-        else hipLaunchKernelGGL((rstage_kernel<RC, false, DBG>), dim3((p.n_groups + 3) / 4), dim3(256), 0, st, p);
-    }
-    {
-        RStageParams p{}; fill(p, h->d_xC, h->d_xD, 11, 6, 7, RD::SPT);
-        Timed t(h, 4);
-        // a launch whose workgroups are (nearly) alone on their CUs runs the three-slot weight ring (owwhip_hx.h WRing): same results
-        const int nwg = (p.n_groups + OWH_WG_D - 1) / OWH_WG_D;
-#ifdef OWH_DEEP_RING
-        if (HX && !DBG && nwg <= h->deep_wgs) { hipLaunchKernelGGL((owh::hstage_kernel<owh::HD, false, false, OWH_WG_D, 5>), dim3(nwg), dim3(64 * OWH_WG_D), 0, st, p); } else
-#endif
-        if (HX && !DBG && (nwg <= h->small_wgs || h->ring3_always[2])) hipLaunchKernelGGL((owh::hstage_kernel<owh::HD, false, false, OWH_WG_D, 3>), dim3(nwg), dim3(64 * OWH_WG_D), 0, st, p);
-        else if (HX) hipLaunchKernelGGL((owh::hstage_kernel<owh::HD, false, DBG, OWH_WG_D>), dim3(nwg), dim3(64 * OWH_WG_D), 0, st, p);
-        else hipLaunchKernelGGL((rstage_kernel<RD, false, DBG>), dim3((p.n_groups + 3) / 4), dim3(256), 0, st, p);
-    }
-    {
-        RStageParams p{}; fill(p, h->d_xD, nullptr, 15, 8, 9, RE::SPT);
-        p.hist19 = h->d_state[10]; p.w19 = h->d_conv[19]; p.feat = h->d_feat; p.emb = h->d_emb; p.nfeat = h->d_nfeat; p.TR = h->TR;
-        p.dbg_off[4] = dbg_off[19];
-        Timed t(h, 5);
-        // a launch whose workgroups are (nearly) alone on their CUs runs the three-slot weight ring (owwhip_hx.h WRing): same results
-        const int nwg = (p.n_groups + OWH_WG_E - 1) / OWH_WG_E;
-#ifdef OWH_DEEP_RING
-        if (HX && !DBG && nwg <= h->deep_wgs) { hipLaunchKernelGGL((owh::hstage_kernel<owh::HE, true, false, OWH_WG_E, 5>), dim3(nwg), dim3(64 * OWH_WG_E), 0, st, p); } else
-#endif
-        if (HX && !DBG && (nwg <= h->small_wgs || h->ring3_always[3])) hipLaunchKernelGGL((owh::hstage_kernel<owh::HE, true, false, OWH_WG_E, 3>), dim3(nwg), dim3(64 * OWH_WG_E), 0, st, p);
-        else if (HX) hipLaunchKernelGGL((owh::hstage_kernel<owh::HE, true, DBG, OWH_WG_E>), dim3(nwg), dim3(64 * OWH_WG_E), 0, st, p);
-        else hipLaunchKernelGGL((rstage_kernel<RE, true, DBG>), dim3((p.n_groups + 3) / 4), dim3(256), 0, st, p);
-    }
+    launch_rstage<RB, owh::HB, OWH_WG_B, false, DBG, HX>(h, fill(h->d_xA, h->d_xB, 3, 2, 3, RB::SPT), 2);
+    launch_rstage<RC, owh::HC, OWH_WG_C, false, DBG, HX>(h, fill(h->d_xB, h->d_xC, 7, 4, 5, RC::SPT), 3);
+    launch_rstage<RD, owh::HD, OWH_WG_D, false, DBG, HX>(h, fill(h->d_xC, h->d_xD, 11, 6, 7, RD::SPT), 4);
+    RStageParams pe = fill(h->d_xD, nullptr, 15, 8, 9, RE::SPT);
+    pe.hist19 = h->d_state[10]; pe.w19 = h->d_conv[19]; pe.feat = h->d_feat; pe.emb = h->d_emb; pe.nfeat = h->d_nfeat; pe.TR = h->TR;
+    pe.dbg_off[4] = dbg_off[19];
+    launch_rstage<RE, owh::HE, OWH_WG_E, true, DBG, HX>(h, pe, 5);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-int run_cnn(oww_ctx* h, int n_active, int mel_stride, int mel_off) {
+int run_cnn(oww_ctx* h, const StepArgs& a, int n_active, int mel_stride, int mel_off) {
     // grids cover whole workgroups of streams: round up to the largest per-workgroup stream count
     n_active = std::min(h->Spad, (n_active + 7) / 8 * 8);
-    if (h->hx) return h->d_dbg ? run_cnn_rr<true, true>(h, n_active, mel_stride, mel_off) : run_cnn_rr<false, true>(h, n_active, mel_stride, mel_off);
-    if (h->rr) return h->d_dbg ? run_cnn_rr<true, false>(h, n_active, mel_stride, mel_off) : run_cnn_rr<false, false>(h, n_active, mel_stride, mel_off);
-    return h->mfma ? run_cnn_t<true>(h, n_active, mel_stride, mel_off) : run_cnn_t<false>(h, n_active, mel_stride, mel_off);
+    if (h->hx) return a.dbg ? run_cnn_rr<true, true>(h, a, n_active, mel_stride, mel_off) : run_cnn_rr<false, true>(h, a, n_active, mel_stride, mel_off);
+    if (h->rr) return a.dbg ? run_cnn_rr<true, false>(h, a, n_active, mel_stride, mel_off) : run_cnn_rr<false, false>(h, a, n_active, mel_stride, mel_off);
+    return h->mfma ? run_cnn_t<true>(h, a, n_active, mel_stride, mel_off) : run_cnn_t<false>(h, a, n_active, mel_stride, mel_off);
 }
 
 int heads_lds_bytes(int NH) { return (HD_SB * 100 + 2 * HD_SB * (NH + 4) + HD_SB * HD_MAXNETS) * 4; }
@@ -815,13 +788,13 @@ void launch_generic_heads(oww_ctx* h, const HeadParams& p, int n_active, int nb,
     else hipLaunchKernelGGL((heads_generic_kernel<4, 4>), dim3((n_active + 15) / 16), dim3(256), gh_lds_bytes(4, 4, hs), st, p, nb, ne, hs);
 }
 
-int run_heads(oww_ctx* h, int n_active, bool accumulate_max, const float* ext, int only_head, float* raw_out, int force_generic) {
+int run_heads(oww_ctx* h, const StepArgs& a, int n_active, bool accumulate_max, const float* ext, int only_head, float* raw_out, int force_generic) {
     hipStream_t st = h->stream;
     Timed t(h, 6);
     HeadParams base{};
     base.feat = ext ? ext : h->d_feat; base.ext = ext ? 1 : 0; base.TR = h->TR; base.nfeat = h->d_nfeat;
     base.raw = raw_out; base.NL = h->NL; base.S = n_active; base.accumulate_max = accumulate_max ? 1 : 0;
-    base.stream_on = ext ? nullptr : h->on_now;
+    base.stream_on = ext ? nullptr : a.on;
     const bool fast_ok = h->mfma && !force_generic;
     if (fast_ok) {
         for (auto& g : h->groups) {
@@ -834,11 +807,10 @@ int run_heads(oww_ctx* h, int n_active, bool accumulate_max, const float* ext, i
                 owh::HeadHxParams q{};
                 q.feat = base.feat; q.ext = base.ext; q.TR = base.TR; q.T = g.T; q.nfeat = base.nfeat; q.w1hx = g.d_w1hx;
                 q.raw = raw_out; q.NL = h->NL; q.S = n_active; q.accumulate_max = base.accumulate_max;
-                q.range_flag = h->d_range; q.stream_on = h->on_now;
-                if (h->lists_now && !ext) { q.ids = h->gl_now[0]; q.n_ids = h->gn_now[0]; }
-                if (h->blk_s1 > 0 && !ext) { q.s_base = h->blk_s0; q.S = h->blk_s1; }
-                const int n_pos = q.ids ? q.n_ids : q.S - q.s_base;
-                if (h->post_in_heads_now) {
+                q.range_flag = h->d_range; q.stream_on = a.on;
+                if (a.lists && !ext) { q.ids = a.gl[0]; q.n_ids = a.gn[0]; }
+                const int n_pos = q.ids ? q.n_ids : q.S;
+                if (a.post_in_heads) {
                     owh::HeadHxPost& pp = q.post;
                     pp.enabled = 1; pp.scores = h->d_scores; pp.ring = h->d_ring; pp.npred = h->d_npred; pp.nfeat = h->d_nfeat;
                     pp.patience = h->d_patience; pp.threshold = h->d_threshold; pp.debounce_frames = h->debounce_frames;
@@ -915,14 +887,14 @@ int run_heads(oww_ctx* h, int n_active, bool accumulate_max, const float* ext, i
     return 0;
 }
 
-int launch_mel(oww_ctx* h, const int16_t* d_pcm, int n_streams, int n_samples, int n_frames, int streaming, float* out, float* smax,
-               int pcm_stride = 0, int max_only = 0, const float* floor_max = nullptr) {
+int launch_mel(oww_ctx* h, const StepArgs& a, const int16_t* d_pcm, int n_streams, int n_samples, int n_frames, int streaming, float* out,
+               float* smax, int pcm_stride = 0, int max_only = 0, const float* floor_max = nullptr) {
     MelParams p{};
     p.pcm = d_pcm; p.n_samples = n_samples; p.n_frames = n_frames; p.streaming = streaming;
     p.pcm_stride = pcm_stride; p.max_only = max_only; p.floor_max = floor_max;
     p.tail = h->d_tail; p.nfeat = h->d_nfeat; p.out = out; p.smax = smax;
     p.hann = h->d_hann; p.mel_start = h->d_mstart; p.mel_taps = h->d_taps; p.S = n_streams;
-    p.stream_on = streaming ? h->on_now : nullptr;
+    p.stream_on = streaming ? a.on : nullptr;
 #ifndef OWK_MEL_WGS
 #define OWK_MEL_WGS 6      // mel workgroups per CU in the persistent grid (20 KB LDS, 68 VGPRs each; 7 and 8 measured slower: 0.85 / 0.77 vs 0.73 ms)
 #endif
@@ -1010,7 +982,7 @@ void free_all(oww_ctx* h) {
     // (hipFree would wait for the whole device as well, but the page-locked words -- h_range, which the f16-split kernels write at
     // exit, h_lists, the ingest slots -- and the streams and events themselves are released by calls that promise no such wait).
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipStream_t st : {h->up_stream, h->down_stream, h->blk_stream[0], h->blk_stream[1], h->blk_stream[2], h->blk_stream[3]})
+    for (hipStream_t st : {h->up_stream, h->down_stream})
         if (st) (void)hipStreamSynchronize(st);
     auto fr = [](auto*& p) { if (p) { (void)dev_free((void*)p); p = nullptr; } };
     fr(h->d_w); fr(h->d_allnets); fr(h->d_generic);
@@ -1022,11 +994,6 @@ void free_all(oww_ctx* h) {
     h->long_cap = 0;
     h->save_floats = 0;
     if (h->d_on) { (void)dev_free(h->d_on); h->d_on = nullptr; }
-    for (int b = 0; b < 4; ++b) {
-        if (h->blk_stream[b]) { (void)hipStreamSynchronize(h->blk_stream[b]); (void)hipStreamDestroy(h->blk_stream[b]); h->blk_stream[b] = nullptr; }
-        if (h->blk_done[b]) { (void)hipEventDestroy(h->blk_done[b]); h->blk_done[b] = nullptr; }
-    }
-    if (h->blk_fork) { (void)hipEventDestroy(h->blk_fork); h->blk_fork = nullptr; }
     if (h->d_lists) { (void)dev_free(h->d_lists); h->d_lists = nullptr; }
     for (int i = 0; i < 2; ++i) {
         if (h->h_lists[i]) { (void)hipHostFree(h->h_lists[i]); h->h_lists[i] = nullptr; }
@@ -1070,12 +1037,11 @@ void launch_bank_tiles(oww_ctx* h, owh::BankParams q, int c, int tile0, int ntil
     }
 }
 
-// nfeat_adv = 1: the step's ring counter advance has already run (block-pipelined step: the bank launch follows the join)
-int run_bank(oww_ctx* h, bool accumulate_max, int nfeat_adv) {
+int run_bank(oww_ctx* h, const StepArgs& a, bool accumulate_max) {
     owh::BankParams q{};
-    q.feat = h->d_feat; q.ext = 0; q.TR = h->TR; q.nfeat = h->d_nfeat; q.nfeat_adv = nfeat_adv;
+    q.feat = h->d_feat; q.ext = 0; q.TR = h->TR; q.nfeat = h->d_nfeat;
     q.entries = h->d_bank_entries; q.heads = h->d_bank_heads; q.K = h->bank_K;
-    q.raw = h->d_bank_raw; q.accumulate_max = accumulate_max ? 1 : 0; q.range_flag = h->d_range; q.stream_on = h->on_now;
+    q.raw = h->d_bank_raw; q.accumulate_max = accumulate_max ? 1 : 0; q.range_flag = h->d_range; q.stream_on = a.on;
     q.fscale = std::ldexp(1.0f, h->hx_efeat);
     for (int c = 0; c < 2; ++c) {
         if (!h->bank_ntiles[c]) continue;
@@ -1090,13 +1056,13 @@ int run_bank(oww_ctx* h, bool accumulate_max, int nfeat_adv) {
     return 0;
 }
 
-int launch_bank_post(oww_ctx* h) {
+int launch_bank_post(oww_ctx* h, const StepArgs& a) {
     if (!bank_active(h)) return 0;
     owh::BankPostParams pp{};
     pp.raw = h->d_bank_raw; pp.scores = h->d_bank_scores; pp.ring = h->d_bank_ring; pp.npred = h->d_bank_npred; pp.sub = h->d_bank_sub;
     pp.patience = h->d_bank_pat; pp.threshold = h->d_bank_thr; pp.debounce_frames = h->debounce_frames;
     pp.S = h->S; pp.K = h->bank_K;
-    pp.vad_ring = h->d_vadring; pp.n_vad = h->d_nvad; pp.vad_threshold = h->vad_threshold; pp.stream_on = h->on_now;
+    pp.vad_ring = h->d_vadring; pp.n_vad = h->d_nvad; pp.vad_threshold = h->vad_threshold; pp.stream_on = a.on;
     {
         Timed t(h, 7);
         hipLaunchKernelGGL(owh::bank_post_kernel, dim3((h->S * h->bank_K + 255) / 256), dim3(256), 0, h->stream, pp);
@@ -1107,35 +1073,29 @@ int launch_bank_post(oww_ctx* h) {
 
 // one chunk of the streaming step on device-resident mel rows
 // (k, c: the mel rows of this chunk sit at row 8c of 8k per stream; first / last: of the CALL, which may span several mel slices)
-int step_chunk(oww_ctx* h, int k, int c, bool first, bool last, bool single);
-int step_chunk(oww_ctx* h, int k, int c) { return step_chunk(h, k, c, c == 0, c == k - 1, k == 1); }
-int step_chunk(oww_ctx* h, int k, int c, bool first, bool last, bool single) {
-    if (int rc = run_cnn(h, h->Spad, 8 * k * 32, c * 8 * 32)) return rc;
+int step_chunk(oww_ctx* h, const StepArgs& a, int k, int c, bool first, bool last) {
+    if (int rc = run_cnn(h, a, h->Spad, 8 * k * 32, c * 8 * 32)) return rc;
     // the bank reads this chunk's ring rows before the fixed heads launch (which may advance the ring counters: post_in_heads)
-    if (bank_active(h) && h->blk_s1 == 0) if (int rc = run_bank(h, !first, 0)) return rc;
-    h->post_in_heads_now = h->post_in_heads && single && h->n_verifiers == 0;
-    const int rc = run_heads(h, h->Spad, !first, nullptr, -1, h->d_raw, 0);
-    const bool done_in_heads = h->post_in_heads_now;
-    h->post_in_heads_now = false;
-    if (rc) return rc;
+    if (bank_active(h)) if (int rc = run_bank(h, a, !first)) return rc;
+    if (int rc = run_heads(h, a, h->Spad, !first, nullptr, -1, h->d_raw, 0)) return rc;
     if (h->n_verifiers > 0 && last) {                // after the maximum over the call's chunks, on the newest feature rows
         VerifierParams v{};
         v.raw = h->d_raw; v.feat = h->d_feat; v.nfeat = h->d_nfeat; v.w = h->d_verw; v.bias = h->d_verb; v.thr = h->d_verthr; v.T = h->d_verT;
-        v.wstride = h->ver_stride; v.NL = h->NL; v.TR = h->TR; v.S = h->S; v.stream_on = h->on_now;
+        v.wstride = h->ver_stride; v.NL = h->NL; v.TR = h->TR; v.S = h->S; v.stream_on = a.on;
         hipLaunchKernelGGL(verifier_kernel, dim3((h->S + 3) / 4), dim3(256), 0, h->stream, v);
     }
-    if (!done_in_heads)
-        hipLaunchKernelGGL(advance_kernel, dim3((h->Spad + 255) / 256), dim3(256), 0, h->stream, h->d_nfeat, h->Spad, h->on_now);
+    if (!a.post_in_heads)
+        hipLaunchKernelGGL(advance_kernel, dim3((h->Spad + 255) / 256), dim3(256), 0, h->stream, h->d_nfeat, h->Spad, a.on);
     return 0;
 }
 
 // voice-activity stand-in network for this step's 1280 new samples of every stream -> one score per stream into the VAD ring
-int launch_vad(oww_ctx* h, const int16_t* d_pcm, int n_samples) {
+int launch_vad(oww_ctx* h, const StepArgs& a, const int16_t* d_pcm, int n_samples) {
     const int G = (h->S + 15) / 16;
     {
         owv::VadFrontParams p{};
         p.pcm = d_pcm; p.n_samples = n_samples; p.S = h->S; p.hann = h->d_vad_hann; p.mag_gain = h->vad_gain;
-        p.w = h->d_vad_encw; p.bias = h->d_vad_encb; p.xout = h->d_vadx; p.range_flag = h->d_range; p.stream_on = h->on_now;
+        p.w = h->d_vad_encw; p.bias = h->d_vad_encb; p.xout = h->d_vadx; p.range_flag = h->d_range; p.stream_on = a.on;
         const int grid = std::min((h->S + owv::V_WG - 1) / owv::V_WG, 256);          // persistent: one 8-wave workgroup per CU
         Timed t(h, 8);
         hipLaunchKernelGGL(owv::vad_front_kernel, dim3(grid), dim3(64 * owv::V_WG), owv::V_LDS_BYTES, h->stream, p);
@@ -1143,8 +1103,8 @@ int launch_vad(oww_ctx* h, const int16_t* d_pcm, int n_samples) {
     {
         owv::VadLstmParams p{};
         p.xin = h->d_vadx; p.hc = h->d_vadhc; p.w = h->d_vad_lstmw; p.bias = h->d_vad_lstmb; p.wd = h->d_vad_wd; p.bd = h->vad_bd;
-        p.ring = h->d_vadring; p.n_vad = h->d_nvad; p.last = h->d_vadlast; p.S = h->S; p.n_groups = G; p.stream_on = h->on_now;
-        if (h->lists_now) { p.glist = h->gl_now[4]; p.n_groups = h->gn_now[4]; }
+        p.ring = h->d_vadring; p.n_vad = h->d_nvad; p.last = h->d_vadlast; p.S = h->S; p.n_groups = G; p.stream_on = a.on;
+        if (a.lists) { p.glist = a.gl[4]; p.n_groups = a.gn[4]; }
         Timed t(h, 9);
         hipLaunchKernelGGL(owv::vad_lstm_kernel, dim3((p.n_groups + owv::L_WG - 1) / owv::L_WG), dim3(64 * owv::L_WG), 0, h->stream, p);
     }
@@ -1153,11 +1113,12 @@ int launch_vad(oww_ctx* h, const int16_t* d_pcm, int n_samples) {
 }
 
 // Lists for a masked step with few participants: [stream ids | C groups | D groups | E groups | VAD groups] into one pinned staging
-// buffer, copied to the device on the compute stream (ordered before the step's kernels).  Returns the number of participants, -1
-// when the dense launches should be used (more than 7/8 of the streams take part: the lists then save nothing; below that they do even
-// for a mask that touches most groups, and a serving edge that places connections by cohort -- serve.py::SlotAllocator -- makes
-// participation per group all-or-nothing, so the launches shrink with the mask), or an OWW_E* code - 100 on failure.
-int build_active_lists(oww_ctx* h, const uint8_t* on) {
+// buffer, copied to the device on the compute stream (ordered before the step's kernels), and entered into a (lists, gl, gn).  Returns
+// the number of participants, -1 when the dense launches should be used (more than 7/8 of the streams take part: the lists then save
+// nothing; below that they do even for a mask that touches most groups, and a serving edge that places connections by cohort --
+// serve.py::SlotAllocator -- makes participation per group all-or-nothing, so the launches shrink with the mask), or an OWW_E* code
+// - 100 on failure.  Only a return > 0 fills a.
+int build_active_lists(oww_ctx* h, const uint8_t* on, StepArgs& a) {
     const int S = h->S;
     int n_act = 0;
     for (int s = 0; s < S; ++s) n_act += on[s] != 0;          // (vectorised by the compiler)
@@ -1216,54 +1177,36 @@ int build_active_lists(oww_ctx* h, const uint8_t* on) {
     size_t off = 0;
     for (int k = 0; k < 5; ++k) {
         if (base[k] != off) memmove(out + off, out + base[k], (size_t)n[k] * sizeof(int));
-        h->gl_now[k] = h->d_lists + off; h->gn_now[k] = n[k];
+        a.gl[k] = h->d_lists + off; a.gn[k] = n[k];
         off += (size_t)n[k];
     }
     if (off) {
         if (copy_async(h->d_lists, out, off * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(OWW_EHIP, "oww_step_masked: list upload failed") - 100;
         (void)hipEventRecord(h->lists_ev[turn], h->stream);
     }
+    a.lists = true;
     return n_act;
 }
 
-int launch_postproc(oww_ctx* h);
-int launch_step(oww_ctx* h, const int16_t* d_pcm, int k) {
+int launch_postproc(oww_ctx* h, const StepArgs& a);
+int launch_step(oww_ctx* h, const StepArgs& args, const int16_t* d_pcm, int k) {
     if (h->vad) {
         if (k != 1) return fail(OWW_EINVAL, "with the on-device VAD network a step carries exactly one 1280-sample chunk per stream (got %d)", k);
-        if (int rc = launch_vad(h, d_pcm, OWW_CHUNK * k)) return rc;
+        if (int rc = launch_vad(h, args, d_pcm, OWW_CHUNK * k)) return rc;
     }
+    StepArgs a = args;
+    a.post_in_heads = h->post_in_heads && k == 1 && h->n_verifiers == 0;
     if (h->fuse && k == 1 && (reinterpret_cast<uintptr_t>(d_pcm) & 15) == 0) {      // (the fused front end uses 16-byte sample loads)
-        h->fuse_pcm = d_pcm;
-        int rc = 0;
-        const bool blocks = h->n_blocks > 1 && h->post_in_heads && h->n_verifiers == 0 && !h->lists_now && !h->timing && !h->want_graph && !h->d_dbg;
-        if (blocks) {
-            // fork: the block streams wait for everything already queued on the handle's stream (PCM upload, VAD launches, masks)
-            hipStream_t main_stream = h->stream;
-            if (hipEventRecord(h->blk_fork, main_stream) != hipSuccess) rc = fail(OWW_EHIP, "block fork failed");
-            const int per = (h->Spad / h->n_blocks + 127) / 128 * 128;
-            for (int b = 0; b < h->n_blocks && !rc; ++b) {
-                h->blk_s0 = b * per; h->blk_s1 = b == h->n_blocks - 1 ? h->Spad : std::min(h->Spad, (b + 1) * per);
-                if (h->blk_s0 >= h->blk_s1 || h->blk_s0 >= h->S) break;
-                if (hipStreamWaitEvent(h->blk_stream[b], h->blk_fork, 0) != hipSuccess) { rc = fail(OWW_EHIP, "block fork failed"); break; }
-                h->stream = h->blk_stream[b];
-                rc = step_chunk(h, 1, 0);
-                h->stream = main_stream;
-                if (!rc && (hipEventRecord(h->blk_done[b], h->blk_stream[b]) != hipSuccess || hipStreamWaitEvent(main_stream, h->blk_done[b], 0) != hipSuccess))
-                    rc = fail(OWW_EHIP, "block join failed");
-            }
-            h->stream = main_stream; h->blk_s0 = h->blk_s1 = 0;
-            if (!rc && bank_active(h)) rc = run_bank(h, false, 1);       // after the join: every block's ring rows are in place
-        } else rc = step_chunk(h, 1, 0);
-        h->fuse_pcm = nullptr;
-        if (rc) return rc;
+        a.fused_pcm = d_pcm;
+        if (int rc = step_chunk(h, a, 1, 0, true, true)) return rc;
     } else {
-        if (int rc = launch_mel(h, d_pcm, h->S, OWW_CHUNK * k, 8 * k, 1, h->d_mel, nullptr)) return rc;
+        if (int rc = launch_mel(h, a, d_pcm, h->S, OWW_CHUNK * k, 8 * k, 1, h->d_mel, nullptr)) return rc;
         for (int c = 0; c < k; ++c)
-            if (int rc = step_chunk(h, k, c)) return rc;
+            if (int rc = step_chunk(h, a, k, c, c == 0, c == k - 1)) return rc;
     }
-    if (h->post_in_heads && k == 1 && h->n_verifiers == 0) { HIPCHK(hipGetLastError()); return launch_bank_post(h); }      // post-processing already ran inside the heads launch
-    if (int rc = launch_postproc(h)) return rc;
-    return launch_bank_post(h);
+    if (a.post_in_heads) { HIPCHK(hipGetLastError()); return launch_bank_post(h, a); }      // post-processing already ran inside the heads launch
+    if (int rc = launch_postproc(h, a)) return rc;
+    return launch_bank_post(h, a);
 }
 
 // A call of more chunks than the handle's mel buffer holds (n_chunks > max_chunks; the reference takes any length: model.py:287-298,
@@ -1272,27 +1215,27 @@ int launch_step(oww_ctx* h, const int16_t* d_pcm, int k) {
 // call whose loud part comes later).  Two passes: the mel kernel over the whole call for its per-stream maximum only, then the
 // slices -- mel rows with that shared floor, one embedding and one heads evaluation per chunk, raw scores max-combined over ALL
 // chunks of the call -- and one post-processing pass.  d_pcm: [S][1280 K] on the device.
-int launch_step_long(oww_ctx* h, const int16_t* d_pcm, int K) {
+int launch_step_long(oww_ctx* h, const StepArgs& a, const int16_t* d_pcm, int K) {
     if (h->vad) return fail(OWW_EINVAL, "with the on-device VAD network a step carries exactly one 1280-sample chunk per stream (got %d)", K);
     if (!h->d_callmax) if (int rc = dalloc(h->stream, &h->d_callmax, (size_t)h->Spad)) return rc;
-    if (int rc = launch_mel(h, d_pcm, h->S, OWW_CHUNK * K, 8 * K, 1, nullptr, h->d_callmax, 0, 1, nullptr)) return rc;
+    if (int rc = launch_mel(h, a, d_pcm, h->S, OWW_CHUNK * K, 8 * K, 1, nullptr, h->d_callmax, 0, 1, nullptr)) return rc;
     for (int o = 0; o < K; o += h->kmax) {
         const int ks = std::min(h->kmax, K - o);
-        if (int rc = launch_mel(h, d_pcm + (size_t)o * OWW_CHUNK, h->S, OWW_CHUNK * ks, 8 * ks, 1, h->d_mel, nullptr, OWW_CHUNK * K, 0, h->d_callmax)) return rc;
+        if (int rc = launch_mel(h, a, d_pcm + (size_t)o * OWW_CHUNK, h->S, OWW_CHUNK * ks, 8 * ks, 1, h->d_mel, nullptr, OWW_CHUNK * K, 0, h->d_callmax)) return rc;
         for (int c = 0; c < ks; ++c)
-            if (int rc = step_chunk(h, ks, c, o + c == 0, o + c == K - 1, false)) return rc;
+            if (int rc = step_chunk(h, a, ks, c, o + c == 0, o + c == K - 1)) return rc;
         h->k_last = ks;
     }
-    if (int rc = launch_postproc(h)) return rc;
-    return launch_bank_post(h);
+    if (int rc = launch_postproc(h, a)) return rc;
+    return launch_bank_post(h, a);
 }
 
-int launch_postproc(oww_ctx* h) {
+int launch_postproc(oww_ctx* h, const StepArgs& a) {
     PostParams pp{};
     pp.raw = h->d_raw; pp.scores = h->d_scores; pp.ring = h->d_ring; pp.npred = h->d_npred;
     pp.patience = h->d_patience; pp.threshold = h->d_threshold; pp.debounce_frames = h->debounce_frames;
     pp.NL = h->NL; pp.S = h->Spad;
-    pp.vad_ring = h->d_vadring; pp.n_vad = h->d_nvad; pp.vad_threshold = h->vad_threshold; pp.stream_on = h->on_now;
+    pp.vad_ring = h->d_vadring; pp.n_vad = h->d_nvad; pp.vad_threshold = h->vad_threshold; pp.stream_on = a.on;
     {
         Timed t(h, 7);
         hipLaunchKernelGGL(postproc_kernel, dim3((h->Spad + 127) / 128), dim3(128), 0, h->stream, pp);
@@ -1402,16 +1345,11 @@ void make_probe_pcm(std::vector<int16_t>& pcm, const std::vector<int16_t>& user 
 }
 
 // one probe step on handle t: mel of the chunk (separate kernel), CNN, frame counters, optionally the heads
-int probe_step(oww_ctx* t, const int16_t* d_chunk, bool heads) {
-    if (int rc = launch_mel(t, d_chunk, CAL_NP, OWW_CHUNK, 8, 1, t->d_mel, nullptr)) return rc;
-    if (int rc = run_cnn(t, CAL_NP, 256, 0)) return rc;
-    if (heads && t->NL > 0) {
-        const bool save = t->post_in_heads_now;
-        t->post_in_heads_now = false;
-        const int rc = run_heads(t, CAL_NP, false, nullptr, -1, t->d_raw, 0);
-        t->post_in_heads_now = save;
-        if (rc) return rc;
-    }
+int probe_step(oww_ctx* t, const StepArgs& a, const int16_t* d_chunk, bool heads) {
+    if (int rc = launch_mel(t, a, d_chunk, CAL_NP, OWW_CHUNK, 8, 1, t->d_mel, nullptr)) return rc;
+    if (int rc = run_cnn(t, a, CAL_NP, 256, 0)) return rc;
+    if (heads && t->NL > 0)
+        if (int rc = run_heads(t, a, CAL_NP, false, nullptr, -1, t->d_raw, 0)) return rc;
     hipLaunchKernelGGL(advance_kernel, dim3((t->Spad + 255) / 256), dim3(256), 0, t->stream, t->d_nfeat, t->Spad, (const uint8_t*)nullptr);
     return 0;
 }
@@ -1456,7 +1394,8 @@ int calibrate_hx(oww_ctx* h, HxCalib& cal) {
         auto absmax = [&]() { hipLaunchKernelGGL(layer_absmax_kernel, dim3(20, CAL_NP), dim3(256), 0, t->stream, t->d_dbg, (size_t)DBG_FLOATS, d_off, d_max); };
         // (a) the all-ones mel history every stream starts from (utils.py:165): the handle sits in that steady state after its commit
         hipLaunchKernelGGL(fill_kernel, dim3(CAL_NP), dim3(256), 0, t->stream, t->d_mel, (size_t)CAL_NP * 256, 1.0f);
-        if ((rc = run_cnn(t, CAL_NP, 256, 0))) break;
+        const StepArgs a = step_args(t);             // (every layer dumped: the maxima are read from t's debug buffer)
+        if ((rc = run_cnn(t, a, CAL_NP, 256, 0))) break;
         absmax();
         // (b) the probe audio, batch by batch from the reset state
         cal.ref_emb.assign((size_t)cal.nb * CAL_T * CAL_NP * 96, 0.f);
@@ -1465,7 +1404,7 @@ int calibrate_hx(oww_ctx* h, HxCalib& cal) {
             const int it = bt % CAL_T;
             if (it == 0 && bt > 0 && (rc = do_reset(t, nullptr, CAL_NP, nullptr))) break;
             if (getenv("OWW_DEBUG_CALIB")) { const hipError_t e = hipStreamSynchronize(t->stream); fprintf(stderr, "calibrate: probe step %d of %d (%s)\n", bt, cal.nb * CAL_T, hipGetErrorString(e)); }
-            if ((rc = probe_step(t, cal.d_pcm + (size_t)bt * CAL_NP * OWW_CHUNK, true))) break;
+            if ((rc = probe_step(t, a, cal.d_pcm + (size_t)bt * CAL_NP * OWW_CHUNK, true))) break;
             absmax();
             if (hipMemcpyAsync(d_ref + (size_t)bt * CAL_NP * 96, t->d_emb, (size_t)CAL_NP * 96 * sizeof(float), hipMemcpyDeviceToDevice, t->stream) != hipSuccess ||
                 (t->NL > 0 && hipMemcpyAsync(d_ref + n_emb + (size_t)bt * CAL_NP * t->NL, t->d_raw, (size_t)CAL_NP * t->NL * sizeof(float), hipMemcpyDeviceToDevice, t->stream) != hipSuccess)) { rc = fail(OWW_EHIP, "oww_commit: probe gather failed"); break; }
@@ -1538,15 +1477,14 @@ int selftest_hx(oww_ctx* h, const HxCalib& cal) {
     if (dev_alloc(&d_out, (n_emb + n_raw) * sizeof(float)) != hipSuccess) return fail(OWW_ENOMEM, "oww_commit: out of device memory (self-test)");
     std::vector<float> emb(n_emb), raw(n_raw);
     int rc = 0;
-    float* saved_dbg = h->d_dbg; h->d_dbg = nullptr;
+    const StepArgs a{};                                  // (no per-layer dumps: the replay runs the kernels the steps run)
     for (int bt = 0; bt < cal.nb * CAL_T && !rc; ++bt) {
         if (bt % CAL_T == 0 && bt > 0 && (rc = do_reset(h, nullptr, CAL_NP, nullptr))) break;
         if (getenv("OWW_DEBUG_CALIB")) { const hipError_t e = hipStreamSynchronize(h->stream); fprintf(stderr, "self-test: probe step %d of %d (%s)\n", bt, cal.nb * CAL_T, hipGetErrorString(e)); }
-        if ((rc = probe_step(h, cal.d_pcm + (size_t)bt * CAL_NP * OWW_CHUNK, true))) break;
+        if ((rc = probe_step(h, a, cal.d_pcm + (size_t)bt * CAL_NP * OWW_CHUNK, true))) break;
         if (hipMemcpyAsync(d_out + (size_t)bt * CAL_NP * 96, h->d_emb, (size_t)CAL_NP * 96 * sizeof(float), hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
             (h->NL > 0 && hipMemcpyAsync(d_out + n_emb + (size_t)bt * CAL_NP * h->NL, h->d_raw, (size_t)CAL_NP * h->NL * sizeof(float), hipMemcpyDeviceToDevice, h->stream) != hipSuccess)) { rc = fail(OWW_EHIP, "oww_commit: probe gather failed"); break; }
     }
-    h->d_dbg = saved_dbg;
     if (!rc && (copy_async(emb.data(), d_out, n_emb * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
                 (h->NL > 0 && copy_async(raw.data(), d_out + n_emb, n_raw * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) ||
                 hipStreamSynchronize(h->stream) != hipSuccess)) rc = fail(OWW_EHIP, "oww_commit: self-test run failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1576,7 +1514,6 @@ int selftest_hx(oww_ctx* h, const HxCalib& cal) {
 // every queued launch of the handle has finished: the routing table, the bank images and the slot state may change
 int bank_quiesce(oww_ctx* h) {
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (hipStream_t st : {h->blk_stream[0], h->blk_stream[1], h->blk_stream[2], h->blk_stream[3]}) if (st) HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -2304,26 +2241,10 @@ int oww_commit(oww_ctx* h) {
     if (h->cfg.debug_layers) if (int rc = dalloc(h->stream, &h->d_dbg, SP * DBG_FLOATS)) return rc;
     if (const char* e = getenv("OWW_PROF_BLOCK")) { h->prof_block = atoi(e); if (int rc = dalloc(h->stream, &h->d_prof, (size_t)4 * 256)) return rc; }
 
-    // block-pipelined step: OFF by default.  Measured with the round-3 kernels at 131,072 x 3 (same box, OWW_BLOCKS = 1 / 2 / 3 / 4):
-    // 6.04 / 6.10 / 6.25 / 6.32 ms per step -- two kernels sharing the chip gain nothing now that the front end no longer stalls
-    // (round 2, two handles on two streams: -3.6 %).  OWW_BLOCKS=2..4 switches it on for large handles (experiments).
-    if (h->hx && h->S >= 16384) {
-        h->n_blocks = 1;
-        if (const char* e = getenv("OWW_BLOCKS")) h->n_blocks = std::min(4, std::max(1, atoi(e)));
-        if (h->n_blocks > 1) {
-            HIPCHK(hipEventCreateWithFlags(&h->blk_fork, hipEventDisableTiming));
-            for (int b = 0; b < h->n_blocks; ++b) {
-                HIPCHK(hipStreamCreateWithFlags(&h->blk_stream[b], hipStreamNonBlocking));
-                HIPCHK(hipEventCreateWithFlags(&h->blk_done[b], hipEventDisableTiming));
-            }
-        }
-    }
     h->fuse = h->hx && !getenv("OWW_NO_FUSE");
-    if (const char* e = getenv("OWW_DEEP_WGS")) h->deep_wgs = atoi(e);
     if (const char* e = getenv("OWW_SMALL_WGS")) h->small_wgs = atoi(e);
     if (const char* e = getenv("OWW_SMALL_WGS_HEADS")) h->small_wgs_heads = atoi(e);
     if (const char* e = getenv("OWW_GENERIC_SPW")) { const int v = atoi(e); h->generic_spw = v == 4 || v == 16 ? v : 0; }
-    if (const char* e = getenv("OWW_RING3_ALWAYS")) for (int i = 0; i < 4; ++i) h->ring3_always[i] = strchr(e, "BCDE"[i]) != nullptr;
     h->post_in_heads = h->hx && !getenv("OWW_NO_FUSE") && h->groups.size() == 1 && h->groups[0].ht == 4 && h->generic_nets.empty() && h->rnn_nets.empty() && h->NL > 0;                  // (A/B switch: OWW_NO_FUSE=1 keeps the separate mel kernel)
     if (int rc = set_lds(owf::hmelA_kernel<false>, owf::FA_LDS_BYTES)) return rc;
     if (int rc = set_lds(owf::hmelA_kernel<true>, owf::FA_LDS_BYTES)) return rc;
@@ -2344,10 +2265,9 @@ int oww_commit(oww_ctx* h) {
     {
         const int warm = std::min<int>(32, (int)SP);
         hipLaunchKernelGGL(fill_kernel, dim3((warm * 256 + 255) / 256), dim3(256), 0, h->stream, h->d_mel, (size_t)warm * 256, 1.0f);
-        float* saved_dbg = h->d_dbg; h->d_dbg = nullptr;
+        const StepArgs a{};                                // (no per-layer dumps)
         for (int it = 0; it < 12; ++it)
-            if (int rc = run_cnn(h, warm, 256, 0)) return rc;
-        h->d_dbg = saved_dbg;
+            if (int rc = run_cnn(h, a, warm, 256, 0)) return rc;
         for (int a = 0; a < N_STATE; ++a)
             HIPCHK(copy_async(h->d_tmpl[a], h->d_state[a], (size_t)h->state_len[a] * (h->rr ? kStateSpgRr[a] : 1) * sizeof(float),
                                   hipMemcpyDeviceToDevice, h->stream));
@@ -2454,6 +2374,7 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
     if (int rc = range_check(h, "oww_step")) return rc;          // raised by an earlier (asynchronous) step: sticky
     HIPCHK(hipSetDevice(h->cfg.device));
     h->k_last = n_chunks;
+    const StepArgs a = step_args(h);
     const size_t n_pcm = (size_t)h->S * OWW_CHUNK * n_chunks;
     if (n_chunks > h->kmax) {                                    // longer than the mel buffer: slices that share the call's clamp floor
         const int16_t* d_call = pcm;
@@ -2466,7 +2387,7 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
             HIPCHK(copy_async(h->d_long, pcm, n_pcm * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
             d_call = h->d_long;
         }
-        if (int rc = launch_step_long(h, d_call, n_chunks)) return rc;
+        if (int rc = launch_step_long(h, a, d_call, n_chunks)) return rc;
         if (scores) {
             const size_t nb = (size_t)h->S * h->NL * sizeof(float);
             if (nb) HIPCHK(copy_async(scores, h->d_scores, nb, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
@@ -2486,7 +2407,7 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
     if (graphable) {
         if (!h->graph_exec) {
             HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-            const int rc = launch_step(h, h->d_pcm, 1);
+            const int rc = launch_step(h, a, h->d_pcm, 1);
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(h->stream, &g);
             if (rc) return rc;
@@ -2497,7 +2418,7 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
         }
         HIPCHK(hipGraphLaunch(h->graph_exec, h->stream));
     } else {
-        if (int rc = launch_step(h, d_pcm, n_chunks)) return rc;
+        if (int rc = launch_step(h, a, d_pcm, n_chunks)) return rc;
     }
     if (scores) {
         const size_t nb = (size_t)h->S * h->NL * sizeof(float);
@@ -2532,16 +2453,15 @@ int oww_step_masked(oww_ctx* h, const int16_t* pcm, int pcm_on_device, const uin
                               pcm_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
         d_pcm = h->d_pcm;
     }
-    h->on_now = h->d_on;
+    StepArgs a = step_args(h);
+    a.on = h->d_on;
     int n_act = -1;
     if (!stream_on_on_device) {                                 // few participants: only their groups are launched (build_active_lists)
-        n_act = build_active_lists(h, stream_on);
-        if (n_act < -1) { h->on_now = nullptr; return n_act + 100; }
+        n_act = build_active_lists(h, stream_on, a);
+        if (n_act < -1) return n_act + 100;
     }
-    h->lists_now = n_act >= 0;
-    const int rc = n_act == 0 ? 0 : launch_step(h, d_pcm, 1);     // nobody takes part: nothing moves
-    h->on_now = nullptr; h->lists_now = false;
-    if (rc) return rc;
+    if (n_act != 0)                                             // (nobody takes part: nothing moves)
+        if (int rc = launch_step(h, a, d_pcm, 1)) return rc;
     if (scores) {
         const size_t nb = (size_t)h->S * h->NL * sizeof(float);
         if (nb) HIPCHK(copy_async(scores, h->d_scores, nb, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
@@ -2598,6 +2518,8 @@ static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const u
     HIPCHK(copy_async(sl.d_pcm, pcm, n_pcm * sizeof(int16_t), hipMemcpyHostToDevice, h->up_stream));
     HIPCHK(hipEventRecord(sl.up, h->up_stream));
     HIPCHK(hipStreamWaitEvent(h->stream, sl.up, 0));
+    StepArgs a = step_args(h);
+    int n_act = -1;
     if (stream_on) {                                   // (the mask is small: copied on the compute stream, ordered before this step's kernels)
         if (!h->d_on) {
             HIPCHK(dev_alloc(&h->d_on, h->Spad));
@@ -2605,17 +2527,12 @@ static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const u
         }
         memcpy(sl.h_on, stream_on, h->S);              // the caller's array is free again when this call returns
         HIPCHK(copy_async(h->d_on, sl.h_on, h->S, hipMemcpyHostToDevice, h->stream));
-        h->on_now = h->d_on;
+        a.on = h->d_on;
+        n_act = build_active_lists(h, stream_on, a);
+        if (n_act < -1) return n_act + 100;
     }
-    int n_act = -1;
-    if (stream_on) {
-        n_act = build_active_lists(h, stream_on);
-        if (n_act < -1) { h->on_now = nullptr; return n_act + 100; }
-    }
-    h->lists_now = n_act >= 0;
-    const int rc_step = n_act == 0 ? 0 : launch_step(h, sl.d_pcm, n_chunks);
-    h->on_now = nullptr; h->lists_now = false;
-    if (rc_step) return rc_step;
+    if (n_act != 0)
+        if (int rc = launch_step(h, a, sl.d_pcm, n_chunks)) return rc;
     const size_t nb = (size_t)h->S * h->NL * sizeof(float);
     if (nb) HIPCHK(copy_async(sl.d_scores, h->d_scores, nb, hipMemcpyDeviceToDevice, h->stream));   // d_scores is rewritten by the next step
     HIPCHK(hipEventRecord(sl.done, h->stream));
@@ -2880,7 +2797,7 @@ static int mel_impl(oww_ctx* h, const int16_t* pcm, int32_t B, int32_t n, float*
         if (dev_alloc(&d_in, (size_t)B * n * sizeof(int16_t)) != hipSuccess || dev_alloc(&d_out, (size_t)B * F * 32 * sizeof(float)) != hipSuccess ||
             dev_alloc(&d_max, (size_t)B * sizeof(float)) != hipSuccess) { rc = fail(OWW_ENOMEM, "oww_mel: out of device memory"); break; }
         if (copy_async(d_in, pcm, (size_t)B * n * sizeof(int16_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_mel: H2D failed"); break; }
-        if ((rc = launch_mel(h, d_in, B, n, F, 0, d_out, d_max))) break;
+        if ((rc = launch_mel(h, StepArgs{}, d_in, B, n, F, 0, d_out, d_max))) break;
         const size_t tot = (size_t)B * F * 32;
         if (per_clip) {
             hipLaunchKernelGGL(clamp_db_rows_kernel, dim3((F * 32 + 255) / 256, B), dim3(256), 0, h->stream, d_out, F * 32, d_max);
@@ -2910,6 +2827,7 @@ int oww_embed(oww_ctx* h, const float* mel_rows, int32_t B, int32_t rows, float*
     const int n_out = (rows - 76) / 8 + 1;
     const int n_steps = (rows + 4) / 8;                 // 4 lead-in rows + rows, 8 per step
     std::vector<float> slab((size_t)B * 256), emb((size_t)B * 96);
+    const StepArgs a = step_args(h);
     if (int rc = park_state(h, B, true)) return rc;
     int rc_all = 0;
     for (int it = 0; it < n_steps && !rc_all; ++it) {
@@ -2921,7 +2839,7 @@ int oww_embed(oww_ctx* h, const float* mel_rows, int32_t B, int32_t rows, float*
                 else memcpy(d, mel_rows + ((size_t)b * rows + src) * 32, 32 * sizeof(float));
             }
         if (copy_async(h->d_mel, slab.data(), slab.size() * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc_all = fail(OWW_EHIP, "oww_embed: H2D failed"); break; }
-        if ((rc_all = run_cnn(h, B, 256, 0))) break;
+        if ((rc_all = run_cnn(h, a, B, 256, 0))) break;
         hipLaunchKernelGGL(advance_kernel, dim3((h->Spad + 255) / 256), dim3(256), 0, h->stream, h->d_nfeat, h->Spad, (const uint8_t*)nullptr);
         if (it >= 9 && copy_async(emb.data(), h->d_emb, emb.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) { rc_all = fail(OWW_EHIP, "oww_embed: D2H failed"); break; }
         if (hipStreamSynchronize(h->stream) != hipSuccess) { rc_all = fail(OWW_EHIP, "oww_embed: device error"); break; }   // slab is reused next iteration
@@ -2963,23 +2881,22 @@ int oww_embed_clips(oww_ctx* h, const int16_t* pcm, int32_t pcm_on_device, int32
         float* o = out_on_device ? out : d_out;
         if (hipMemsetAsync(d_mel, 0, lead * sizeof(float), h->stream) != hipSuccess ||
             (Bp > B && hipMemsetAsync(d_mel + lead + (size_t)B * F * 32, 0, (size_t)(Bp - B) * F * 32 * sizeof(float), h->stream) != hipSuccess)) { rc = fail(OWW_EHIP, "oww_embed_clips: memset failed"); break; }
-        if ((rc = launch_mel(h, pcm_on_device ? pcm : d_in, B, n, F, 0, d_mel + lead, d_max))) break;
+        StepArgs a = step_args(h);
+        a.mel = d_mel + lead;
+        if ((rc = launch_mel(h, a, pcm_on_device ? pcm : d_in, B, n, F, 0, d_mel + lead, d_max))) break;
         hipLaunchKernelGGL(clamp_transform_rows_kernel, dim3((F * 32 + 255) / 256, B), dim3(256), 0, h->stream, d_mel + lead, F * 32, d_max);
-        h->mel_src = d_mel + lead;
         for (int it = 0; it < n_steps && !rc; ++it) {
-            rc = run_cnn(h, B, F * 32, (it * 8 - 4) * 32);
+            rc = run_cnn(h, a, B, F * 32, (it * 8 - 4) * 32);
             if (rc) break;
             hipLaunchKernelGGL(advance_kernel, dim3((h->Spad + 255) / 256), dim3(256), 0, h->stream, h->d_nfeat, h->Spad, (const uint8_t*)nullptr);
             if (it >= 9 && hipMemcpy2DAsync(o + (size_t)(it - 9) * 96, (size_t)n_out * 96 * sizeof(float), h->d_emb, 96 * sizeof(float),
                                             96 * sizeof(float), B, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
                 rc = fail(OWW_EHIP, "oww_embed_clips: gather failed");
         }
-        h->mel_src = nullptr;
         if (rc) break;
         if (!out_on_device && copy_async(out, d_out, (size_t)B * n_out * 96 * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_embed_clips: D2H failed"); break; }
         if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_embed_clips: device error: %s", hipGetErrorString(hipGetLastError())); break; }
     } while (0);
-    h->mel_src = nullptr;
     const int rc_restore = park_state(h, B, false);
     (void)hipStreamSynchronize(h->stream);
     (void)dev_free(d_in); (void)dev_free(d_mel); (void)dev_free(d_max); (void)dev_free(d_out);
@@ -3004,7 +2921,7 @@ int oww_head(oww_ctx* h, int32_t head, const float* features, int32_t B, float* 
         }
         if (copy_async(d_f, features, nf * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_head: H2D failed"); break; }
         if (hipMemsetAsync(d_raw, 0, (size_t)B * h->NL * sizeof(float), h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_head: memset failed"); break; }
-        if ((rc = run_heads(h, B, false, d_f, head, d_raw, 0))) break;
+        if ((rc = run_heads(h, step_args(h), B, false, d_f, head, d_raw, 0))) break;
         std::vector<float> raw((size_t)B * h->NL);
         if (copy_async(raw.data(), d_raw, raw.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_head: D2H failed"); break; }

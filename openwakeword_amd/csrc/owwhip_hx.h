@@ -1000,7 +1000,7 @@ __global__ __launch_bounds__(64 * WG, (DBG || NS > 3 ? 1 : (NS == 3 && C::WPS > 
     const bool active = g < p.n_groups;
     if (!active) g = p.n_groups - 1;
     if (p.glist) g = p.glist[g];          // a masked step with few participants runs only the groups that hold one (owwhip.hip: build_active_lists)
-    else g += p.g_base;                   // block-pipelined step: this launch covers groups g_base .. g_base + n_groups - 1
+    else g += p.g_base;                   // (g_base: always 0 since the block-pipelined step was removed)
     lanemask_t bad = 0;
     ring_issue<NS, NBAM, WG>(p.w[0], wbuf, wave, lane);
     if (NS >= 3) ring_issue<NS, NBAM, WG>(p.w[0] + (size_t)NBAM * 256, wbuf1, wave, lane);   // (NS - 1 chunks in flight from the start)
@@ -1649,7 +1649,7 @@ struct HeadHxParams {
     const uint8_t* stream_on;   // oww_step_masked: [S] 1 = the stream takes part in this step; nullptr = all do
     const int* ids;             // oww_step_masked with few participants: the n_ids participating streams (position k of the launch = stream
     int n_ids;                  // ids[k]); nullptr = streams s_base .. S-1
-    int s_base;                 // block-pipelined step: first stream of this launch (S = one past its last)
+    int s_base;                 // first stream of this launch (S = one past its last); always 0 since the block-pipelined step was removed
     // Like every CNN layer, the first GEMM runs on a calibrated power-of-two scale: the features are multiplied by fscale = 2^e_feat
     // as they are loaded (oww_commit puts the probe set's largest |embedding| at 2^9..2^10 -- a factor 64 below the f16 overflow, and
     // embeddings of order 1e-4 keep the low halves of their split), each net's weights are stored as halves of 2^e_w w with the
@@ -2399,7 +2399,8 @@ struct BankHeadDev {
 struct BankParams {
     const float* feat;       // ring [S][TR][96], or external [B][T][96] (ext != 0: the self-test of oww_bank_add)
     int ext, TR;
-    const uint32_t* nfeat;   // ring row counters; nfeat_adv = 1 when this step's counter advance has already run (block-pipelined step)
+    const uint32_t* nfeat;   // ring row counters; nfeat_adv = 1: this step's counter advance has already run (always 0 since the
+                             // block-pipelined step was removed)
     int nfeat_adv;
     const BankTile* tiles;
     const int* entries;

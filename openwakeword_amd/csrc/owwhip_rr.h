@@ -473,7 +473,7 @@ struct RStageParams {
     const uint8_t* stream_on;  // oww_step_masked (register-resident families): [S] 1 = the stream takes part in this step; nullptr = all do
     const int* glist;          // f16-split family, oww_step_masked with few participants: the n_groups groups (of this stage's SPT streams)
                                // that hold at least one participating stream; nullptr = groups g_base .. g_base + n_groups-1
-    int g_base;                // f16-split family: first group of the block this launch covers (block-pipelined step; 0 otherwise)
+    int g_base;                // f16-split family: first group this launch covers (always 0 since the block-pipelined step was removed)
 };
 
 // max-pool PT x PF of the stage output and scatter into the next stage's register-dump layout
@@ -644,7 +644,7 @@ struct RAParams {
     const float* shift[3];
     float* xout;           // stage B xin: [S][4][8][64]
     int n_streams;         // streams to run
-    int s_base;            // f16-split family: first stream of the block this launch covers (block-pipelined step; 0 otherwise)
+    int s_base;            // f16-split family: first stream this launch covers (always 0 since the block-pipelined step was removed)
     int S;
     float* dbg;
     size_t dbg_stride;

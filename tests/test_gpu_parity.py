@@ -412,13 +412,11 @@ def test_large_batch_properties(emb, heads):
 @pytest.mark.parametrize("S", [40, 2500])
 def test_weight_ring_depth_never_changes_a_bit(emb, heads, monkeypatch, S):
     """The stage kernels stream their weights through an LDS ring of 2 slots (large launches) or 3 (at most two workgroups per CU) --
-    and of 4 / 5 in builds with -DOWH_DEEP_RING (OWW_DEEP_WGS; measured no faster, not in the default build, where the variable is
-    ignored) -- same arithmetic in the same order, only what is in flight differs.  Scores AND feature rings of a handle pinned to
-    the deepest ring built, to the three-slot ring and to the two-slot ring must be bit-identical."""
+    same arithmetic in the same order, only what is in flight differs.  Scores AND feature rings of a handle pinned to the
+    three-slot ring and to the two-slot ring must be bit-identical."""
     pcm = W.synthetic_pcm(S, 1280 * 8, seed=91)
 
-    def run(deep, small):
-        monkeypatch.setenv("OWW_DEEP_WGS", str(deep))
+    def run(small):
         monkeypatch.setenv("OWW_SMALL_WGS", str(small))
         e = StreamEngine(S, heads, emb)
         try:
@@ -429,47 +427,64 @@ def test_weight_ring_depth_never_changes_a_bit(emb, heads, monkeypatch, S):
         finally:
             e.close()
 
-    a = run(1 << 20, 1 << 20)          # every stage on its deepest ring
-    b = run(0, 1 << 20)                # three slots
-    c = run(0, 0)                      # two slots
-    monkeypatch.delenv("OWW_DEEP_WGS"); monkeypatch.delenv("OWW_SMALL_WGS")
-    for x, y in ((a, b), (a, c)):
-        np.testing.assert_array_equal(x[0], y[0])
-        np.testing.assert_array_equal(x[1], y[1])
-    assert a[0][-1].max() > 0
+    b = run(1 << 20)                   # three slots
+    c = run(0)                         # two slots
+    monkeypatch.delenv("OWW_SMALL_WGS")
+    np.testing.assert_array_equal(b[0], c[0])
+    np.testing.assert_array_equal(b[1], c[1])
+    assert b[0][-1].max() > 0
 
 
-def test_block_pipelined_step_is_bit_identical(emb, heads, monkeypatch):
-    """OWW_BLOCKS=3: the fused one-chunk step launched as three stream blocks on internal HIP streams (off by default: measured no
-    faster) must give exactly the scores of the single-launch step, also through a masked step.  Since round 4 this is also the
-    stress test of the small-launch kernels: a block of ~5,500 streams runs the three-slot weight ring of the stage kernels and the
-    deep ring of the heads kernel -- counted waits and bare barriers -- while the single launch of 16,480 runs the two-slot forms, and
-    three blocks' kernels share the CUs.  (The first five scores of a stream are zeroed by model.py:331-333: only frames >= 5 can show
-    a difference, so the run is ten frames, three times.)"""
-    S = 16384 + 96                                                  # (block borders at multiples of 128, a ragged last block)
+def test_concurrent_block_engines_are_bit_identical(emb, heads):
+    """Three engines over the blocks of a 16,480-stream batch, each on its own HIP stream and stepped on device-resident PCM with no
+    host sync between them, must give exactly the scores of one 16,480-stream engine, also through a masked step; batch invariance
+    makes the rows comparable.  This is the stress test of the small-launch kernels: a block of ~5,500 streams runs the three-slot
+    weight ring of the stage kernels and the deep ring of the heads kernel -- counted waits and bare barriers -- while the single
+    engine runs the two-slot forms, and three engines' kernels share the CUs.  (The first five scores of a stream are zeroed by
+    model.py:331-333: only frames >= 5 can show a difference, so the run is ten frames, three times.)"""
+    import torch
+    S = 16384 + 96
+    borders = [0, 5504, 11008, S]                                   # 5,504 / 5,504 / 5,472 streams
     n_frames = 10
     pcm = W.synthetic_pcm(S, 1280 * n_frames, seed=72)
     on = (np.random.default_rng(3).random(S) < 0.8).astype(np.uint8)
-    monkeypatch.delenv("OWW_BLOCKS", raising=False)
+    dev = torch.device("cuda:0")
+    # [frame][stream][sample] on the device: a block's chunk of one frame is one contiguous, 16-byte aligned slice
+    pcm_dev = torch.from_numpy(np.ascontiguousarray(pcm.reshape(S, n_frames, 1280).transpose(1, 0, 2))).to(dev)
+    hip_streams = [torch.cuda.Stream(dev) for _ in range(3)]
     one = StreamEngine(S, heads, emb)
-    monkeypatch.setenv("OWW_BLOCKS", "3")
-    three = StreamEngine(S, heads, emb)
+    parts = [StreamEngine(b1 - b0, heads, emb, hip_stream=st.cuda_stream)
+             for b0, b1, st in zip(borders[:-1], borders[1:], hip_streams)]
+    scores = torch.empty((n_frames, S, one.n_labels), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
     try:
         for rep in range(3):
-            one.reset(); three.reset()
+            one.reset()
+            for e in parts:
+                e.reset()
+            want = []
             for t in range(n_frames):
                 x = np.ascontiguousarray(pcm[:, 1280 * t: 1280 * (t + 1)])
-                if t == 7:
-                    a, b = one.step_masked(x, on), three.step_masked(x, on)
-                else:
-                    a, b = one.step(x), three.step(x)
-                np.testing.assert_array_equal(a, b, err_msg=f"repetition {rep} frame {t}")
-            assert a.max() > 0
-            for s_ in (0, 5503, 5504, S - 1):                        # embeddings too, either side of a block border
-                np.testing.assert_array_equal(one.get_features(s_, 4), three.get_features(s_, 4))
+                want.append(one.step_masked(x, on) if t == 7 else one.step(x))
+                for e, b0, b1 in zip(parts, borders[:-1], borders[1:]):
+                    x_ptr, sc_ptr = pcm_dev[t, b0:b1].data_ptr(), scores[t, b0:b1].data_ptr()
+                    if t == 7:
+                        e.step_masked_device(x_ptr, on[b0:b1], sc_ptr)
+                    else:
+                        e.step_device(x_ptr, 1, sc_ptr)
+            for e in parts:
+                e.sync()
+            got = scores.cpu().numpy()
+            for t in range(n_frames):
+                np.testing.assert_array_equal(want[t], got[t], err_msg=f"repetition {rep} frame {t}")
+            assert want[-1].max() > 0
+            for s_ in (0, 5503, 5504, 11007, 11008, S - 1):            # embeddings too, either side of a block border
+                k = np.searchsorted(borders, s_, side="right") - 1
+                np.testing.assert_array_equal(one.get_features(s_, 4), parts[k].get_features(s_ - borders[k], 4))
     finally:
         one.close()
-        three.close()
+        for e in parts:
+            e.close()
 
 
 def test_host_fed_pipeline_matches_blocking_steps(emb, heads):
