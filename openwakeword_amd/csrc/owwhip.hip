@@ -406,7 +406,6 @@ struct NetHost {
     const float* blocks;              // the n_blocks blocks back to back: w[H][H] b[H] (g[H] be[H])
     const float* rnn = nullptr;       // model_type "rnn" (kind 3): the head's blob (owk::heads_rnn_kernel); its size in rnn_floats
     size_t rnn_floats = 0;
-    int hx_e1 = 0, hx_e2 = 0, hx_e3 = 0;   // fp16-split heads: power-of-two scales of w1 / w2 (/ w3: wide form) (hx_weight_exp)
 };
 struct HeadHost {
     int kind, T, hidden, n_out, has_ln, n_blocks;
@@ -420,17 +419,90 @@ struct FastGroup {
     const float* d_w1pk = nullptr;
     const float* d_b1cat = nullptr;
     const float* d_w1hx = nullptr;    // fp16-split k-step-major layer-1 weights (heads_hx_kernel)
-    std::vector<const float*> d_w2hx; // per net
-    // fp16-split fast path: per net the seven per-unit arrays (b1, ln1 g / b, b2, ln2 g / b, w3) padded with zeros to the kernel's 64
-    // hidden units -- a narrower net (the reference's training pipeline defaults to 32: examples/custom_model.yml:89) runs as a
-    // 64-unit net whose padding units are identically zero and are left out of the LayerNorm statistics (owh::HeadHxNet::hidden)
-    std::vector<const float*> d_pad;  // per net: 7 x 64 floats (wide form: 6 x 128 + 16, see below)
-    // wide form (owh::heads_wide_tail: nets of up to 128 hidden units / 8 outputs, sigmoid or ReLU + softmax -- the multiclass `timer`
-    // model): ht = 8 hidden tiles per net, at most two nets per launch; d_pad = b1, ln1 g / b, b2, ln2 g / b padded to 128 units + b3
-    // padded to 16 outputs; the output layer as a third f16-split matrix
+    // fp16-split fast path: ht hidden tiles of 16 units per net.  4: nets of up to 64 units, zero-padded (pack_hx_net).  8: the wide
+    // form (owh::heads_wide_tail: nets of up to 128 hidden units / 8 outputs, sigmoid or ReLU + softmax -- the multiclass `timer`
+    // model), at most two nets per launch
     int ht = 4;
-    std::vector<const float*> d_w3hx; // per net
+    std::vector<owh::HeadHxNet> hx_net;   // per net: what the kernel reads behind the first layer (make_hx_net; built once at commit)
 };
+
+// A dense head net inside its blob: w1[T * 96][H] b1 (ln1g ln1b) | n_blocks x (w[H][H] b (g be)) | w3[H][O] b3.  Fills the net's shape
+// and pointers (LayerNorm arrays stay null without LayerNorm; w2 .. ln2b name block 0: what the MFMA head kernels read); returns the end.
+const float* parse_dense_net(const float* q, int T, int hidden, int n_out, int has_ln, int n_blocks, NetHost& n) {
+    const size_t K = (size_t)T * 96, H = hidden, O = n_out;
+    n.T = T; n.hidden = hidden; n.n_out = n_out; n.has_ln = has_ln; n.n_blocks = n_blocks;
+    n.w1 = q; q += K * H; n.b1 = q; q += H;
+    if (has_ln) { n.ln1g = q; q += H; n.ln1b = q; q += H; }
+    n.blocks = q;
+    if (n_blocks > 0) { n.w2 = q; n.b2 = q + H * H; }
+    if (n_blocks > 0 && has_ln) { n.ln2g = n.b2 + H; n.ln2b = n.ln2g + H; }
+    q += (size_t)n_blocks * (H * H + H + (has_ln ? 2 * H : 0));
+    n.w3 = q; q += H * O; n.b3 = q; q += O;
+    return q;
+}
+
+// ---- one net in the form of the fp16-split heads kernels (heads_hx_kernel, heads_bank_kernel), fixed heads and bank heads alike: ht
+// hidden tiles (4: up to 64 hidden units, one sigmoid output; 8: the wide form), HP = 16 ht units of which those beyond n.hidden are
+// identically zero and left out of the LayerNorm statistics (owh::HeadHxNet::hidden; the reference's training pipeline defaults to 32
+// units: examples/custom_model.yml:89).  Every matrix on its own power-of-two scale (hx_weight_exp), undone on the fp32 accumulators.
+struct HxNetPack {
+    int e1 = 0, e2 = 0, e3 = 0;           // scales of w1 / w2 / w3 (wide form)
+    size_t w2 = 0, w3 = 0, pad = 0;       // where pack_hx_net put the pieces, floats from the start of the image
+};
+// the scales of a net's matrices; false when a weight is not finite
+bool hx_net_scales(const NetHost& n, int ht, HxNetPack& p) {
+    const size_t K = (size_t)n.T * 96, H = n.hidden;
+    p.e1 = hx_weight_exp(n.w1, K * H); p.e2 = hx_weight_exp(n.w2, H * H); p.e3 = ht == 8 ? hx_weight_exp(n.w3, H * n.n_out) : 0;
+    return p.e1 != -1000 && p.e2 != -1000 && p.e3 != -1000;
+}
+
+// First layer: the net's w1[K][H] into columns [c0, c0 + H) of a zeroed [K][NH] matrix (its columns up to c0 + HP stay zero), 2^e1 as
+// the multiplier of its HP columns.  The caller packs the matrix (pack_hx_w1): a fixed group its nets side by side, a bank head its own.
+void place_w1(const NetHost& n, int c0, int HP, int NH, int e1, std::vector<float>& wcat, std::vector<double>& colmul) {
+    const size_t K = (size_t)n.T * 96, H = n.hidden;
+    for (size_t k = 0; k < K; ++k) memcpy(&wcat[k * NH + c0], n.w1 + k * H, H * sizeof(float));
+    for (int c = 0; c < HP; ++c) colmul[c0 + c] = std::ldexp(1.0, e1);
+}
+
+// Everything behind the first layer, appended to the image in this order: w2 zero-padded to [HP][HP]; in the wide form the output layer
+// as a third split matrix [HP][16] (outputs n_out .. 15 zero); the pad block -- b1, ln1 g / b, b2, ln2 g / b and, in the narrow form, w3
+// at a stride of HP floats, then b3: 16 floats in the wide form, 4 in the narrow form where b3_in_pad (bank heads), none otherwise
+// (the kernel reads a fixed narrow net's b3 from the net's natural array).
+void pack_hx_net(const NetHost& n, int ht, bool b3_in_pad, HostBuf& hb, HxNetPack& p) {
+    const size_t HP = 16 * (size_t)ht, H = n.hidden, O = n.n_out;
+    std::vector<float> pk;
+    auto add_split = [&](const float* w, size_t cols, size_t CP, int e) {      // w[H][cols] inside a zero [HP][CP], times 2^e
+        std::vector<double> cm(CP, std::ldexp(1.0, e));
+        HxFold fold; fold.colmul = cm.data();
+        std::vector<float> wp(HP * CP, 0.f);
+        for (size_t i = 0; i < H; ++i) memcpy(&wp[i * CP], w + i * cols, cols * sizeof(float));
+        pack_hx(wp.data(), 1, (int)HP, (int)CP, pk, &fold);
+        return hb.add(pk);
+    };
+    p.w2 = add_split(n.w2, H, HP, p.e2);
+    if (ht == 8) p.w3 = add_split(n.w3, O, 16, p.e3);
+    const size_t n_arr = ht == 8 ? 6 : 7, n_b3 = ht == 8 ? 16 : b3_in_pad ? 4 : 0;
+    std::vector<float> pad(n_arr * HP + n_b3, 0.f);
+    const float* src[7] = {n.b1, n.ln1g, n.ln1b, n.b2, n.ln2g, n.ln2b, n.w3};
+    for (size_t a = 0; a < n_arr; ++a) if (src[a]) memcpy(&pad[a * HP], src[a], H * sizeof(float));
+    if (n_b3) memcpy(&pad[n_arr * HP], n.b3, O * sizeof(float));
+    p.pad = hb.add(pad);
+}
+
+// The kernel's view of a packed net whose image starts at img (device).  b3: the narrow form's output bias where the pad block has none.
+owh::HeadHxNet make_hx_net(const NetHost& n, int ht, const HxNetPack& p, const float* img, const float* b3, int hx_efeat) {
+    const int HP = 16 * ht;
+    const float* pd = img + p.pad;
+    owh::HeadHxNet o{};
+    o.w2hx = img + p.w2; o.b1 = pd; o.ln1g = pd + HP; o.ln1b = pd + 2 * HP; o.b2 = pd + 3 * HP; o.ln2g = pd + 4 * HP; o.ln2b = pd + 5 * HP;
+    if (ht == 4) { o.w3 = pd + 6 * HP; o.b3 = b3 ? b3 : pd + 7 * HP; }
+    else { o.b3 = pd + 6 * HP; o.w3hx = img + p.w3; o.u3 = std::ldexp(1.0f, -p.e3); }
+    o.has_ln = n.has_ln; o.role = n.role; o.head = n.head; o.out_col = n.out_col;
+    o.hidden = n.hidden; o.inv_hidden = 1.0f / (float)n.hidden;
+    o.u1 = std::ldexp(1.0f, -(hx_efeat + p.e1)); o.u2 = std::ldexp(1.0f, -p.e2);
+    o.n_out = n.n_out; o.final_act = n.final_act;
+    return o;
+}
 
 constexpr int N_STATE = 11;
 // per-stream floats of every state array: hist_mel, hist2, B:b,d  C:b,d  D:b,d  E:b,d  hist19
@@ -469,13 +541,10 @@ struct oww_ctx {
     const float* d_conv[20] = {};     // layer 0: natural [9][24]; 1..19: packed (mfma) or natural (valu)
     const float* d_scale[20] = {};
     const float* d_shift[20] = {};
-    const float* d_conv0_mfma = nullptr;   // conv0 in MFMA k-step order (shared by the LDS-MFMA and register-resident kernels)
     NetDesc* d_allnets = nullptr;
-    std::vector<NetDesc> host_descs;  // device pointers of every net's arrays (host copy of d_allnets)
     std::vector<FastGroup> groups;
     std::vector<int> generic_nets;    // indices into nets (with verifier right after its primary)
     std::vector<int> rnn_nets;        // recurrent heads (train.py:85-98): owk::heads_rnn_kernel, one launch per head
-    NetDesc* d_generic = nullptr;
     int generic_hmax = 0;
     int generic_spw = 0;              // OWW_GENERIC_SPW: 4 / 16 pins the generic heads kernel's shape, 0 = by launch size
     // state
@@ -554,7 +623,7 @@ struct oww_ctx {
         bool live = false;
         int T = 0, hidden = 0, has_ln = 0, ht = 4, patience = 0;
         float threshold = NAN;
-        float* d_img = nullptr;                  // w1hx | w2hx | padded per-unit arrays (| w3hx): the packing of a fixed net of the same width
+        float* d_img = nullptr;                  // w1hx | the pieces of pack_hx_net: the packing of a fixed net of the same width
         size_t w1_bytes = 0;                     // first-layer weight bytes one tile streams
         owh::BankHeadDev dev{};
     };
@@ -816,19 +885,7 @@ int run_heads(oww_ctx* h, const StepArgs& a, int n_active, bool accumulate_max, 
                     pp.patience = h->d_patience; pp.threshold = h->d_threshold; pp.debounce_frames = h->debounce_frames;
                     pp.vad_ring = h->d_vadring; pp.n_vad = h->d_nvad; pp.vad_threshold = h->vad_threshold;
                 }
-                for (int i = 0; i < g.n_nets; ++i) {
-                    const NetHost& n = h->nets[g.nets[i]];
-                    const NetDesc d = h->host_descs[g.nets[i]];
-                    owh::HeadHxNet& o = q.net[i];
-                    const float* pd = g.d_pad[i];                      // the per-unit arrays padded to 64 (wide form: 128) units
-                    const int HP = 16 * g.ht;
-                    o.w2hx = g.d_w2hx[i]; o.b1 = pd; o.ln1g = pd + HP; o.ln1b = pd + 2 * HP; o.b2 = pd + 3 * HP; o.ln2g = pd + 4 * HP; o.ln2b = pd + 5 * HP;
-                    o.w3 = pd + 6 * HP; o.b3 = d.b3; o.has_ln = n.has_ln; o.role = n.role; o.head = n.head; o.out_col = n.out_col;
-                    o.hidden = n.hidden; o.inv_hidden = 1.0f / (float)n.hidden;
-                    o.u1 = std::ldexp(1.0f, -(h->hx_efeat + n.hx_e1)); o.u2 = std::ldexp(1.0f, -n.hx_e2);
-                    o.n_out = n.n_out; o.final_act = n.final_act;
-                    if (g.ht == 8) { o.w3 = nullptr; o.b3 = pd + 6 * HP; o.w3hx = g.d_w3hx[i]; o.u3 = std::ldexp(1.0f, -n.hx_e3); }
-                }
+                for (int i = 0; i < g.n_nets; ++i) q.net[i] = g.hx_net[i];
                 q.fscale = std::ldexp(1.0f, h->hx_efeat);
                 const dim3 grid((n_pos + 32 * owh::HX_WG - 1) / (32 * owh::HX_WG)), block(64 * owh::HX_WG);
                 // a launch that leaves workgroups alone on their CUs runs the deep weight ring (owwhip_hx.h: HX_NBUF_DEEP); same results
@@ -985,7 +1042,7 @@ void free_all(oww_ctx* h) {
     for (hipStream_t st : {h->up_stream, h->down_stream})
         if (st) (void)hipStreamSynchronize(st);
     auto fr = [](auto*& p) { if (p) { (void)dev_free((void*)p); p = nullptr; } };
-    fr(h->d_w); fr(h->d_allnets); fr(h->d_generic);
+    fr(h->d_w); fr(h->d_allnets);
     for (auto& g : h->groups) fr(g.d_nets);
     for (int a = 0; a < N_STATE; ++a) { fr(h->d_state[a]); fr(h->d_tmpl[a]); }
     fr(h->d_xA); fr(h->d_xB); fr(h->d_xC); fr(h->d_xD); fr(h->d_mel); fr(h->d_feat); fr(h->d_emb); fr(h->d_raw);
@@ -1577,17 +1634,13 @@ int bank_route(oww_ctx* h) {
     return 0;
 }
 
-// float64 evaluation of a binary one-block net (blob after the header) on one window x[T][96]: the bank self-test's reference
-double bank_eval_f64(const float* q, int T, int H, int has_ln, const float* x) {
-    const size_t K = (size_t)T * 96;
-    const float *w1 = q, *b1 = w1 + K * H, *g1 = b1 + H, *e1 = g1 + H;
-    const float* w2 = has_ln ? e1 + H : b1 + H;
-    const float *b2 = w2 + (size_t)H * H, *g2 = b2 + H, *e2 = g2 + H;
-    const float* w3 = has_ln ? e2 + H : b2 + H;
-    const float* b3 = w3 + H;
+// float64 evaluation of a binary one-block net on one window x[T][96]: the bank self-test's reference
+double bank_eval_f64(const NetHost& n, const float* x) {
+    const size_t K = (size_t)n.T * 96;
+    const int H = n.hidden;
     std::vector<double> a(H), z(H);
     auto ln_relu = [&](std::vector<double>& v, const float* g, const float* be) {
-        if (has_ln) {
+        if (n.has_ln) {
             double mu = 0.0, var = 0.0;
             for (int i = 0; i < H; ++i) mu += v[i];
             mu /= H;
@@ -1597,20 +1650,485 @@ double bank_eval_f64(const float* q, int T, int H, int has_ln, const float* x) {
         }
         for (int i = 0; i < H; ++i) v[i] = std::max(v[i], 0.0);
     };
-    for (int i = 0; i < H; ++i) a[i] = b1[i];
-    for (size_t k = 0; k < K; ++k) for (int i = 0; i < H; ++i) a[i] += (double)x[k] * w1[k * H + i];
-    ln_relu(a, g1, e1);
-    for (int i = 0; i < H; ++i) z[i] = b2[i];
-    for (int k = 0; k < H; ++k) for (int i = 0; i < H; ++i) z[i] += a[k] * w2[(size_t)k * H + i];
-    ln_relu(z, g2, e2);
-    double o = b3[0];
-    for (int i = 0; i < H; ++i) o += z[i] * w3[i];
+    for (int i = 0; i < H; ++i) a[i] = n.b1[i];
+    for (size_t k = 0; k < K; ++k) for (int i = 0; i < H; ++i) a[i] += (double)x[k] * n.w1[k * H + i];
+    ln_relu(a, n.ln1g, n.ln1b);
+    for (int i = 0; i < H; ++i) z[i] = n.b2[i];
+    for (int k = 0; k < H; ++k) for (int i = 0; i < H; ++i) z[i] += a[k] * n.w2[(size_t)k * H + i];
+    ln_relu(z, n.ln2g, n.ln2b);
+    double o = n.b3[0];
+    for (int i = 0; i < H; ++i) o += z[i] * n.w3[i];
     return 1.0 / (1.0 + std::exp(-o));
 }
 
 void comm_release(oww_ctx* h) {
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
     h->comm = nullptr; h->comm_rank = 0; h->comm_world = 1;
+}
+
+// blob of oww_load_vad (floats after the 8-int header): gain, hann[256], 4 x (w[3][cin][cout], b[cout]), 2 x (w[128][256], b[256]), wd[64], bd
+const int kVadEnc[4][2] = {{128, 16}, {16, 32}, {32, 32}, {32, 64}};
+size_t vad_blob_floats() {
+    size_t n = 1 + 256;
+    for (auto& e : kVadEnc) n += (size_t)3 * e[0] * e[1] + e[1];
+    n += 2 * ((size_t)128 * 256 + 256) + 64 + 1;
+    return n;
+}
+
+// ---- oww_commit, phase by phase ------------------------------------------------------------------------------------------------------
+// Where the pack_* phases put every piece of the device weight image (floats from its start); bind_weights turns them into pointers.
+struct WeightOff {
+    size_t hann = 0, start = 0, taps = 0, meloff = 0, meldst = 0;
+    size_t conv[20] = {}, scale[20] = {}, shift[20] = {};
+    struct Net { size_t w1, b1, ln1g, ln1b, w2, b2, ln2g, ln2b, w3, b3, w2pk, blocks, rnn; };
+    std::vector<Net> net;                       // natural arrays of every net
+    struct Group { size_t w1pk = 0, b1cat = 0, w1hx = 0; std::vector<HxNetPack> net; };
+    std::vector<Group> group;                   // per FastGroup
+    size_t vhann = 0, vencw = 0, vencb = 0, vlw = 0, vlb = 0, vwd = 0;
+};
+
+// heads -> nets, label columns, feature-ring depth
+int build_nets(oww_ctx* h) {
+    h->nets.clear(); h->head_nets.clear();
+    int col = 0, maxT = 16, hmax = 1;
+    for (size_t hi = 0; hi < h->heads.size(); ++hi) {
+        HeadHost& hh = h->heads[hi];
+        hh.out_col = col;
+        const float* q = hh.blob.data();
+        const int begin = (int)h->nets.size();
+        for (int r = 0; r < (hh.kind == 1 ? 2 : 1); ++r) {                   // (gated heads: two nets)
+            NetHost n{};
+            n.head = (int)hi; n.role = r; n.out_col = col;
+            if (hh.kind == 3) {                                              // recurrent head: one net, its blob as a whole
+                n.hidden = hh.hidden; n.n_out = hh.n_out; n.T = hh.T; n.final_act = hh.n_out == 1 ? 0 : 1;
+                n.rnn = q; n.rnn_floats = hh.blob.size();
+            } else {
+                q = parse_dense_net(q, hh.T, hh.hidden, hh.n_out, hh.has_ln, hh.n_blocks, n);
+                n.final_act = hh.kind == 2 ? 1 : 0;
+            }
+            h->nets.push_back(n);
+        }
+        h->head_nets.push_back({begin, (int)h->nets.size()});
+        col += hh.n_out;
+        maxT = std::max(maxT, hh.T);
+        hmax = std::max(hmax, hh.hidden);
+    }
+    h->NL = col;
+    if (h->NL > OWW_MAX_LABELS) return fail(OWW_EINVAL, "too many labels (%d)", h->NL);
+    h->TR = h->cfg.feature_ring > 0 ? std::max(h->cfg.feature_ring, maxT) : maxT;
+    h->generic_hmax = hmax;
+    return 0;
+}
+
+// The mel front end's tables.  Fused front end: the sparse mel taps read a COMPACT copy of each frame's power row -- one segment per mel
+// bin, [first tap .. last non-zero tap] -- whose segment starts have pairwise different residues mod 32, so that the 32 lanes of a tap
+// read hit 32 different LDS banks (the plain power row gave three bins per bank for every tap: most of the launch's bank conflicts).
+// Every power bin belongs to at most two triangular filters, hence two destinations per bin (mel_dst: lo / hi 16 bits; kMelJunk = none).
+int pack_mel_tables(const oww_ctx* h, HostBuf& hb, WeightOff& o) {
+    o.hann = hb.add(h->mel_blob.data(), 400);
+    o.start = hb.add(h->mel_blob.data() + 400, 32);          // int32 bit patterns
+    o.taps = hb.add(h->mel_blob.data() + 432, 512);
+    constexpr int kMelTable = 250, kMelJunk = 250;           // floats of a frame's table; bins without a second filter store here
+    const int32_t* start = reinterpret_cast<const int32_t*>(h->mel_blob.data() + 400);
+    const float* taps = h->mel_blob.data() + 432;
+    int nz[32], first[32];
+    for (int m = 0; m < 32; ++m) {
+        nz[m] = 0;
+        for (int t = 0; t < 16; ++t) if (taps[m * 16 + t] != 0.f) nz[m] = t + 1;
+        first[m] = start[m] - 2;                              // power-row index of tap 0 (the kernels keep FFT bins 2..121)
+    }
+    int off[32], best[32], best_end = 1 << 30;
+    uint64_t st = 0x9E3779B97F4A7C15ull;
+    for (int it = 0; it < 20000 && best_end > kMelTable; ++it) {                // randomised first-fit; a few hundred tries are enough
+        int order[32];
+        for (int i = 0; i < 32; ++i) order[i] = i;
+        for (int i = 31; i > 0; --i) { st ^= st << 13; st ^= st >> 7; st ^= st << 17; std::swap(order[i], order[st % (uint64_t)(i + 1)]); }
+        unsigned used = 0; int cur = 0, end = 0;
+        for (int i = 0; i < 32; ++i) {
+            const int m = order[i];
+            int p = cur;
+            while (used >> (p & 31) & 1u) ++p;
+            used |= 1u << (p & 31); off[m] = p; cur = p + nz[m];
+            end = std::max(end, p + 16);                      // a lane reads 16 taps from its start
+        }
+        if (end < best_end) { best_end = end; memcpy(best, off, sizeof off); }
+    }
+    if (best_end > kMelTable) {                               // (cannot happen for a 32-filter bank of <= 16 taps; plain prefix layout)
+        int cur = 0;
+        for (int m = 0; m < 32; ++m) { best[m] = cur; cur += nz[m]; }
+        if (cur + 16 > kMelTable) return fail(OWW_EINVAL, "oww_commit: the mel filter bank has more than %d taps", kMelTable - 16);
+    }
+    std::vector<float> dst(128, 0.f);
+    for (int i = 0; i < 120; ++i) {
+        uint32_t d[2] = {kMelJunk, kMelJunk}; int n = 0;
+        for (int m = 0; m < 32; ++m) {
+            const int t = i - first[m];
+            if (t >= 0 && t < nz[m] && taps[m * 16 + t] != 0.f) {
+                if (n == 2) return fail(OWW_EINVAL, "oww_commit: FFT bin %d feeds more than two mel filters (not a triangular filter bank)", i + 2);
+                d[n++] = (uint32_t)(best[m] + t);
+            }
+        }
+        const uint32_t packed = d[0] | (d[1] << 16);
+        memcpy(&dst[i], &packed, 4);
+    }
+    std::vector<float> offf(32);
+    for (int m = 0; m < 32; ++m) { const int32_t v = best[m]; memcpy(&offf[m], &v, 4); }
+    o.meloff = hb.add(offf.data(), 32);
+    o.meldst = hb.add(dst.data(), 128);
+    return 0;
+}
+
+// the 20 layers of the embedding CNN in the operand order of the handle's kernel family, each followed by its BatchNorm arrays
+int pack_cnn(const oww_ctx* h, HostBuf& hb, WeightOff& o) {
+    const float* q = h->emb_blob.data();
+    std::vector<float> pk;
+    for (int l = 0; l < 20; ++l) {
+        const LayerDef& L = kLayers[l];
+        const size_t nw = (size_t)L.kh * L.kw * L.cin * L.cout;
+        const float* bn_scale = l < 19 ? q + nw : nullptr;             // folded inference BatchNorm of this layer (blob order: w, scale, shift)
+        if (!h->mfma) o.conv[l] = hb.add(q, nw);
+        else if (h->hx) {
+            // fold_cnn: W' = s w 2^(e_out - e_in) per output channel (calibrate_hx's scale ladder; e_in = 0 for the mel input)
+            std::vector<double> colmul(L.cout);
+            const int de = h->hx_e[l] - h->hx_ein[l];
+            for (int c = 0; c < L.cout; ++c) colmul[c] = std::ldexp(bn_scale ? (double)bn_scale[c] : 1.0, de);
+            HxFold fold; fold.colmul = colmul.data();
+            const bool time_merged = OWH_KMERGE && L.kh == 3 && L.kw == 1 && ((L.cin + 15) / 16) % 2 == 1 &&
+                                     (L.cin % 16 == 8 || OWH_KMERGE_B);                     // stage C (and B): layers b, d
+            // 1x3 layers with a 72-channel input (stage C layer c, stage D layer a): owh::conv_mel_hxm, same packing rule
+            const bool mel_merged = OWH_KMERGE_MEL && owh::kInterleave && L.kh == 1 && L.kw == 3 &&
+                                    ((L.cin + 15) / 16) % 2 == 1 && (L.cin + 15) / 16 >= 3 &&
+                                    (L.cin % 16 == 8 || (OWH_KMERGE_MEL2 && l == 7 && OWH_WPS_C == 2) ||   // (l == 7: stage C layer a, 48 -> 72)
+                                     (OWH_KMERGE_MEL2B && l == 5));                                   // (l == 5: stage B layer c, A/B switch)
+            if (l == 0) pack_hx_conv0(q, pk, &fold);
+            else if (l <= 2) pack_hx_stage_a(q, l, pk, &fold);
+            else if (time_merged || mel_merged) pack_hx_tm(q, L.cin, L.cout, pk, &fold);
+            else pack_hx(q, 3, L.cin, L.cout, pk, &fold, OWH_REM2 && !OWH_KMERGE_B && !OWH_KMERGE_MEL2B && l >= 4 && l <= 6);     // (stage B layers b, c, d)
+            if (!(fold.absmax < 65000.0))
+                return fail(OWW_ERANGE, "conv layer %d: folded weight magnitude %.3g (BatchNorm scale x weight x activation-scale ratio 2^%d) is outside "
+                            "the f16 range of the fp16-split kernels (use_mfma = 3); use use_mfma = 1", l, fold.absmax, de);
+            o.conv[l] = hb.add(pk);
+        }
+        else if (h->rr && l > 0) { pack_rr(q, 3, L.cin, L.cout, pk); o.conv[l] = hb.add(pk); }
+        else if (l == 0) {
+            // conv0: K = 9 taps padded to 12 -> three k-steps; lane (i, j) of k-step s holds w[k = 4s+j][cout = 16ct+i]
+            pk.assign(2 * 3 * 64, 0.f);
+            for (int ct = 0; ct < 2; ++ct)
+                for (int s = 0; s < 3; ++s)
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int k = 4 * s + (lane >> 4), co = ct * 16 + (lane & 15);
+                        if (k < 9 && co < 24) pk[(ct * 3 + s) * 64 + lane] = q[k * 24 + co];
+                    }
+            o.conv[l] = hb.add(pk);
+        } else { pack_mfma(q, 3, L.cin, L.cout, pk); o.conv[l] = hb.add(pk); }
+        q += nw;
+        if (l < 19) {
+            // zero padded to whole 16-channel tiles: the register-resident kernels evaluate the pad channels (as zeros)
+            std::vector<float> pad((size_t)(L.cout + 15) / 16 * 16, 0.f);
+            if (h->hx) {
+                // f16-split family: the scale lives in the weights.  Slot "scale" is only read by conv0: the third operand of the
+                // med3 that applies its ReLU in the folded form (+inf where the BatchNorm scale is >= 0, -inf where it is negative)
+                std::vector<float> bound(L.cout);
+                for (int c = 0; c < L.cout; ++c) bound[c] = q[c] < 0.f ? -INFINITY : INFINITY;
+                pad_hx_rows(bound.data(), L.cout, 1.0f, pad);
+            }
+            else memcpy(pad.data(), q, L.cout * sizeof(float));
+            o.scale[l] = hb.add(pad); q += L.cout;
+            std::fill(pad.begin(), pad.end(), 0.f);
+            if (h->hx) pad_hx_rows(q, L.cout, std::ldexp(1.0f, h->hx_e[l]), pad);       // accumulator start values K h, tile row order
+            else memcpy(pad.data(), q, L.cout * sizeof(float));
+            o.shift[l] = hb.add(pad); q += L.cout;
+        }
+    }
+    return 0;
+}
+
+// heads: the natural arrays of every net (+ packed w2 for hidden == 64), then the heads' nets sorted into fast groups, generic nets and
+// recurrent nets, and the image of every fast group
+int pack_head_nets(oww_ctx* h, HostBuf& hb, WeightOff& off) {
+    off.net.assign(h->nets.size(), WeightOff::Net{});
+    for (size_t ni = 0; ni < h->nets.size(); ++ni) {
+        const NetHost& n = h->nets[ni];
+        WeightOff::Net& o = off.net[ni];
+        if (n.rnn) { o.rnn = hb.add(n.rnn, n.rnn_floats); continue; }
+        const size_t in = (size_t)n.T * 96, H = n.hidden, O = n.n_out;
+        o.w1 = hb.add(n.w1, in * H); o.b1 = hb.add(n.b1, H);
+        o.ln1g = n.has_ln ? hb.add(n.ln1g, H) : 0; o.ln1b = n.has_ln ? hb.add(n.ln1b, H) : 0;
+        const size_t blk = H * H + H + (n.has_ln ? 2 * H : 0);
+        o.blocks = n.n_blocks > 0 ? hb.add(n.blocks, (size_t)n.n_blocks * blk) : 0;      // (the generic kernel walks them in place)
+        if (n.n_blocks > 0) {
+            o.w2 = hb.add(n.w2, H * H); o.b2 = hb.add(n.b2, H);
+            o.ln2g = n.has_ln ? hb.add(n.ln2g, H) : 0; o.ln2b = n.has_ln ? hb.add(n.ln2b, H) : 0;
+        }
+        o.w3 = hb.add(n.w3, H * O); o.b3 = hb.add(n.b3, O);
+        if (n.hidden == 64 && n.n_blocks == 1) { std::vector<float> pk; pack_mfma(n.w2, 1, 64, 64, pk); o.w2pk = hb.add(pk); }
+    }
+    // grouping: heads whose nets are all (hidden 64, n_out 1, sigmoid) share a fast group per T (<= 8 nets each)
+    h->groups.clear(); h->generic_nets.clear(); h->rnn_nets.clear();
+    for (size_t hi = 0; hi < h->heads.size(); ++hi) {
+        const auto [nb, ne] = h->head_nets[hi];
+        if (h->nets[nb].rnn) { h->rnn_nets.push_back(nb); continue; }       // recurrent heads have their own kernel in every family
+        bool fast = h->mfma;
+        // the MFMA head kernels: sigmoid nets of one output and one hidden block; exactly 64 hidden units in the fp32 family
+        // (heads64_kernel), up to 64 in the fp16-split family (zero-padded, see pack_hx_net)
+        for (int ni = nb; ni < ne; ++ni)
+            fast = fast && (h->nets[ni].hidden == 64 || (h->hx && h->nets[ni].hidden <= 64)) && h->nets[ni].n_out == 1 &&
+                   h->nets[ni].final_act == 0 && h->nets[ni].n_blocks == 1;
+        // the wide form of the fp16-split heads kernel: ungated nets of up to 128 hidden units and 8 outputs with one hidden block
+        // (the released multiclass `timer`: docs/models/timers.md:9-27; train.py's default layer_dim = 128)
+        bool wide = !fast && h->hx && h->mfma && ne - nb == 1 && !getenv("OWW_NO_WIDE_HEADS");
+        for (int ni = nb; ni < ne; ++ni) wide = wide && h->nets[ni].hidden <= 128 && h->nets[ni].n_out <= 8 && h->nets[ni].n_blocks == 1 && h->nets[ni].role == 0;
+        if (!fast && !wide) { for (int ni = nb; ni < ne; ++ni) h->generic_nets.push_back(ni); continue; }
+        FastGroup* g = nullptr;
+        const int ht = wide ? 8 : 4;
+        const int cap = h->hx ? 16 / ht : HD_MAXNETS;                // heads_hx_kernel: at most sixteen hidden tiles per launch
+        for (auto& gg : h->groups) if (gg.T == h->nets[nb].T && gg.ht == ht && gg.n_nets + (ne - nb) <= cap) { g = &gg; break; }
+        if (!g) { h->groups.push_back(FastGroup{}); g = &h->groups.back(); g->T = h->nets[nb].T; g->n_nets = 0; g->ht = ht; }
+        for (int ni = nb; ni < ne; ++ni) { g->nets.push_back(ni); g->n_nets++; }
+    }
+    // group images: the first layers of a group's nets side by side, HP = 16 ht columns per net -- for heads64_kernel (narrow groups,
+    // with the concatenated b1) and, fp16-split family, for heads_hx_kernel -- then every net's pack_hx_net pieces
+    for (auto& g : h->groups) {
+        const int HP = 16 * g.ht;
+        g.NH = HP * g.n_nets;
+        const size_t K = (size_t)g.T * 96;
+        std::vector<float> wcat(K * g.NH, 0.f), pk;
+        std::vector<double> colmul(g.NH);
+        WeightOff::Group go;
+        go.net.resize(g.n_nets);
+        for (int gi = 0; gi < g.n_nets; ++gi) {
+            const NetHost& n = h->nets[g.nets[gi]];
+            if (h->hx && !hx_net_scales(n, g.ht, go.net[gi])) return fail(OWW_EINVAL, "head weights are not finite");
+            place_w1(n, HP * gi, HP, g.NH, go.net[gi].e1, wcat, colmul);
+        }
+        if (g.ht == 4) {
+            std::vector<float> bcat(g.NH, 0.f);
+            for (int gi = 0; gi < g.n_nets; ++gi) memcpy(&bcat[64 * gi], h->nets[g.nets[gi]].b1, h->nets[g.nets[gi]].hidden * sizeof(float));
+            pack_mfma(wcat.data(), g.T, 96, g.NH, pk);
+            go.w1pk = hb.add(pk); go.b1cat = hb.add(bcat);
+        }
+        if (h->hx) {
+            pack_hx_w1(wcat.data(), (int)K, g.NH, colmul.data(), pk);
+            go.w1hx = hb.add(pk);
+            for (int gi = 0; gi < g.n_nets; ++gi) pack_hx_net(h->nets[g.nets[gi]], g.ht, false, hb, go.net[gi]);
+        }
+        off.group.push_back(go);
+    }
+    return 0;
+}
+
+// voice-activity stand-in (always fp16-split MFMA kernels, whatever the CNN family)
+int pack_vad(oww_ctx* h, HostBuf& hb, WeightOff& o) {
+    h->vad = !h->vad_blob.empty();
+    if (!h->vad) return 0;
+    const float* q = h->vad_blob.data();
+    h->vad_gain = *q++;
+    o.vhann = hb.add(q, 256); q += 256;
+    std::vector<float> encw, encb(4 * 64, 0.f), pk;
+    for (int l = 0; l < 4; ++l) {
+        const int cin = kVadEnc[l][0], cout = kVadEnc[l][1];
+        if (!hx_in_range(q, (size_t)3 * cin * cout)) return fail(OWW_EINVAL, "VAD encoder weights too large for the fp16-split kernels");
+        pack_hx(q, 3, cin, cout, pk);
+        encw.insert(encw.end(), pk.begin(), pk.end());
+        q += (size_t)3 * cin * cout;
+        memcpy(&encb[l * 64], q, cout * sizeof(float)); q += cout;
+    }
+    if (encw.size() != (size_t)owv::V_WFLOATS) return fail(OWW_EINVAL, "internal: VAD encoder image is %zu floats, expected %d", encw.size(), owv::V_WFLOATS);
+    o.vencw = hb.add(encw); o.vencb = hb.add(encb);
+    std::vector<float> lw, lb;
+    for (int l = 0; l < 2; ++l) {
+        if (!hx_in_range(q, (size_t)128 * 256)) return fail(OWW_EINVAL, "VAD LSTM weights too large for the fp16-split kernels");
+        // columns regrouped so that the four gates of hidden tile u are neighbours: column 16 (4u + gate) + i <- gate * 64 + 16u + i
+        std::vector<float> perm((size_t)128 * 256);
+        for (int k = 0; k < 128; ++k)
+            for (int u = 0; u < 4; ++u)
+                for (int gt = 0; gt < 4; ++gt)
+                    for (int i = 0; i < 16; ++i) perm[(size_t)k * 256 + 16 * (4 * u + gt) + i] = q[(size_t)k * 256 + gt * 64 + 16 * u + i];
+        pack_hx(perm.data(), 1, 128, 256, pk);
+        lw.insert(lw.end(), pk.begin(), pk.end());
+        q += (size_t)128 * 256;
+        lb.insert(lb.end(), q, q + 256); q += 256;
+    }
+    o.vlw = hb.add(lw); o.vlb = hb.add(lb);
+    o.vwd = hb.add(q, 64); q += 64;
+    h->vad_bd = *q;
+    return 0;
+}
+
+// upload the image; offsets -> device pointers, the NetDesc tables and the fast groups' HeadHxNets
+int bind_weights(oww_ctx* h, const HostBuf& hb, const WeightOff& off) {
+    HIPCHK(dev_alloc(&h->d_w, hb.data.size() * sizeof(float)));
+    HIPCHK(copy_sync(h->d_w, hb.data.data(), hb.data.size() * sizeof(float), hipMemcpyHostToDevice));
+    const float* w = h->d_w;
+    h->d_hann = w + off.hann; h->d_mstart = reinterpret_cast<const int*>(w + off.start); h->d_taps = w + off.taps;
+    h->d_meloff = reinterpret_cast<const int*>(w + off.meloff); h->d_meldst = reinterpret_cast<const unsigned*>(w + off.meldst);
+    if (h->vad) {
+        h->d_vad_hann = w + off.vhann; h->d_vad_encw = w + off.vencw; h->d_vad_encb = w + off.vencb;
+        h->d_vad_lstmw = w + off.vlw; h->d_vad_lstmb = w + off.vlb; h->d_vad_wd = w + off.vwd;
+    }
+    for (int l = 0; l < 20; ++l) {
+        h->d_conv[l] = w + off.conv[l];
+        h->d_scale[l] = l < 19 ? w + off.scale[l] : nullptr;
+        h->d_shift[l] = l < 19 ? w + off.shift[l] : nullptr;
+    }
+    auto make_desc = [&](int ni, int hid_off) {
+        const NetHost& n = h->nets[ni];
+        const WeightOff::Net& o = off.net[ni];
+        NetDesc d{};
+        d.hidden = n.hidden; d.n_out = n.n_out; d.has_ln = n.has_ln; d.final_act = n.final_act; d.T = n.T;
+        d.head = n.head; d.role = n.role; d.out_col = n.out_col; d.hid_off = hid_off;
+        if (n.rnn) { d.rnn = w + o.rnn; return d; }
+        d.w1 = w + o.w1; d.b1 = w + o.b1;
+        d.ln1g = n.has_ln ? w + o.ln1g : nullptr; d.ln1b = n.has_ln ? w + o.ln1b : nullptr;
+        d.n_blocks = n.n_blocks;
+        d.blocks = n.n_blocks > 0 ? w + o.blocks : nullptr;
+        d.w2 = n.n_blocks > 0 ? w + o.w2 : nullptr; d.b2 = n.n_blocks > 0 ? w + o.b2 : nullptr;
+        d.ln2g = n.has_ln && n.n_blocks > 0 ? w + o.ln2g : nullptr; d.ln2b = n.has_ln && n.n_blocks > 0 ? w + o.ln2b : nullptr;
+        d.w3 = w + o.w3; d.b3 = w + o.b3;
+        d.w2pk = n.hidden == 64 && n.n_blocks == 1 ? w + o.w2pk : nullptr;
+        return d;
+    };
+    if (!h->nets.empty()) {
+        std::vector<NetDesc> all;
+        for (size_t ni = 0; ni < h->nets.size(); ++ni) all.push_back(make_desc((int)ni, 0));
+        HIPCHK(dev_alloc(&h->d_allnets, all.size() * sizeof(NetDesc)));
+        HIPCHK(copy_sync(h->d_allnets, all.data(), all.size() * sizeof(NetDesc), hipMemcpyHostToDevice));
+    }
+    for (size_t gi = 0; gi < h->groups.size(); ++gi) {
+        FastGroup& g = h->groups[gi];
+        const WeightOff::Group& go = off.group[gi];
+        std::vector<NetDesc> ds;
+        for (int i = 0; i < g.n_nets; ++i) ds.push_back(make_desc(g.nets[i], 64 * i));
+        HIPCHK(dev_alloc(&g.d_nets, ds.size() * sizeof(NetDesc)));
+        HIPCHK(copy_sync(g.d_nets, ds.data(), ds.size() * sizeof(NetDesc), hipMemcpyHostToDevice));
+        g.d_w1pk = w + go.w1pk; g.d_b1cat = w + go.b1cat;
+        if (!h->hx) continue;
+        g.d_w1hx = w + go.w1hx;
+        for (int i = 0; i < g.n_nets; ++i)
+            g.hx_net.push_back(make_hx_net(h->nets[g.nets[i]], g.ht, go.net[i], w, g.ht == 4 ? w + off.net[g.nets[i]].b3 : nullptr, h->hx_efeat));
+    }
+    return 0;
+}
+
+// sticky range flag of the f16-split kernels: page-locked + device-mapped, so the host reads it without a copy
+int alloc_range_flag(oww_ctx* h) {
+    void* dp = nullptr;
+    HIPCHK(hipHostMalloc((void**)&h->h_range, 64, hipHostMallocMapped));
+    h->h_range[0] = 0; h->h_range[1] = -1;
+    HIPCHK(hipHostGetDevicePointer(&dp, h->h_range, 0));
+    h->d_range = (int*)dp;
+    return 0;
+}
+
+// every per-stream buffer, zero-filled on the handle's stream
+int alloc_state(oww_ctx* h) {
+    const size_t SP = h->Spad;
+    for (int a = 0; a < N_STATE; ++a) {
+        if (int rc = dalloc(h->stream, &h->d_state[a], SP * h->state_len[a])) return rc;
+        if (int rc = dalloc(h->stream, &h->d_tmpl[a], (size_t)h->state_len[a] * (h->rr ? kStateSpgRr[a] : 1))) return rc;
+    }
+    const int* xlen = h->rr ? kXLenRr : kXLenLds;
+    float** x[4] = {&h->d_xA, &h->d_xB, &h->d_xC, &h->d_xD};
+    for (int i = 0; i < 4; ++i) if (int rc = dalloc(h->stream, x[i], SP * xlen[i])) return rc;
+    if (int rc = dalloc(h->stream, &h->d_mel, SP * 8 * h->kmax * 32)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_feat, SP * h->TR * 96)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_emb, SP * 96)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_raw, SP * std::max(h->NL, 1))) return rc;
+    if (int rc = dalloc(h->stream, &h->d_scores, SP * std::max(h->NL, 1))) return rc;
+    if (int rc = dalloc(h->stream, &h->d_ring, SP * std::max(h->NL, 1) * OWW_SCORE_RING)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_featinit, (size_t)h->TR * 96)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_nfeat, SP)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_npred, SP)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_vadring, SP * 8)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_nvad, SP)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_vadin, SP)) return rc;
+    if (h->vad) {
+        const size_t G = (SP + 15) / 16;
+        if (int rc = dalloc(h->stream, &h->d_vadx, G * 4 * 1024)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_vadhc, G * 4096)) return rc;
+        if (int rc = dalloc(h->stream, &h->d_vadlast, SP)) return rc;
+    }
+    if (int rc = dalloc(h->stream, &h->d_tail, SP * 480)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_pcm, (size_t)h->S * OWW_CHUNK * h->kmax)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_patience, (size_t)std::max(h->NL, 1))) return rc;
+    if (int rc = dalloc(h->stream, &h->d_threshold, (size_t)std::max(h->NL, 1))) return rc;
+    {
+        std::vector<float> nanv(std::max(h->NL, 1), NAN);
+        HIPCHK(copy_async(h->d_threshold, nanv.data(), nanv.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));   // (behind the buffer's zero fill, same stream)
+    }
+    if (h->cfg.debug_layers) if (int rc = dalloc(h->stream, &h->d_dbg, SP * DBG_FLOATS)) return rc;
+    if (const char* e = getenv("OWW_PROF_BLOCK")) { h->prof_block = atoi(e); if (int rc = dalloc(h->stream, &h->d_prof, (size_t)4 * 256)) return rc; }
+    return 0;
+}
+
+// dynamic-LDS limits of the kernels that ask for more than the default
+int set_kernel_lds(oww_ctx* h) {
+    int rc = 0;
+    auto lds = [&rc](auto kernel, int bytes) { if (!rc) rc = set_lds(kernel, bytes); };
+    for (const auto& g : h->groups) if (g.ht == 4) lds(heads64_kernel, heads_lds_bytes(g.NH));
+    if (!h->rnn_nets.empty()) lds(heads_rnn_kernel<RNN_SPW>, (int)rnn_lds_bytes(RNN_TMAX));
+    if (h->vad) lds(owv::vad_front_kernel, owv::V_LDS_BYTES);
+    lds(owf::hmelA_kernel<false>, owf::FA_LDS_BYTES); lds(owf::hmelA_kernel<true>, owf::FA_LDS_BYTES);
+    lds(stageA_kernel<true>, CfgA::LDS_BYTES); lds(stageA_kernel<false>, CfgA::LDS_BYTES);
+    lds(stage_kernel<CfgB, true, false>, CfgB::LDS_BYTES); lds(stage_kernel<CfgB, false, false>, CfgB::LDS_BYTES);
+    lds(stage_kernel<CfgC, true, false>, CfgC::LDS_BYTES); lds(stage_kernel<CfgC, false, false>, CfgC::LDS_BYTES);
+    lds(stage_kernel<CfgD, true, false>, CfgD::LDS_BYTES); lds(stage_kernel<CfgD, false, false>, CfgD::LDS_BYTES);
+    lds(stage_kernel<CfgE, true, true>, CfgE::LDS_BYTES); lds(stage_kernel<CfgE, false, true>, CfgE::LDS_BYTES);
+    return rc;
+}
+
+// reset state = what an all-ones mel history leaves behind (utils.py:165 melspectrogram_buffer = ones((76,32))): run the incremental
+// CNN on ones rows until the zero start is flushed out, keep the result as the reset template, reset every stream
+int derive_reset_state(oww_ctx* h, const HxCalib& cal, CommitClock& clk) {
+    const size_t SP = h->Spad;
+    const int warm = std::min<int>(32, (int)SP);
+    hipLaunchKernelGGL(fill_kernel, dim3((warm * 256 + 255) / 256), dim3(256), 0, h->stream, h->d_mel, (size_t)warm * 256, 1.0f);
+    const StepArgs args{};                             // (no per-layer dumps)
+    for (int it = 0; it < 12; ++it)
+        if (int rc = run_cnn(h, args, warm, 256, 0)) return rc;
+    for (int a = 0; a < N_STATE; ++a)
+        HIPCHK(copy_async(h->d_tmpl[a], h->d_state[a], (size_t)h->state_len[a] * (h->rr ? kStateSpgRr[a] : 1) * sizeof(float),
+                              hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_mel, 0, SP * 8 * h->kmax * 32 * sizeof(float), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_emb, 0, SP * 96 * sizeof(float), h->stream));
+    if (int rc = do_reset(h, nullptr, (int)SP, nullptr)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    clk.lap("warm-up + reset");
+    // the warm-up already drove the network with an all-ones mel history: weights that overflow the f16 range there are refused now
+    if (int rc = range_check(h, "oww_commit")) return rc;
+    // f16-split family: replay the calibration probes and hold the result to the exact-fp32 run (refuses weights the split loses)
+    if (h->hx && !getenv("OWW_NO_COMMIT_SELFTEST")) {
+        if (int rc = selftest_hx(h, cal)) return rc;
+        HIPCHK(hipMemsetAsync(h->d_mel, 0, SP * 8 * h->kmax * 32 * sizeof(float), h->stream));
+        HIPCHK(hipMemsetAsync(h->d_emb, 0, SP * 96 * sizeof(float), h->stream));
+        HIPCHK(hipMemsetAsync(h->d_raw, 0, SP * std::max(h->NL, 1) * sizeof(float), h->stream));
+        if (int rc = do_reset(h, nullptr, (int)SP, nullptr)) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        clk.lap("self-test replay + reset");
+    }
+    return 0;
+}
+
+// head bank (oww_bank_configure): subscription table, per-slot outputs, the head table; no head yet
+int alloc_bank(oww_ctx* h) {
+    const size_t SK = (size_t)h->S * h->bank_K;
+    if (int rc = dalloc(h->stream, &h->d_bank_sub, SK, false)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_bank_idx, SK)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_bank_raw, SK)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_bank_scores, SK)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_bank_ring, SK * OWW_SCORE_RING)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_bank_npred, SK)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_bank_entries, SK)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_bank_heads, (size_t)h->bank_cap)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_bank_pat, (size_t)h->bank_cap)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_bank_thr, (size_t)h->bank_cap, false)) return rc;
+    h->bank.assign(h->bank_cap, oww_ctx::BankHead{});
+    h->bank_sub.assign(SK, -1);
+    std::vector<float> nanv(h->bank_cap, NAN);
+    HIPCHK(copy_async(h->d_bank_sub, h->bank_sub.data(), SK * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(copy_async(h->d_bank_thr, nanv.data(), nanv.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 }  // namespace
@@ -1734,17 +2252,6 @@ int oww_add_head(oww_ctx* h, const void* blob, size_t nbytes) {
     OWW_GUARD_END
 }
 
-namespace {
-// blob of oww_load_vad (floats after the 8-int header): gain, hann[256], 4 x (w[3][cin][cout], b[cout]), 2 x (w[128][256], b[256]), wd[64], bd
-const int kVadEnc[4][2] = {{128, 16}, {16, 32}, {32, 32}, {32, 64}};
-size_t vad_blob_floats() {
-    size_t n = 1 + 256;
-    for (auto& e : kVadEnc) n += (size_t)3 * e[0] * e[1] + e[1];
-    n += 2 * ((size_t)128 * 256 + 256) + 64 + 1;
-    return n;
-}
-}  // namespace
-
 int oww_load_vad(oww_ctx* h, const void* blob, size_t nbytes) {
     OWW_GUARD_BEGIN
     if (!h || !blob) return fail(OWW_EINVAL, "oww_load_vad: null argument");
@@ -1798,49 +2305,7 @@ int oww_commit(oww_ctx* h) {
     if (h->committed) return fail(OWW_ESTATE, "already committed");
     if (h->mel_blob.empty() || h->emb_blob.empty()) return fail(OWW_ESTATE, "mel and embedding weights must be loaded before commit");
     HIPCHK(hipSetDevice(h->cfg.device));
-
-    // ---- nets ----
-    h->nets.clear(); h->head_nets.clear();
-    int col = 0, maxT = 16, hmax = 1;
-    for (size_t hi = 0; hi < h->heads.size(); ++hi) {
-        HeadHost& hh = h->heads[hi];
-        hh.out_col = col;
-        const size_t in = (size_t)hh.T * 96, H = hh.hidden, O = hh.n_out;
-        const float* q = hh.blob.data();
-        const int begin = (int)h->nets.size();
-        if (hh.kind == 3) {                                                  // recurrent head: one net, its blob as a whole
-            NetHost n{};
-            n.hidden = hh.hidden; n.n_out = hh.n_out; n.has_ln = 0; n.T = hh.T; n.final_act = hh.n_out == 1 ? 0 : 1;
-            n.head = (int)hi; n.role = 0; n.out_col = col; n.n_blocks = 0;
-            n.rnn = q; n.rnn_floats = hh.blob.size();
-            h->nets.push_back(n);
-        }
-        for (int r = 0; r < (hh.kind == 3 ? 0 : hh.kind == 1 ? 2 : 1); ++r) {
-            NetHost n{};
-            n.hidden = hh.hidden; n.n_out = hh.n_out; n.has_ln = hh.has_ln; n.T = hh.T;
-            n.final_act = hh.kind == 2 ? 1 : 0; n.head = (int)hi; n.role = r; n.out_col = col;
-            n.n_blocks = hh.n_blocks;
-            n.w1 = q; q += in * H; n.b1 = q; q += H;
-            if (hh.has_ln) { n.ln1g = q; q += H; n.ln1b = q; q += H; }
-            n.blocks = q;
-            if (hh.n_blocks > 0) {                                           // (block 0 by name: what the MFMA head kernels read)
-                n.w2 = q; n.b2 = q + H * H;
-                if (hh.has_ln) { n.ln2g = n.b2 + H; n.ln2b = n.ln2g + H; }
-            }
-            q += (size_t)hh.n_blocks * (H * H + H + (hh.has_ln ? 2 * H : 0));
-            n.w3 = q; q += H * O; n.b3 = q; q += O;
-            h->nets.push_back(n);
-        }
-        h->head_nets.push_back({begin, (int)h->nets.size()});
-        col += hh.n_out;
-        maxT = std::max(maxT, hh.T);
-        hmax = std::max(hmax, hh.hidden);
-    }
-    h->NL = col;
-    if (h->NL > OWW_MAX_LABELS) return fail(OWW_EINVAL, "too many labels (%d)", h->NL);
-    h->TR = h->cfg.feature_ring > 0 ? std::max(h->cfg.feature_ring, maxT) : maxT;
-    h->generic_hmax = hmax;
-
+    if (int rc = build_nets(h)) return rc;
     // ---- f16-split family: per-layer activation scales from a calibration run on the exact-fp32 kernels (calibrate_hx) ----
     CommitClock clk(h->hx ? "f16-split" : "family");
     HxCalib cal;
@@ -1850,465 +2315,30 @@ int oww_commit(oww_ctx* h) {
         if (getenv("OWW_DEBUG_CALIB"))
             for (int l = 0; l < 20; ++l) fprintf(stderr, "calib layer %2d: max|a| %-12.5g e_in %4d e_out %4d\n", l, h->hx_absmax[l], h->hx_ein[l], h->hx_e[l]);
     }
-
-    // ---- device weight image ----
+    // ---- device weight image: pack, upload ----
     HostBuf hb;
-    const size_t o_hann = hb.add(h->mel_blob.data(), 400);
-    const size_t o_start = hb.add(h->mel_blob.data() + 400, 32);          // int32 bit patterns
-    const size_t o_taps = hb.add(h->mel_blob.data() + 432, 512);
-    // fused front end: the sparse mel taps read a COMPACT copy of each frame's power row -- one segment per mel bin, [first tap ..
-    // last non-zero tap] -- whose segment starts have pairwise different residues mod 32, so that the 32 lanes of a tap read hit 32
-    // different LDS banks (the plain power row gave three bins per bank for every tap: most of the launch's bank conflicts).  Every
-    // power bin belongs to at most two triangular filters, hence two destinations per bin (mel_dst: lo / hi 16 bits; kMelJunk = none).
-    size_t o_meloff = 0, o_meldst = 0;
-    {
-        constexpr int kMelTable = 250, kMelJunk = 250;           // floats of a frame's table; bins without a second filter store here
-        const int32_t* start = reinterpret_cast<const int32_t*>(h->mel_blob.data() + 400);
-        const float* taps = h->mel_blob.data() + 432;
-        int nz[32], first[32];
-        for (int m = 0; m < 32; ++m) {
-            nz[m] = 0;
-            for (int t = 0; t < 16; ++t) if (taps[m * 16 + t] != 0.f) nz[m] = t + 1;
-            first[m] = start[m] - 2;                              // power-row index of tap 0 (the kernels keep FFT bins 2..121)
-        }
-        int off[32], best[32], best_end = 1 << 30;
-        uint64_t st = 0x9E3779B97F4A7C15ull;
-        for (int it = 0; it < 20000 && best_end > kMelTable; ++it) {                // randomised first-fit; a few hundred tries are enough
-            int order[32];
-            for (int i = 0; i < 32; ++i) order[i] = i;
-            for (int i = 31; i > 0; --i) { st ^= st << 13; st ^= st >> 7; st ^= st << 17; std::swap(order[i], order[st % (uint64_t)(i + 1)]); }
-            unsigned used = 0; int cur = 0, end = 0;
-            for (int i = 0; i < 32; ++i) {
-                const int m = order[i];
-                int o = cur;
-                while (used >> (o & 31) & 1u) ++o;
-                used |= 1u << (o & 31); off[m] = o; cur = o + nz[m];
-                end = std::max(end, o + 16);                      // a lane reads 16 taps from its start
-            }
-            if (end < best_end) { best_end = end; memcpy(best, off, sizeof off); }
-        }
-        if (best_end > kMelTable) {                               // (cannot happen for a 32-filter bank of <= 16 taps; plain prefix layout)
-            int cur = 0;
-            for (int m = 0; m < 32; ++m) { best[m] = cur; cur += nz[m]; }
-            if (cur + 16 > kMelTable) return fail(OWW_EINVAL, "oww_commit: the mel filter bank has more than %d taps", kMelTable - 16);
-        }
-        std::vector<float> dst(128, 0.f);
-        for (int i = 0; i < 120; ++i) {
-            uint32_t d[2] = {kMelJunk, kMelJunk}; int n = 0;
-            for (int m = 0; m < 32; ++m) {
-                const int t = i - first[m];
-                if (t >= 0 && t < nz[m] && taps[m * 16 + t] != 0.f) {
-                    if (n == 2) return fail(OWW_EINVAL, "oww_commit: FFT bin %d feeds more than two mel filters (not a triangular filter bank)", i + 2);
-                    d[n++] = (uint32_t)(best[m] + t);
-                }
-            }
-            const uint32_t packed = d[0] | (d[1] << 16);
-            memcpy(&dst[i], &packed, 4);
-        }
-        std::vector<float> offf(32);
-        for (int m = 0; m < 32; ++m) { const int32_t v = best[m]; memcpy(&offf[m], &v, 4); }
-        o_meloff = hb.add(offf.data(), 32);
-        o_meldst = hb.add(dst.data(), 128);
-    }
-    size_t o_conv[20], o_scale[20] = {}, o_shift[20] = {};
-    {
-        const float* q = h->emb_blob.data();
-        std::vector<float> pk;
-        for (int l = 0; l < 20; ++l) {
-            const LayerDef& L = kLayers[l];
-            const size_t nw = (size_t)L.kh * L.kw * L.cin * L.cout;
-            const float* bn_scale = l < 19 ? q + nw : nullptr;             // folded inference BatchNorm of this layer (blob order: w, scale, shift)
-            if (!h->mfma) o_conv[l] = hb.add(q, nw);
-            else if (h->hx) {
-                // fold_cnn: W' = s w 2^(e_out - e_in) per output channel (calibrate_hx's scale ladder; e_in = 0 for the mel input)
-                std::vector<double> colmul(L.cout);
-                const int de = h->hx_e[l] - h->hx_ein[l];
-                for (int c = 0; c < L.cout; ++c) colmul[c] = std::ldexp(bn_scale ? (double)bn_scale[c] : 1.0, de);
-                HxFold fold; fold.colmul = colmul.data();
-                const bool time_merged = OWH_KMERGE && L.kh == 3 && L.kw == 1 && ((L.cin + 15) / 16) % 2 == 1 &&
-                                         (L.cin % 16 == 8 || OWH_KMERGE_B);                     // stage C (and B): layers b, d
-                // 1x3 layers with a 72-channel input (stage C layer c, stage D layer a): owh::conv_mel_hxm, same packing rule
-                const bool mel_merged = OWH_KMERGE_MEL && owh::kInterleave && L.kh == 1 && L.kw == 3 &&
-                                        ((L.cin + 15) / 16) % 2 == 1 && (L.cin + 15) / 16 >= 3 &&
-                                        (L.cin % 16 == 8 || (OWH_KMERGE_MEL2 && l == 7 && OWH_WPS_C == 2) ||   // (l == 7: stage C layer a, 48 -> 72)
-                                         (OWH_KMERGE_MEL2B && l == 5));                                   // (l == 5: stage B layer c, A/B switch)
-                if (l == 0) pack_hx_conv0(q, pk, &fold);
-                else if (l <= 2) pack_hx_stage_a(q, l, pk, &fold);
-                else if (time_merged || mel_merged) pack_hx_tm(q, L.cin, L.cout, pk, &fold);
-                else pack_hx(q, 3, L.cin, L.cout, pk, &fold, OWH_REM2 && !OWH_KMERGE_B && !OWH_KMERGE_MEL2B && l >= 4 && l <= 6);     // (stage B layers b, c, d)
-                if (!(fold.absmax < 65000.0))
-                    return fail(OWW_ERANGE, "conv layer %d: folded weight magnitude %.3g (BatchNorm scale x weight x activation-scale ratio 2^%d) is outside "
-                                "the f16 range of the fp16-split kernels (use_mfma = 3); use use_mfma = 1", l, fold.absmax, de);
-                o_conv[l] = hb.add(pk);
-            }
-            else if (h->rr && l > 0) { pack_rr(q, 3, L.cin, L.cout, pk); o_conv[l] = hb.add(pk); }
-            else if (l == 0) {
-                // conv0: K = 9 taps padded to 12 -> three k-steps; lane (i, j) of k-step s holds w[k = 4s+j][cout = 16ct+i]
-                pk.assign(2 * 3 * 64, 0.f);
-                for (int ct = 0; ct < 2; ++ct)
-                    for (int s = 0; s < 3; ++s)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int k = 4 * s + (lane >> 4), co = ct * 16 + (lane & 15);
-                            if (k < 9 && co < 24) pk[(ct * 3 + s) * 64 + lane] = q[k * 24 + co];
-                        }
-                o_conv[l] = hb.add(pk);
-            } else { pack_mfma(q, 3, L.cin, L.cout, pk); o_conv[l] = hb.add(pk); }
-            q += nw;
-            if (l < 19) {
-                // zero padded to whole 16-channel tiles: the register-resident kernels evaluate the pad channels (as zeros)
-                std::vector<float> pad((size_t)(L.cout + 15) / 16 * 16, 0.f);
-                if (h->hx) {
-                    // f16-split family: the scale lives in the weights.  Slot "scale" is only read by conv0: the third operand of the
-                    // med3 that applies its ReLU in the folded form (+inf where the BatchNorm scale is >= 0, -inf where it is negative)
-                    std::vector<float> bound(L.cout);
-                    for (int c = 0; c < L.cout; ++c) bound[c] = q[c] < 0.f ? -INFINITY : INFINITY;
-                    pad_hx_rows(bound.data(), L.cout, 1.0f, pad);
-                }
-                else memcpy(pad.data(), q, L.cout * sizeof(float));
-                o_scale[l] = hb.add(pad); q += L.cout;
-                std::fill(pad.begin(), pad.end(), 0.f);
-                if (h->hx) pad_hx_rows(q, L.cout, std::ldexp(1.0f, h->hx_e[l]), pad);       // accumulator start values K h, tile row order
-                else memcpy(pad.data(), q, L.cout * sizeof(float));
-                o_shift[l] = hb.add(pad); q += L.cout;
-            }
-        }
-    }
-    // heads: natural arrays for every net (+ packed w2 for hidden==64), fast groups
-    struct NetOff { size_t w1, b1, ln1g, ln1b, w2, b2, ln2g, ln2b, w3, b3, w2pk, blocks, rnn; };
-    std::vector<NetOff> noff(h->nets.size());
-    for (size_t ni = 0; ni < h->nets.size(); ++ni) {
-        const NetHost& n = h->nets[ni];
-        if (n.rnn) { noff[ni] = NetOff{}; noff[ni].rnn = hb.add(n.rnn, n.rnn_floats); continue; }
-        const size_t in = (size_t)n.T * 96, H = n.hidden, O = n.n_out;
-        NetOff& o = noff[ni];
-        o.w1 = hb.add(n.w1, in * H); o.b1 = hb.add(n.b1, H);
-        o.ln1g = n.has_ln ? hb.add(n.ln1g, H) : 0; o.ln1b = n.has_ln ? hb.add(n.ln1b, H) : 0;
-        const size_t blk = H * H + H + (n.has_ln ? 2 * H : 0);
-        o.blocks = n.n_blocks > 0 ? hb.add(n.blocks, (size_t)n.n_blocks * blk) : 0;      // (the generic kernel walks them in place)
-        o.w2 = o.b2 = o.ln2g = o.ln2b = 0;
-        if (n.n_blocks > 0) {
-            o.w2 = hb.add(n.w2, H * H); o.b2 = hb.add(n.b2, H);
-            o.ln2g = n.has_ln ? hb.add(n.ln2g, H) : 0; o.ln2b = n.has_ln ? hb.add(n.ln2b, H) : 0;
-        }
-        o.w3 = hb.add(n.w3, H * O); o.b3 = hb.add(n.b3, O);
-        o.w2pk = 0;
-        if (n.hidden == 64 && n.n_blocks == 1) { std::vector<float> pk; pack_mfma(n.w2, 1, 64, 64, pk); o.w2pk = hb.add(pk); }
-    }
-    // grouping: heads whose nets are all (hidden 64, n_out 1, sigmoid) share a fast group per T (<= 8 nets each)
-    h->groups.clear(); h->generic_nets.clear(); h->rnn_nets.clear();
-    struct GOff { size_t w1pk, b1cat, w1hx; std::vector<size_t> w2hx, pad, w3hx; };
-    std::vector<GOff> goff;
-    for (size_t hi = 0; hi < h->heads.size(); ++hi) {
-        const auto [nb, ne] = h->head_nets[hi];
-        if (h->nets[nb].rnn) { h->rnn_nets.push_back(nb); continue; }       // recurrent heads have their own kernel in every family
-        bool fast = h->mfma;
-        // the MFMA head kernels: sigmoid nets of one output and one hidden block; exactly 64 hidden units in the fp32 family
-        // (heads64_kernel), up to 64 in the fp16-split family (zero-padded, see FastGroup::d_pad)
-        for (int ni = nb; ni < ne; ++ni)
-            fast = fast && (h->nets[ni].hidden == 64 || (h->hx && h->nets[ni].hidden <= 64)) && h->nets[ni].n_out == 1 &&
-                   h->nets[ni].final_act == 0 && h->nets[ni].n_blocks == 1;
-        // the wide form of the fp16-split heads kernel: ungated nets of up to 128 hidden units and 8 outputs with one hidden block
-        // (the released multiclass `timer`: docs/models/timers.md:9-27; train.py's default layer_dim = 128)
-        bool wide = !fast && h->hx && h->mfma && ne - nb == 1 && !getenv("OWW_NO_WIDE_HEADS");
-        for (int ni = nb; ni < ne; ++ni) wide = wide && h->nets[ni].hidden <= 128 && h->nets[ni].n_out <= 8 && h->nets[ni].n_blocks == 1 && h->nets[ni].role == 0;
-        if (!fast && !wide) { for (int ni = nb; ni < ne; ++ni) h->generic_nets.push_back(ni); continue; }
-        FastGroup* g = nullptr;
-        const int ht = wide ? 8 : 4;
-        const int cap = h->hx ? 16 / ht : HD_MAXNETS;                // heads_hx_kernel: at most sixteen hidden tiles per launch
-        for (auto& gg : h->groups) if (gg.T == h->nets[nb].T && gg.ht == ht && gg.n_nets + (ne - nb) <= cap) { g = &gg; break; }
-        if (!g) { h->groups.push_back(FastGroup{}); g = &h->groups.back(); g->T = h->nets[nb].T; g->n_nets = 0; g->ht = ht; }
-        for (int ni = nb; ni < ne; ++ni) { g->nets.push_back(ni); g->n_nets++; }
-    }
-    for (auto& g : h->groups) {
-        if (g.ht == 8) {
-            // ---- wide group: hidden columns padded to 128 per net
-            const int HP = 128;
-            g.NH = HP * g.n_nets;
-            const size_t K = (size_t)g.T * 96;
-            std::vector<float> wcat(K * g.NH, 0.f), pk;
-            std::vector<double> colmul(g.NH);
-            GOff go{0, 0, 0, {}, {}, {}};
-            for (int gi = 0; gi < g.n_nets; ++gi) {
-                NetHost& n = h->nets[g.nets[gi]];
-                const size_t H = n.hidden, O = n.n_out;
-                for (size_t k = 0; k < K; ++k) memcpy(&wcat[k * g.NH + HP * gi], n.w1 + k * H, H * sizeof(float));
-                n.hx_e1 = hx_weight_exp(n.w1, K * H); n.hx_e2 = hx_weight_exp(n.w2, H * H); n.hx_e3 = hx_weight_exp(n.w3, H * O);
-                if (n.hx_e1 == -1000 || n.hx_e2 == -1000 || n.hx_e3 == -1000) return fail(OWW_EINVAL, "head weights are not finite");
-                for (int c = 0; c < HP; ++c) colmul[HP * gi + c] = std::ldexp(1.0, n.hx_e1);
-            }
-            pack_hx_w1(wcat.data(), (int)K, g.NH, colmul.data(), pk);
-            go.w1hx = hb.add(pk);
-            for (int gi = 0; gi < g.n_nets; ++gi) {
-                const NetHost& n = h->nets[g.nets[gi]];
-                const size_t H = n.hidden, O = n.n_out;
-                std::vector<double> cm2(HP, std::ldexp(1.0, n.hx_e2)), cm3(16, std::ldexp(1.0, n.hx_e3));
-                HxFold f2; f2.colmul = cm2.data();
-                std::vector<float> w2p((size_t)HP * HP, 0.f);            // [in 128][out 128], zero rows / columns beyond H
-                for (size_t i = 0; i < H; ++i) memcpy(&w2p[i * HP], n.w2 + i * H, H * sizeof(float));
-                pack_hx(w2p.data(), 1, HP, HP, pk, &f2); go.w2hx.push_back(hb.add(pk));
-                HxFold f3; f3.colmul = cm3.data();
-                std::vector<float> w3p((size_t)HP * 16, 0.f);            // [in 128][out 16], outputs O .. 15 zero
-                for (size_t i = 0; i < H; ++i) memcpy(&w3p[i * 16], n.w3 + i * O, O * sizeof(float));
-                pack_hx(w3p.data(), 1, HP, 16, pk, &f3); go.w3hx.push_back(hb.add(pk));
-                std::vector<float> pad(6 * HP + 16, 0.f);                // b1, ln1g, ln1b, b2, ln2g, ln2b | b3
-                const float* src[6] = {n.b1, n.has_ln ? n.ln1g : nullptr, n.has_ln ? n.ln1b : nullptr, n.b2,
-                                       n.has_ln ? n.ln2g : nullptr, n.has_ln ? n.ln2b : nullptr};
-                for (int a = 0; a < 6; ++a) if (src[a]) memcpy(&pad[a * HP], src[a], H * sizeof(float));
-                memcpy(&pad[6 * HP], n.b3, O * sizeof(float));
-                go.pad.push_back(hb.add(pad));
-            }
-            goff.push_back(go);
-            continue;
-        }
-        g.NH = 64 * g.n_nets;
-        const size_t K = (size_t)g.T * 96;
-        std::vector<float> wcat(K * g.NH, 0.f), bcat(g.NH, 0.f), pk;
-        for (int gi = 0; gi < g.n_nets; ++gi) {
-            const NetHost& n = h->nets[g.nets[gi]];
-            const size_t H = n.hidden;                                   // (<= 64; columns H .. 63 of the net's block stay zero)
-            for (size_t k = 0; k < K; ++k) memcpy(&wcat[k * g.NH + 64 * gi], n.w1 + k * H, H * sizeof(float));
-            memcpy(&bcat[64 * gi], n.b1, H * sizeof(float));
-        }
-        pack_mfma(wcat.data(), g.T, 96, g.NH, pk);
-        GOff go{hb.add(pk), hb.add(bcat), 0, {}, {}, {}};
-        if (h->hx) {
-            // every net's two matrices on their own power-of-two scale (hx_weight_exp); undone on the fp32 accumulators (HeadHxNet::u1, u2)
-            std::vector<double> colmul(g.NH);
-            for (int gi = 0; gi < g.n_nets; ++gi) {
-                NetHost& n = h->nets[g.nets[gi]];
-                const size_t H = n.hidden;
-                n.hx_e1 = hx_weight_exp(n.w1, K * H); n.hx_e2 = hx_weight_exp(n.w2, H * H);
-                if (n.hx_e1 == -1000 || n.hx_e2 == -1000) return fail(OWW_EINVAL, "head weights are not finite");
-                for (int c = 0; c < 64; ++c) colmul[64 * gi + c] = std::ldexp(1.0, n.hx_e1);
-            }
-            pack_hx_w1(wcat.data(), (int)K, g.NH, colmul.data(), pk);
-            go.w1hx = hb.add(pk);
-            for (int gi = 0; gi < g.n_nets; ++gi) {
-                const NetHost& n = h->nets[g.nets[gi]];
-                const size_t H = n.hidden;
-                std::vector<double> cm2(64, std::ldexp(1.0, n.hx_e2));
-                HxFold fold; fold.colmul = cm2.data();
-                std::vector<float> w2p(64 * 64, 0.f);                    // [in 64][out 64], zero rows / columns beyond H
-                for (size_t i = 0; i < H; ++i) memcpy(&w2p[i * 64], n.w2 + i * H, H * sizeof(float));
-                pack_hx(w2p.data(), 1, 64, 64, pk, &fold); go.w2hx.push_back(hb.add(pk));
-                std::vector<float> pad(7 * 64, 0.f);                     // b1, ln1g, ln1b, b2, ln2g, ln2b, w3
-                const float* src[7] = {n.b1, n.has_ln ? n.ln1g : nullptr, n.has_ln ? n.ln1b : nullptr, n.b2,
-                                       n.has_ln ? n.ln2g : nullptr, n.has_ln ? n.ln2b : nullptr, n.w3};
-                for (int a = 0; a < 7; ++a) if (src[a]) memcpy(&pad[a * 64], src[a], H * sizeof(float));
-                go.pad.push_back(hb.add(pad));
-            }
-        }
-        goff.push_back(go);
-    }
-    // voice-activity stand-in (always fp16-split MFMA kernels, whatever the CNN family)
-    size_t o_vhann = 0, o_vencw = 0, o_vencb = 0, o_vlw = 0, o_vlb = 0, o_vwd = 0;
-    h->vad = !h->vad_blob.empty();
-    if (h->vad) {
-        const float* q = h->vad_blob.data();
-        h->vad_gain = *q++;
-        o_vhann = hb.add(q, 256); q += 256;
-        std::vector<float> encw, encb(4 * 64, 0.f), pk;
-        for (int l = 0; l < 4; ++l) {
-            const int cin = kVadEnc[l][0], cout = kVadEnc[l][1];
-            if (!hx_in_range(q, (size_t)3 * cin * cout)) return fail(OWW_EINVAL, "VAD encoder weights too large for the fp16-split kernels");
-            pack_hx(q, 3, cin, cout, pk);
-            encw.insert(encw.end(), pk.begin(), pk.end());
-            q += (size_t)3 * cin * cout;
-            memcpy(&encb[l * 64], q, cout * sizeof(float)); q += cout;
-        }
-        if (encw.size() != (size_t)owv::V_WFLOATS) return fail(OWW_EINVAL, "internal: VAD encoder image is %zu floats, expected %d", encw.size(), owv::V_WFLOATS);
-        o_vencw = hb.add(encw); o_vencb = hb.add(encb);
-        std::vector<float> lw, lb;
-        for (int l = 0; l < 2; ++l) {
-            if (!hx_in_range(q, (size_t)128 * 256)) return fail(OWW_EINVAL, "VAD LSTM weights too large for the fp16-split kernels");
-            // columns regrouped so that the four gates of hidden tile u are neighbours: column 16 (4u + gate) + i <- gate * 64 + 16u + i
-            std::vector<float> perm((size_t)128 * 256);
-            for (int k = 0; k < 128; ++k)
-                for (int u = 0; u < 4; ++u)
-                    for (int gt = 0; gt < 4; ++gt)
-                        for (int i = 0; i < 16; ++i) perm[(size_t)k * 256 + 16 * (4 * u + gt) + i] = q[(size_t)k * 256 + gt * 64 + 16 * u + i];
-            pack_hx(perm.data(), 1, 128, 256, pk);
-            lw.insert(lw.end(), pk.begin(), pk.end());
-            q += (size_t)128 * 256;
-            lb.insert(lb.end(), q, q + 256); q += 256;
-        }
-        o_vlw = hb.add(lw); o_vlb = hb.add(lb);
-        o_vwd = hb.add(q, 64); q += 64;
-        h->vad_bd = *q;
-    }
+    WeightOff off;
+    if (int rc = pack_mel_tables(h, hb, off)) return rc;
+    if (int rc = pack_cnn(h, hb, off)) return rc;
+    if (int rc = pack_head_nets(h, hb, off)) return rc;
+    if (int rc = pack_vad(h, hb, off)) return rc;
     clk.lap("weight packing (host)");
-    HIPCHK(dev_alloc(&h->d_w, hb.data.size() * sizeof(float)));
-    HIPCHK(copy_sync(h->d_w, hb.data.data(), hb.data.size() * sizeof(float), hipMemcpyHostToDevice));
-    h->d_hann = h->d_w + o_hann; h->d_mstart = reinterpret_cast<const int*>(h->d_w + o_start); h->d_taps = h->d_w + o_taps;
-    h->d_meloff = reinterpret_cast<const int*>(h->d_w + o_meloff); h->d_meldst = reinterpret_cast<const unsigned*>(h->d_w + o_meldst);
-    if (h->vad) {
-        h->d_vad_hann = h->d_w + o_vhann; h->d_vad_encw = h->d_w + o_vencw; h->d_vad_encb = h->d_w + o_vencb;
-        h->d_vad_lstmw = h->d_w + o_vlw; h->d_vad_lstmb = h->d_w + o_vlb; h->d_vad_wd = h->d_w + o_vwd;
-    }
-    for (int l = 0; l < 20; ++l) {
-        h->d_conv[l] = h->d_w + o_conv[l];
-        h->d_scale[l] = l < 19 ? h->d_w + o_scale[l] : nullptr;
-        h->d_shift[l] = l < 19 ? h->d_w + o_shift[l] : nullptr;
-    }
-    auto make_desc = [&](int ni, int hid_off) {
-        const NetHost& n = h->nets[ni];
-        const NetOff& o = noff[ni];
-        NetDesc d{};
-        d.hidden = n.hidden; d.n_out = n.n_out; d.has_ln = n.has_ln; d.final_act = n.final_act; d.T = n.T;
-        d.head = n.head; d.role = n.role; d.out_col = n.out_col; d.hid_off = hid_off;
-        if (n.rnn) { d.rnn = h->d_w + o.rnn; return d; }
-        d.w1 = h->d_w + o.w1; d.b1 = h->d_w + o.b1;
-        d.ln1g = n.has_ln ? h->d_w + o.ln1g : nullptr; d.ln1b = n.has_ln ? h->d_w + o.ln1b : nullptr;
-        d.n_blocks = n.n_blocks;
-        d.blocks = n.n_blocks > 0 ? h->d_w + o.blocks : nullptr;
-        d.w2 = n.n_blocks > 0 ? h->d_w + o.w2 : nullptr; d.b2 = n.n_blocks > 0 ? h->d_w + o.b2 : nullptr;
-        d.ln2g = n.has_ln && n.n_blocks > 0 ? h->d_w + o.ln2g : nullptr; d.ln2b = n.has_ln && n.n_blocks > 0 ? h->d_w + o.ln2b : nullptr;
-        d.w3 = h->d_w + o.w3; d.b3 = h->d_w + o.b3;
-        d.w2pk = n.hidden == 64 && n.n_blocks == 1 ? h->d_w + o.w2pk : nullptr;
-        return d;
-    };
-    if (!h->nets.empty()) {
-        std::vector<NetDesc> all;
-        for (size_t ni = 0; ni < h->nets.size(); ++ni) all.push_back(make_desc((int)ni, 0));
-        h->host_descs = all;
-        HIPCHK(dev_alloc(&h->d_allnets, all.size() * sizeof(NetDesc)));
-        HIPCHK(copy_sync(h->d_allnets, all.data(), all.size() * sizeof(NetDesc), hipMemcpyHostToDevice));
-    }
-    for (size_t gi = 0; gi < h->groups.size(); ++gi) {
-        FastGroup& g = h->groups[gi];
-        std::vector<NetDesc> ds;
-        for (int i = 0; i < g.n_nets; ++i) ds.push_back(make_desc(g.nets[i], 64 * i));
-        HIPCHK(dev_alloc(&g.d_nets, ds.size() * sizeof(NetDesc)));
-        HIPCHK(copy_sync(g.d_nets, ds.data(), ds.size() * sizeof(NetDesc), hipMemcpyHostToDevice));
-        g.d_w1pk = h->d_w + goff[gi].w1pk; g.d_b1cat = h->d_w + goff[gi].b1cat;
-        if (h->hx) {
-            g.d_w1hx = h->d_w + goff[gi].w1hx;
-            for (size_t o : goff[gi].w2hx) g.d_w2hx.push_back(h->d_w + o);
-            for (size_t o : goff[gi].pad) g.d_pad.push_back(h->d_w + o);
-            for (size_t o : goff[gi].w3hx) g.d_w3hx.push_back(h->d_w + o);
-        }
-        if (g.ht == 4) if (int rc = set_lds(heads64_kernel, heads_lds_bytes(g.NH))) return rc;
-    }
-    if (!h->rnn_nets.empty()) if (int rc = set_lds(heads_rnn_kernel<RNN_SPW>, (int)rnn_lds_bytes(RNN_TMAX))) return rc;
-
-    // ---- sticky range flag of the f16-split kernels: page-locked + device-mapped, so the host reads it without a copy ----
-    {
-        void* dp = nullptr;
-        HIPCHK(hipHostMalloc((void**)&h->h_range, 64, hipHostMallocMapped));
-        h->h_range[0] = 0; h->h_range[1] = -1;
-        HIPCHK(hipHostGetDevicePointer(&dp, h->h_range, 0));
-        h->d_range = (int*)dp;
-    }
+    if (int rc = bind_weights(h, hb, off)) return rc;
+    if (int rc = alloc_range_flag(h)) return rc;
     clk.lap("weight upload");
     // ---- state ----
-    const size_t SP = h->Spad;
-    for (int a = 0; a < N_STATE; ++a) {
-        if (int rc = dalloc(h->stream, &h->d_state[a], SP * h->state_len[a])) return rc;
-        if (int rc = dalloc(h->stream, &h->d_tmpl[a], (size_t)h->state_len[a] * (h->rr ? kStateSpgRr[a] : 1))) return rc;
-    }
-    const int* xlen = h->rr ? kXLenRr : kXLenLds;
-    if (int rc = dalloc(h->stream, &h->d_xA, SP * xlen[0])) return rc;
-    if (int rc = dalloc(h->stream, &h->d_xB, SP * xlen[1])) return rc;
-    if (int rc = dalloc(h->stream, &h->d_xC, SP * xlen[2])) return rc;
-    if (int rc = dalloc(h->stream, &h->d_xD, SP * xlen[3])) return rc;
-    if (int rc = dalloc(h->stream, &h->d_mel, SP * 8 * h->kmax * 32)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_feat, SP * h->TR * 96)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_emb, SP * 96)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_raw, SP * std::max(h->NL, 1))) return rc;
-    if (int rc = dalloc(h->stream, &h->d_scores, SP * std::max(h->NL, 1))) return rc;
-    if (int rc = dalloc(h->stream, &h->d_ring, SP * std::max(h->NL, 1) * OWW_SCORE_RING)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_featinit, (size_t)h->TR * 96)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_nfeat, SP)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_npred, SP)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_vadring, SP * 8)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_nvad, SP)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_vadin, SP)) return rc;
-    if (h->vad) {
-        const size_t G = (SP + 15) / 16;
-        if (int rc = dalloc(h->stream, &h->d_vadx, G * 4 * 1024)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_vadhc, G * 4096)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_vadlast, SP)) return rc;
-        if (int rc = set_lds(owv::vad_front_kernel, owv::V_LDS_BYTES)) return rc;
-    }
-    if (int rc = dalloc(h->stream, &h->d_tail, SP * 480)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_pcm, (size_t)h->S * OWW_CHUNK * h->kmax)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_patience, (size_t)std::max(h->NL, 1))) return rc;
-    if (int rc = dalloc(h->stream, &h->d_threshold, (size_t)std::max(h->NL, 1))) return rc;
-    {
-        std::vector<float> nanv(std::max(h->NL, 1), NAN);
-        HIPCHK(copy_async(h->d_threshold, nanv.data(), nanv.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));   // (behind the buffer's zero fill, same stream)
-    }
-    if (h->cfg.debug_layers) if (int rc = dalloc(h->stream, &h->d_dbg, SP * DBG_FLOATS)) return rc;
-    if (const char* e = getenv("OWW_PROF_BLOCK")) { h->prof_block = atoi(e); if (int rc = dalloc(h->stream, &h->d_prof, (size_t)4 * 256)) return rc; }
-
-    h->fuse = h->hx && !getenv("OWW_NO_FUSE");
+    if (int rc = alloc_state(h)) return rc;
+    h->fuse = h->hx && !getenv("OWW_NO_FUSE");                            // (A/B switch: OWW_NO_FUSE=1 keeps the separate mel kernel)
     if (const char* e = getenv("OWW_SMALL_WGS")) h->small_wgs = atoi(e);
     if (const char* e = getenv("OWW_SMALL_WGS_HEADS")) h->small_wgs_heads = atoi(e);
     if (const char* e = getenv("OWW_GENERIC_SPW")) { const int v = atoi(e); h->generic_spw = v == 4 || v == 16 ? v : 0; }
-    h->post_in_heads = h->hx && !getenv("OWW_NO_FUSE") && h->groups.size() == 1 && h->groups[0].ht == 4 && h->generic_nets.empty() && h->rnn_nets.empty() && h->NL > 0;                  // (A/B switch: OWW_NO_FUSE=1 keeps the separate mel kernel)
-    if (int rc = set_lds(owf::hmelA_kernel<false>, owf::FA_LDS_BYTES)) return rc;
-    if (int rc = set_lds(owf::hmelA_kernel<true>, owf::FA_LDS_BYTES)) return rc;
-    if (int rc = set_lds(stageA_kernel<true>, CfgA::LDS_BYTES)) return rc;
-    if (int rc = set_lds(stageA_kernel<false>, CfgA::LDS_BYTES)) return rc;
-    if (int rc = set_lds(stage_kernel<CfgB, true, false>, CfgB::LDS_BYTES)) return rc;
-    if (int rc = set_lds(stage_kernel<CfgB, false, false>, CfgB::LDS_BYTES)) return rc;
-    if (int rc = set_lds(stage_kernel<CfgC, true, false>, CfgC::LDS_BYTES)) return rc;
-    if (int rc = set_lds(stage_kernel<CfgC, false, false>, CfgC::LDS_BYTES)) return rc;
-    if (int rc = set_lds(stage_kernel<CfgD, true, false>, CfgD::LDS_BYTES)) return rc;
-    if (int rc = set_lds(stage_kernel<CfgD, false, false>, CfgD::LDS_BYTES)) return rc;
-    if (int rc = set_lds(stage_kernel<CfgE, true, true>, CfgE::LDS_BYTES)) return rc;
-    if (int rc = set_lds(stage_kernel<CfgE, false, true>, CfgE::LDS_BYTES)) return rc;
-
-    // ---- reset state = what an all-ones mel history leaves behind (utils.py:165 melspectrogram_buffer =
-    //      ones((76,32))): run the incremental CNN on ones rows until the zero start is flushed out ----
+    h->post_in_heads = h->fuse && h->groups.size() == 1 && h->groups[0].ht == 4 && h->generic_nets.empty() && h->rnn_nets.empty() && h->NL > 0;
+    if (int rc = set_kernel_lds(h)) return rc;
     clk.lap("state allocation");
-    {
-        const int warm = std::min<int>(32, (int)SP);
-        hipLaunchKernelGGL(fill_kernel, dim3((warm * 256 + 255) / 256), dim3(256), 0, h->stream, h->d_mel, (size_t)warm * 256, 1.0f);
-        const StepArgs a{};                                // (no per-layer dumps)
-        for (int it = 0; it < 12; ++it)
-            if (int rc = run_cnn(h, a, warm, 256, 0)) return rc;
-        for (int a = 0; a < N_STATE; ++a)
-            HIPCHK(copy_async(h->d_tmpl[a], h->d_state[a], (size_t)h->state_len[a] * (h->rr ? kStateSpgRr[a] : 1) * sizeof(float),
-                                  hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemsetAsync(h->d_mel, 0, SP * 8 * h->kmax * 32 * sizeof(float), h->stream));
-        HIPCHK(hipMemsetAsync(h->d_emb, 0, SP * 96 * sizeof(float), h->stream));
-        if (int rc = do_reset(h, nullptr, (int)SP, nullptr)) return rc;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        clk.lap("warm-up + reset");
-        // the warm-up already drove the network with an all-ones mel history: weights that overflow the f16 range there are refused now
-        if (int rc = range_check(h, "oww_commit")) return rc;
-        // f16-split family: replay the calibration probes and hold the result to the exact-fp32 run (refuses weights the split loses)
-        if (h->hx && !getenv("OWW_NO_COMMIT_SELFTEST")) {
-            if (int rc = selftest_hx(h, cal)) return rc;
-            HIPCHK(hipMemsetAsync(h->d_mel, 0, SP * 8 * h->kmax * 32 * sizeof(float), h->stream));
-            HIPCHK(hipMemsetAsync(h->d_emb, 0, SP * 96 * sizeof(float), h->stream));
-            HIPCHK(hipMemsetAsync(h->d_raw, 0, SP * std::max(h->NL, 1) * sizeof(float), h->stream));
-            if (int rc = do_reset(h, nullptr, (int)SP, nullptr)) return rc;
-            HIPCHK(hipStreamSynchronize(h->stream));
-            clk.lap("self-test replay + reset");
-        }
-    }
+    // ---- reset state, then reset all ----
+    if (int rc = derive_reset_state(h, cal, clk)) return rc;
     if (h->hx) { h->probe_emb = cal.ref_emb; h->probe_nb = cal.nb; }      // (oww_bank_add's self-test inputs)
-    if (h->bank_K > 0) {
-        const size_t SK = (size_t)h->S * h->bank_K;
-        if (int rc = dalloc(h->stream, &h->d_bank_sub, SK, false)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_bank_idx, SK)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_bank_raw, SK)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_bank_scores, SK)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_bank_ring, SK * OWW_SCORE_RING)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_bank_npred, SK)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_bank_entries, SK)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_bank_heads, (size_t)h->bank_cap)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_bank_pat, (size_t)h->bank_cap)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_bank_thr, (size_t)h->bank_cap, false)) return rc;
-        h->bank.assign(h->bank_cap, oww_ctx::BankHead{});
-        h->bank_sub.assign(SK, -1);
-        std::vector<float> nanv(h->bank_cap, NAN);
-        HIPCHK(copy_async(h->d_bank_sub, h->bank_sub.data(), SK * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(copy_async(h->d_bank_thr, nanv.data(), nanv.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
+    if (h->bank_K > 0) if (int rc = alloc_bank(h)) return rc;
     h->committed = true;
     return OWW_OK;
     OWW_GUARD_END
@@ -3063,48 +3093,20 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
     for (int b = 0; b < h->bank_cap && id < 0; ++b) if (!h->bank[b].live) id = b;
     if (id < 0) return fail(OWW_EINVAL, "oww_bank_add: the bank is full (capacity %d)", h->bank_cap);
     HIPCHK(hipSetDevice(h->cfg.device));
-    // ---- pack exactly as oww_commit packs a fixed net of the same width (ht 4: <= 64 units, ht 8: <= 128)
-    const float *w1 = q, *b1 = w1 + K * H, *ln1g = has_ln ? b1 + H : nullptr, *ln1b = has_ln ? b1 + 2 * H : nullptr;
-    const float* w2 = b1 + H + (has_ln ? 2 * H : 0);
-    const float *b2 = w2 + (size_t)H * H, *ln2g = has_ln ? b2 + H : nullptr, *ln2b = has_ln ? b2 + 2 * H : nullptr;
-    const float* w3 = b2 + H + (has_ln ? 2 * H : 0);
-    const float* b3 = w3 + H;
+    // ---- the packing of a fixed net of the same width (ht 4: <= 64 units, ht 8: <= 128), in an image of its own: w1hx | pack_hx_net
+    NetHost net{};
+    parse_dense_net(q, T, H, 1, has_ln, 1, net);
     const int ht = H <= 64 ? 4 : 8, HP = 16 * ht;
-    const int e1 = hx_weight_exp(w1, K * H), e2 = hx_weight_exp(w2, (size_t)H * H), e3 = ht == 8 ? hx_weight_exp(w3, (size_t)H) : 0;
-    if (e1 == -1000 || e2 == -1000 || e3 == -1000) return fail(OWW_EINVAL, "oww_bank_add: head weights are not finite");
+    HxNetPack pack;
+    if (!hx_net_scales(net, ht, pack)) return fail(OWW_EINVAL, "oww_bank_add: head weights are not finite");
     HostBuf hb;
     std::vector<float> wcat(K * HP, 0.f), pk;
-    for (size_t k = 0; k < K; ++k) memcpy(&wcat[k * HP], w1 + k * H, H * sizeof(float));
-    std::vector<double> colmul(HP, std::ldexp(1.0, e1));
+    std::vector<double> colmul(HP);
+    place_w1(net, 0, HP, HP, pack.e1, wcat, colmul);
     pack_hx_w1(wcat.data(), (int)K, HP, colmul.data(), pk);
     const size_t o_w1 = hb.add(pk);
     const size_t w1_floats = pk.size();
-    std::vector<double> cm2(HP, std::ldexp(1.0, e2));
-    HxFold f2; f2.colmul = cm2.data();
-    std::vector<float> w2p((size_t)HP * HP, 0.f);
-    for (int i = 0; i < H; ++i) memcpy(&w2p[(size_t)i * HP], w2 + (size_t)i * H, H * sizeof(float));
-    pack_hx(w2p.data(), 1, HP, HP, pk, &f2);
-    const size_t o_w2 = hb.add(pk);
-    size_t o_w3 = 0;
-    std::vector<float> pad;
-    if (ht == 4) {                                       // b1, ln1g, ln1b, b2, ln2g, ln2b, w3 | b3
-        pad.assign(7 * 64 + 4, 0.f);
-        const float* src[7] = {b1, ln1g, ln1b, b2, ln2g, ln2b, w3};
-        for (int a = 0; a < 7; ++a) if (src[a]) memcpy(&pad[a * 64], src[a], H * sizeof(float));
-        pad[7 * 64] = b3[0];
-    } else {                                             // b1, ln1g, ln1b, b2, ln2g, ln2b | b3 padded to 16
-        pad.assign(6 * HP + 16, 0.f);
-        const float* src[6] = {b1, ln1g, ln1b, b2, ln2g, ln2b};
-        for (int a = 0; a < 6; ++a) if (src[a]) memcpy(&pad[a * HP], src[a], H * sizeof(float));
-        pad[6 * HP] = b3[0];
-        std::vector<double> cm3(16, std::ldexp(1.0, e3));
-        HxFold f3; f3.colmul = cm3.data();
-        std::vector<float> w3p((size_t)HP * 16, 0.f);
-        for (int i = 0; i < H; ++i) w3p[(size_t)i * 16] = w3[i];
-        pack_hx(w3p.data(), 1, HP, 16, pk, &f3);
-        o_w3 = hb.add(pk);
-    }
-    const size_t o_pad = hb.add(pad);
+    pack_hx_net(net, ht, true, hb, pack);
     float* d_img = nullptr;
     HIPCHK(dev_alloc(&d_img, hb.data.size() * sizeof(float)));
     if (copy_sync(d_img, hb.data.data(), hb.data.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
@@ -3113,14 +3115,7 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
     }
     owh::BankHeadDev dv{};
     dv.w1hx = d_img + o_w1; dv.T = T; dv.ht = ht;
-    owh::HeadHxNet& o = dv.net;
-    const float* pd = d_img + o_pad;
-    o.w2hx = d_img + o_w2; o.b1 = pd; o.ln1g = pd + HP; o.ln1b = pd + 2 * HP; o.b2 = pd + 3 * HP; o.ln2g = pd + 4 * HP; o.ln2b = pd + 5 * HP;
-    o.has_ln = has_ln; o.role = 0; o.head = 0; o.out_col = 0; o.hidden = H; o.inv_hidden = 1.0f / (float)H;
-    o.u1 = std::ldexp(1.0f, -(h->hx_efeat + e1)); o.u2 = std::ldexp(1.0f, -e2);
-    o.n_out = 1; o.final_act = 0;
-    if (ht == 4) { o.w3 = pd + 6 * HP; o.b3 = pd + 7 * 64; }
-    else { o.w3 = nullptr; o.b3 = pd + 6 * HP; o.w3hx = d_img + o_w3; o.u3 = std::ldexp(1.0f, -e3); }
+    dv.net = make_hx_net(net, ht, pack, d_img, nullptr, h->hx_efeat);
     // ---- self-test: the routed kernel on windows of the commit's probe embeddings against float64, the tolerance oww_commit holds
     //      fixed heads to (1e-3)
     const int NP = 32, CT = 16;
@@ -3166,7 +3161,7 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
     bool finite = true;
     for (int w = 0; w < B && !rc; ++w) {
         finite = finite && std::isfinite(got[w]);
-        err = std::max(err, std::fabs((double)got[w] - bank_eval_f64(q, T, H, has_ln, &win[(size_t)w * K])));
+        err = std::max(err, std::fabs((double)got[w] - bank_eval_f64(net, &win[(size_t)w * K])));
     }
     const bool raised = h->h_range && *(volatile int*)h->h_range && !flag_before;
     if (raised) *(volatile int*)h->h_range = 0;                 // (the self-test's own overflow is not the streams')
