@@ -277,6 +277,44 @@ int  oww_bank_scores(oww_ctx* h, float* out);
 const float* oww_bank_scores_dev(const oww_ctx* h);
 int  oww_bank_routing(oww_ctx* h, int32_t info[6], double* weight_bytes);
 
+/* ---- per-stream custom verifiers: each stream re-scored by ITS user's verifier ------------------------------------------------------
+ * custom_verifier_model.train_custom_verifier (custom_verifier_model.py:116-177) fits a verifier to one user's voice, and Model attaches
+ * it to that user's Model (model.py:44-45, 185-195), with that Model's threshold.  oww_set_verifier above sets one verifier per label for
+ * every stream of the handle; these entries assign verifiers per (stream, fixed score column) and per (stream, bank slot).
+ *   oww_verifier_configure  before oww_commit: a device pool of `capacity` folded verifiers (1..65536; each w[T * 96] and a bias, T <= the
+ *                       feature ring) and an assignment table of every (stream, fixed column) and (stream, bank slot) pair -- a verifier
+ *                       id and a threshold each, all OWW_VERIFIER_DEFAULT.  A handle that never calls it allocates and launches exactly
+ *                       what it did before.
+ *   oww_verifier_add    after commit: the folded verifier of oww_set_verifier (w = coef / scale, n_w = T * 96, bias) -> pool id >= 0.
+ *                       n_w not a multiple of 96, T beyond the ring or non-finite values: OWW_EINVAL; a full pool: OWW_EINVAL.
+ *   oww_verifier_remove every assignment that names `id` reverts to OWW_VERIFIER_DEFAULT; the id is free again.
+ *   oww_assign_verifiers       score column `label`, streams stream_ids[n]: verifier_ids[n], thresholds[n] (host pointers).
+ *   oww_bank_assign_verifiers  the same for bank slot `slot`.
+ *                       Ids: >= 0 a pool verifier; OWW_VERIFIER_DEFAULT the label's handle-wide oww_set_verifier setting, if any (a bank
+ *                       slot has none: no verifier); OWW_VERIFIER_NONE no verifier, even where the label has a handle-wide one.  An
+ *                       unknown id, a stream out of range, a pool verifier whose T differs from the T of the column's model or of the
+ *                       slot's subscribed head, or a pool verifier for an empty slot: OWW_EINVAL, nothing changed.
+ *   oww_verifier_stats  out = {pairs whose assignment is not OWW_VERIFIER_DEFAULT, verifier evaluations of the last step}; the second is
+ *                       counted by the per-stream kernel only (0 while no pair is assigned and oww_set_verifier's kernel serves the label).
+ * Semantics per (stream, column) and (stream, slot), one verification per call: the raw head output (max over the chunks of a multi-chunk
+ * call); where it is >= the threshold it is replaced by sigmoid(w . last-T-feature-rows + bias) on the newest rows, bit for bit what
+ * oww_set_verifier's path computes for the same (w, bias, threshold); then first-5 zeroing, patience / threshold / debounce, the 30-deep
+ * ring (which keeps the verified score) and the VAD gate.  A per-stream assignment overrides the label's handle-wide verifier for that
+ * stream.  oww_reset keeps assignments (Model.reset keeps custom_verifier_models); a bank slot whose head changes (oww_subscribe,
+ * oww_bank_remove) drops its assignment back to the default; masked steps leave sitting-out streams alone; assignment calls wait for
+ * queued steps (oww_submit) and re-capture the oww_use_graph graph on the next step.
+ * Cost model: while any pair is assigned, one launch verifies every pair that has a verifier (a pool one or the handle-wide one), 16 pairs
+ * per wave: a 16-byte list entry and the raw score per pair, then T x 96 x 4 bytes of feature rows and of weights per re-scored pair;
+ * oww_set_verifier's kernel does not run then, and post-processing does not ride in the heads launch. */
+#define OWW_VERIFIER_DEFAULT -1
+#define OWW_VERIFIER_NONE    -2
+int  oww_verifier_configure(oww_ctx* h, int32_t capacity);
+int  oww_verifier_add(oww_ctx* h, const float* w, int32_t n_w, float bias);
+int  oww_verifier_remove(oww_ctx* h, int32_t id);
+int  oww_assign_verifiers(oww_ctx* h, int32_t label, const int32_t* stream_ids, int32_t n, const int32_t* verifier_ids, const float* thresholds);
+int  oww_bank_assign_verifiers(oww_ctx* h, int32_t slot, const int32_t* stream_ids, int32_t n, const int32_t* verifier_ids, const float* thresholds);
+int  oww_verifier_stats(oww_ctx* h, int64_t out[2]);
+
 /* ---- multi-GPU: delivery of the scores to one rank over RCCL (xGMI), for binders without torch.distributed ----------------------
  * Streams are independent, so N GPUs = N handles in N processes, each owning a contiguous range of the global streams (the
  * reference's only scale-out, utils.py:502-536 bulk_predict, splits FILES over processes the same way); nothing in the data path

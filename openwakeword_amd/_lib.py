@@ -78,6 +78,12 @@ SYMBOLS = {
     "oww_bank_scores": (C.c_int, [_P, _P]),
     "oww_bank_scores_dev": (_P, [_P]),
     "oww_bank_routing": (C.c_int, [_P, _P, _P]),
+    "oww_verifier_configure": (C.c_int, [_P, C.c_int32]),
+    "oww_verifier_add": (C.c_int, [_P, _P, C.c_int32, C.c_float]),
+    "oww_verifier_remove": (C.c_int, [_P, C.c_int32]),
+    "oww_assign_verifiers": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
+    "oww_bank_assign_verifiers": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
+    "oww_verifier_stats": (C.c_int, [_P, _P]),
     "oww_comm_id": (C.c_int, [_P]),
     "oww_comm_init": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "oww_gather_scores": (C.c_int, [_P, _P, _P]),

@@ -641,6 +641,18 @@ struct oww_ctx {
     double bank_wbytes = 0.0;                    // first-layer weight bytes one step streams over all tiles
     std::vector<float> probe_emb;                // oww_commit's fp32 probe embeddings [nb * 16][32][96]: oww_bank_add's self-test
     int probe_nb = 0;
+    // per-stream custom verifiers (oww_verifier_*): a pool of folded verifiers, one (verifier, threshold) per (stream, fixed column) and
+    // per (stream, bank slot), and the device list of the pairs to verify that stream_verifier_kernel walks
+    int vpool_cap = 0;                           // 0 = not configured (oww_verifier_configure)
+    int vpool_stride = 0;                        // floats per pool entry: feature ring x 96
+    std::vector<int> vpool_T;                    // [cap] feature rows of each pool verifier; 0 = free
+    float *d_vpool_w = nullptr, *d_vpool_b = nullptr;
+    std::vector<int> vasg_fix, vasg_bank;        // [S][NL], [S][K]: pool id, OWW_VERIFIER_DEFAULT or OWW_VERIFIER_NONE
+    std::vector<float> vthr_fix, vthr_bank;      // thresholds of the pool assignments
+    long long vasg_n = 0;                        // pairs whose assignment is not the default: > 0 switches to stream_verifier_kernel
+    std::vector<float> ver_thr;                  // host copy of d_verthr (the handle-wide verifiers' thresholds)
+    SvEntry* d_svlist = nullptr; int sv_n = 0;   // [S * (NL + K)] capacity; sv_n entries in use
+    unsigned long long* d_sv_eval = nullptr;     // evaluations of the last step
 };
 
 namespace {
@@ -1076,6 +1088,8 @@ void free_all(oww_ctx* h) {
     fr(h->d_bank_sub); fr(h->d_bank_idx); fr(h->d_bank_raw); fr(h->d_bank_scores); fr(h->d_bank_ring); fr(h->d_bank_npred);
     fr(h->d_bank_heads); fr(h->d_bank_pat); fr(h->d_bank_thr); fr(h->d_bank_tiles); fr(h->d_bank_entries);
     h->bank_tiles_cap = 0;
+    fr(h->d_vpool_w); fr(h->d_vpool_b); fr(h->d_svlist); fr(h->d_sv_eval);
+    h->sv_n = 0;
     comm_release(h);
 }
 
@@ -1128,6 +1142,26 @@ int launch_bank_post(oww_ctx* h, const StepArgs& a) {
     return 0;
 }
 
+// ---- per-stream verifiers: with any per-stream assignment, stream_verifier_kernel verifies every (stream, column / slot) pair that
+//      has a verifier -- its pool verifier or the column's handle-wide one -- and verifier_kernel does not run
+bool sv_active(const oww_ctx* h) { return h->vasg_n > 0; }
+
+int launch_stream_verifiers(oww_ctx* h, const StepArgs& a) {
+    HIPCHK(hipMemsetAsync(h->d_sv_eval, 0, sizeof(unsigned long long), h->stream));
+    if (h->sv_n == 0) return 0;
+    StreamVerifierParams v{};
+    v.list = h->d_svlist; v.n = h->sv_n;
+    v.raw = h->d_raw; v.bank_raw = h->d_bank_raw; v.NL = h->NL; v.K = h->bank_K;
+    v.feat = h->d_feat; v.nfeat = h->d_nfeat; v.TR = h->TR;
+    v.pool_w = h->d_vpool_w; v.pool_b = h->d_vpool_b; v.pool_stride = h->vpool_stride;
+    v.ver_w = h->d_verw; v.ver_b = h->d_verb; v.ver_stride = h->ver_stride;
+    v.stream_on = a.on; v.n_eval = h->d_sv_eval;
+    const int per_block = 4 * SV_PAIRS;
+    hipLaunchKernelGGL(stream_verifier_kernel, dim3((h->sv_n + per_block - 1) / per_block), dim3(256), 0, h->stream, v);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // one chunk of the streaming step on device-resident mel rows
 // (k, c: the mel rows of this chunk sit at row 8c of 8k per stream; first / last: of the CALL, which may span several mel slices)
 int step_chunk(oww_ctx* h, const StepArgs& a, int k, int c, bool first, bool last) {
@@ -1135,7 +1169,9 @@ int step_chunk(oww_ctx* h, const StepArgs& a, int k, int c, bool first, bool las
     // the bank reads this chunk's ring rows before the fixed heads launch (which may advance the ring counters: post_in_heads)
     if (bank_active(h)) if (int rc = run_bank(h, a, !first)) return rc;
     if (int rc = run_heads(h, a, h->Spad, !first, nullptr, -1, h->d_raw, 0)) return rc;
-    if (h->n_verifiers > 0 && last) {                // after the maximum over the call's chunks, on the newest feature rows
+    if (sv_active(h) && last) {                      // (as below: after the maximum over the call's chunks, before the ring advances)
+        if (int rc = launch_stream_verifiers(h, a)) return rc;
+    } else if (h->n_verifiers > 0 && last) {         // after the maximum over the call's chunks, on the newest feature rows
         VerifierParams v{};
         v.raw = h->d_raw; v.feat = h->d_feat; v.nfeat = h->d_nfeat; v.w = h->d_verw; v.bias = h->d_verb; v.thr = h->d_verthr; v.T = h->d_verT;
         v.wstride = h->ver_stride; v.NL = h->NL; v.TR = h->TR; v.S = h->S; v.stream_on = a.on;
@@ -1252,7 +1288,7 @@ int launch_step(oww_ctx* h, const StepArgs& args, const int16_t* d_pcm, int k) {
         if (int rc = launch_vad(h, args, d_pcm, OWW_CHUNK * k)) return rc;
     }
     StepArgs a = args;
-    a.post_in_heads = h->post_in_heads && k == 1 && h->n_verifiers == 0;
+    a.post_in_heads = h->post_in_heads && k == 1 && h->n_verifiers == 0 && !sv_active(h);
     if (h->fuse && k == 1 && (reinterpret_cast<uintptr_t>(d_pcm) & 15) == 0) {      // (the fused front end uses 16-byte sample loads)
         a.fused_pcm = d_pcm;
         if (int rc = step_chunk(h, a, 1, 0, true, true)) return rc;
@@ -1632,6 +1668,48 @@ int bank_route(oww_ctx* h) {
     if (!entries.empty()) HIPCHK(copy_sync(h->d_bank_entries, entries.data(), entries.size() * sizeof(int), hipMemcpyHostToDevice));
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }     // the launch list changed
     return 0;
+}
+
+// ---- per-stream verifier helpers (oww_verifier_*) ------------------------------------------------------------------------------------
+// The list stream_verifier_kernel walks, from the assignment tables: stream-major; per stream its fixed columns (a pool verifier, or
+// the column's handle-wide verifier where the pair keeps the default), then its bank slots (pool verifiers only).  Empty while no
+// pair carries a per-stream assignment: verifier_kernel then serves the handle-wide verifiers as before.  Callers have quiesced the
+// handle's stream; the captured step graph is invalidated (it bakes the list length).
+int sv_rebuild(oww_ctx* h) {
+    std::vector<SvEntry> list;
+    if (h->vasg_n > 0) {
+        const int NL = h->NL, K = h->bank_K;
+        list.reserve((size_t)h->S * NL);
+        for (int s = 0; s < h->S; ++s) {
+            for (int c = 0; c < NL; ++c) {
+                const size_t at = (size_t)s * NL + c;
+                const int v = h->vasg_fix[at];
+                if (v >= 0) list.push_back(SvEntry{s, (int16_t)c, (int16_t)h->vpool_T[v], v, h->vthr_fix[at]});
+                else if (v == OWW_VERIFIER_DEFAULT && !h->ver_T.empty() && h->ver_T[c] > 0)
+                    list.push_back(SvEntry{s, (int16_t)c, (int16_t)h->ver_T[c], ~c, h->ver_thr[c]});
+            }
+            for (int k = 0; k < K; ++k) {
+                const size_t at = (size_t)s * K + k;
+                const int v = h->vasg_bank[at];
+                if (v >= 0) list.push_back(SvEntry{s, (int16_t)~k, (int16_t)h->vpool_T[v], v, h->vthr_bank[at]});
+            }
+        }
+    }
+    if (!list.empty()) HIPCHK(copy_sync(h->d_svlist, list.data(), list.size() * sizeof(SvEntry), hipMemcpyHostToDevice));
+    h->sv_n = (int)list.size();
+    const unsigned long long zero = 0;
+    HIPCHK(copy_sync(h->d_sv_eval, &zero, sizeof zero, hipMemcpyHostToDevice));
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }     // the launch list changed
+    return 0;
+}
+
+// bank slots whose head changed (oww_subscribe, oww_bank_remove) drop their verifier assignment back to the default (none)
+int sv_drop_bank(oww_ctx* h, const std::vector<int>& slots) {
+    if (h->vpool_cap == 0) return 0;
+    bool any = false;
+    for (int at : slots)
+        if (h->vasg_bank[at] != OWW_VERIFIER_DEFAULT) { h->vasg_bank[at] = OWW_VERIFIER_DEFAULT; --h->vasg_n; any = true; }
+    return any ? sv_rebuild(h) : 0;
 }
 
 // float64 evaluation of a binary one-block net on one window x[T][96]: the bank self-test's reference
@@ -2131,6 +2209,23 @@ int alloc_bank(oww_ctx* h) {
     return 0;
 }
 
+// per-stream verifiers (oww_verifier_configure): the pool, the assignment tables (every pair at the default) and the pair list
+int alloc_verifiers(oww_ctx* h) {
+    h->vpool_stride = h->TR * OWW_EMB_DIM;
+    if (int rc = dalloc(h->stream, &h->d_vpool_w, (size_t)h->vpool_cap * h->vpool_stride)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_vpool_b, (size_t)h->vpool_cap)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_svlist, (size_t)h->S * (h->NL + h->bank_K), false)) return rc;
+    if (int rc = dalloc(h->stream, &h->d_sv_eval, 1)) return rc;
+    h->vpool_T.assign(h->vpool_cap, 0);
+    h->vasg_fix.assign((size_t)h->S * h->NL, OWW_VERIFIER_DEFAULT);
+    h->vthr_fix.assign((size_t)h->S * h->NL, 0.f);
+    h->vasg_bank.assign((size_t)h->S * h->bank_K, OWW_VERIFIER_DEFAULT);
+    h->vthr_bank.assign((size_t)h->S * h->bank_K, 0.f);
+    h->vasg_n = 0; h->sv_n = 0;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -2339,6 +2434,7 @@ int oww_commit(oww_ctx* h) {
     if (int rc = derive_reset_state(h, cal, clk)) return rc;
     if (h->hx) { h->probe_emb = cal.ref_emb; h->probe_nb = cal.nb; }      // (oww_bank_add's self-test inputs)
     if (h->bank_K > 0) if (int rc = alloc_bank(h)) return rc;
+    if (h->vpool_cap > 0) if (int rc = alloc_verifiers(h)) return rc;
     h->committed = true;
     return OWW_OK;
     OWW_GUARD_END
@@ -2621,18 +2717,21 @@ int oww_set_verifier(oww_ctx* h, int32_t label, const float* w, int32_t n_w, flo
         if (int rc = dalloc(h->stream, &h->d_verthr, (size_t)h->NL)) return rc;
         if (int rc = dalloc(h->stream, &h->d_verT, (size_t)h->NL)) return rc;
         h->ver_T.assign(h->NL, 0);
+        h->ver_thr.assign(h->NL, 0.f);
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     if (w) {
         HIPCHK(copy_sync(h->d_verw + (size_t)label * h->ver_stride, w, (size_t)n_w * sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(copy_sync(h->d_verb + label, &bias, sizeof(float), hipMemcpyHostToDevice));
         HIPCHK(copy_sync(h->d_verthr + label, &threshold, sizeof(float), hipMemcpyHostToDevice));
+        h->ver_thr[label] = threshold;
     }
     h->ver_T[label] = w ? T : 0;
     HIPCHK(copy_sync(h->d_verT, h->ver_T.data(), (size_t)h->NL * sizeof(int), hipMemcpyHostToDevice));
     h->n_verifiers = 0;
     for (int t : h->ver_T) h->n_verifiers += t > 0;
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }       // the launch list changed
+    if (sv_active(h)) if (int rc = sv_rebuild(h)) return rc;     // the pairs at the default follow the handle-wide verifier
     return OWW_OK;
     OWW_GUARD_END
 }
@@ -3192,6 +3291,7 @@ int oww_bank_remove(oww_ctx* h, int32_t id) {
     for (int i = 0; i < h->S * h->bank_K; ++i) if (h->bank_sub[i] == id) { h->bank_sub[i] = -1; changed.push_back(i); }
     if (!changed.empty()) HIPCHK(copy_sync(h->d_bank_sub, h->bank_sub.data(), h->bank_sub.size() * sizeof(int), hipMemcpyHostToDevice));
     if (int rc = bank_clear(h, changed)) return rc;
+    if (int rc = sv_drop_bank(h, changed)) return rc;
     (void)dev_free(h->bank[id].d_img);
     h->bank[id] = oww_ctx::BankHead{};
     return bank_route(h);
@@ -3236,6 +3336,7 @@ int oww_subscribe(oww_ctx* h, const int32_t* stream_ids, int32_t n, const int32_
     if (changed.empty()) return OWW_OK;
     HIPCHK(copy_sync(h->d_bank_sub, h->bank_sub.data(), h->bank_sub.size() * sizeof(int), hipMemcpyHostToDevice));
     if (int rc = bank_clear(h, changed)) return rc;
+    if (int rc = sv_drop_bank(h, changed)) return rc;
     return bank_route(h);
     OWW_GUARD_END
 }
@@ -3259,6 +3360,118 @@ int oww_bank_routing(oww_ctx* h, int32_t info[6], double* weight_bytes) {
     if (info)
         for (int c = 0; c < 2; ++c) { info[3 * c] = h->bank_ntiles[c]; info[3 * c + 1] = h->bank_wg[c]; info[3 * c + 2] = h->bank_entries_n[c]; }
     if (weight_bytes) *weight_bytes = h->bank_wbytes;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+// ---- per-stream custom verifiers ------------------------------------------------------------------------------------------------------
+int oww_verifier_configure(oww_ctx* h, int32_t capacity) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    if (h->committed) return fail(OWW_ESTATE, "oww_verifier_configure: call before oww_commit");
+    if (capacity < 1 || capacity > 65536) return fail(OWW_EINVAL, "oww_verifier_configure: capacity = %d (1..65536)", capacity);
+    h->vpool_cap = capacity;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_verifier_add(oww_ctx* h, const float* w, int32_t n_w, float bias) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed || h->vpool_cap == 0) return fail(OWW_ESTATE, "oww_verifier_add: needs oww_verifier_configure before oww_commit, and a committed handle");
+    if (!w || n_w <= 0 || n_w % OWW_EMB_DIM) return fail(OWW_EINVAL, "oww_verifier_add: %d weights (a verifier has T x 96)", n_w);
+    const int T = n_w / OWW_EMB_DIM;
+    if (T > h->TR) return fail(OWW_EINVAL, "oww_verifier_add: T = %d exceeds the handle's feature ring (%d rows)", T, h->TR);
+    for (int i = 0; i < n_w; ++i) if (!std::isfinite(w[i])) return fail(OWW_EINVAL, "oww_verifier_add: weight %d is not finite", i);
+    if (!std::isfinite(bias)) return fail(OWW_EINVAL, "oww_verifier_add: the bias is not finite");
+    int id = -1;
+    for (int v = 0; v < h->vpool_cap && id < 0; ++v) if (h->vpool_T[v] == 0) id = v;
+    if (id < 0) return fail(OWW_EINVAL, "oww_verifier_add: the verifier pool is full (capacity %d)", h->vpool_cap);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(copy_sync(h->d_vpool_w + (size_t)id * h->vpool_stride, w, (size_t)n_w * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(h->d_vpool_b + id, &bias, sizeof bias, hipMemcpyHostToDevice));
+    h->vpool_T[id] = T;
+    return id;
+    OWW_GUARD_END
+}
+
+int oww_verifier_remove(oww_ctx* h, int32_t id) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed || h->vpool_cap == 0) return fail(OWW_ESTATE, "oww_verifier_remove: no verifier pool on this handle");
+    if (id < 0 || id >= h->vpool_cap || h->vpool_T[id] == 0) return fail(OWW_EINVAL, "oww_verifier_remove: %d is not a pool verifier", id);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));     // in-flight steps may still read the entry and the list
+    for (auto* tab : {&h->vasg_fix, &h->vasg_bank})
+        for (int& v : *tab) if (v == id) { v = OWW_VERIFIER_DEFAULT; --h->vasg_n; }
+    h->vpool_T[id] = 0;
+    return sv_rebuild(h);
+    OWW_GUARD_END
+}
+
+// shared body of oww_assign_verifiers (bank = false: `col` is a score column) and oww_bank_assign_verifiers (bank = true: a slot)
+static int assign_impl(oww_ctx* h, bool bank, int32_t col, const int32_t* stream_ids, int32_t n, const int32_t* verifier_ids,
+                       const float* thresholds) {
+    const char* fn = bank ? "oww_bank_assign_verifiers" : "oww_assign_verifiers";
+    if (!h || !h->committed || h->vpool_cap == 0) return fail(OWW_ESTATE, "%s: no verifier pool on this handle (oww_verifier_configure)", fn);
+    if (bank && h->bank_K == 0) return fail(OWW_ESTATE, "%s: no bank on this handle", fn);
+    const int ncol = bank ? h->bank_K : h->NL;
+    if (col < 0 || col >= ncol) return fail(OWW_EINVAL, "%s: %s %d outside [0,%d)", fn, bank ? "slot" : "label", col, ncol);
+    if (n < 0 || (n > 0 && (!stream_ids || !verifier_ids || !thresholds))) return fail(OWW_EINVAL, "%s: bad argument", fn);
+    int colT = 0;                                      // feature rows of the column's model
+    if (!bank) for (const auto& hh : h->heads) if (col >= hh.out_col && col < hh.out_col + hh.n_out) colT = hh.T;
+    for (int i = 0; i < n; ++i) {
+        const int s = stream_ids[i], v = verifier_ids[i];
+        if (s < 0 || s >= h->S) return fail(OWW_EINVAL, "%s: stream id %d out of range (0..%d)", fn, s, h->S - 1);
+        if (v < OWW_VERIFIER_NONE || v >= h->vpool_cap || (v >= 0 && h->vpool_T[v] == 0))
+            return fail(OWW_EINVAL, "%s: %d is not a pool verifier, OWW_VERIFIER_DEFAULT or OWW_VERIFIER_NONE (stream %d)", fn, v, s);
+        if (v < 0) continue;
+        int T = colT;
+        if (bank) {
+            const int b = h->bank_sub[(size_t)s * h->bank_K + col];
+            if (b < 0) return fail(OWW_EINVAL, "%s: slot %d of stream %d is empty", fn, col, s);
+            T = h->bank[b].T;
+        }
+        if (h->vpool_T[v] != T)
+            return fail(OWW_EINVAL, "%s: verifier %d has T = %d feature rows, the model of stream %d's %s %d has T = %d", fn, v, h->vpool_T[v], s,
+                        bank ? "slot" : "label", col, T);
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));           // ordered behind every queued step (oww_submit)
+    std::vector<int>& tab = bank ? h->vasg_bank : h->vasg_fix;
+    std::vector<float>& thr = bank ? h->vthr_bank : h->vthr_fix;
+    for (int i = 0; i < n; ++i) {
+        const size_t at = (size_t)stream_ids[i] * ncol + col;
+        h->vasg_n += (verifier_ids[i] != OWW_VERIFIER_DEFAULT) - (tab[at] != OWW_VERIFIER_DEFAULT);
+        tab[at] = verifier_ids[i];
+        thr[at] = thresholds[i];
+    }
+    return sv_rebuild(h);
+}
+
+int oww_assign_verifiers(oww_ctx* h, int32_t label, const int32_t* stream_ids, int32_t n, const int32_t* verifier_ids, const float* thresholds) {
+    OWW_GUARD_BEGIN
+    return assign_impl(h, false, label, stream_ids, n, verifier_ids, thresholds);
+    OWW_GUARD_END
+}
+
+int oww_bank_assign_verifiers(oww_ctx* h, int32_t slot, const int32_t* stream_ids, int32_t n, const int32_t* verifier_ids, const float* thresholds) {
+    OWW_GUARD_BEGIN
+    return assign_impl(h, true, slot, stream_ids, n, verifier_ids, thresholds);
+    OWW_GUARD_END
+}
+
+int oww_verifier_stats(oww_ctx* h, int64_t out[2]) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed) return fail(OWW_ESTATE, "oww_verifier_stats: handle not committed");
+    if (!out) return fail(OWW_EINVAL, "oww_verifier_stats: null output");
+    unsigned long long n_eval = 0;
+    if (h->d_sv_eval) {
+        HIPCHK(hipSetDevice(h->cfg.device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(copy_sync(&n_eval, h->d_sv_eval, sizeof n_eval, hipMemcpyDeviceToHost));
+    }
+    out[0] = h->vasg_n;
+    out[1] = (int64_t)n_eval;
     return OWW_OK;
     OWW_GUARD_END
 }

@@ -1537,6 +1537,71 @@ __global__ __launch_bounds__(256) void verifier_kernel(VerifierParams p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// per-stream custom verifiers (oww_verifier_* / oww_assign_verifiers / oww_bank_assign_verifiers): one entry per (stream, fixed
+// score column) or (stream, bank slot) that has a verifier -- a pool entry assigned to that pair, or the column's handle-wide
+// verifier (oww_set_verifier) where the pair keeps the default.  Built on the host whenever an assignment changes.  A wave takes
+// SV_PAIRS entries, ballots raw >= threshold and evaluates each hit with all 64 lanes in the arithmetic of verifier_kernel (lane-
+// strided fmaf chain, xor butterfly 32..1, sigmoid), so the scores are bit for bit the handle-wide path's.
+// ------------------------------------------------------------------------------------------------
+struct SvEntry {
+    int32_t s;               // stream
+    int16_t col;             // >= 0: fixed score column; < 0: bank slot ~col
+    int16_t T;               // feature rows of the verifier (= of the column's model / the slot's head)
+    int32_t v;               // >= 0: pool verifier; < 0: the handle-wide verifier of column ~v
+    float thr;               // re-score when raw >= thr (model.py:322)
+};
+static_assert(sizeof(SvEntry) == 16, "SvEntry is one 16-byte load");
+
+constexpr int SV_PAIRS = 16;     // entries per wave
+struct StreamVerifierParams {
+    const SvEntry* list; int n;
+    float* raw;              // [S][NL] fixed head outputs of this step (re-scored in place)
+    float* bank_raw;         // [S][K] bank head outputs of this step (re-scored in place)
+    int NL, K;
+    const float* feat;       // feature ring [S][TR][96]
+    const uint32_t* nfeat;   // [S] (not yet advanced for this step)
+    int TR;
+    const float* pool_w; const float* pool_b; int pool_stride;    // pool [cap][pool_stride], [cap]
+    const float* ver_w; const float* ver_b; int ver_stride;       // handle-wide [NL][ver_stride], [NL]
+    const uint8_t* stream_on;    // oww_step_masked
+    unsigned long long* n_eval;  // evaluations of this call (zeroed before the launch)
+};
+
+__global__ __launch_bounds__(256) void stream_verifier_kernel(StreamVerifierParams p) {
+    const int lane = threadIdx.x & 63;
+    const int e0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * SV_PAIRS;
+    if (e0 >= p.n) return;
+    SvEntry me{0, 0, 0, 0, 0.f};
+    bool hit = false;
+    float* dst = nullptr;
+    if (lane < SV_PAIRS && e0 + lane < p.n) {
+        me = p.list[e0 + lane];
+        if (!p.stream_on || p.stream_on[me.s]) {
+            dst = me.col >= 0 ? p.raw + (size_t)me.s * p.NL + me.col : p.bank_raw + (size_t)me.s * p.K + ~(int)me.col;
+            hit = *dst >= me.thr;
+        }
+    }
+    uint64_t m = __ballot(hit);
+    if (lane == 0 && m) atomicAdd(p.n_eval, (unsigned long long)__popcll(m));
+    while (m) {
+        const int j = __builtin_ctzll(m);
+        m &= m - 1;
+        const int s = __shfl(me.s, j), T = __shfl((int)me.T, j), v = __shfl(me.v, j);
+        const float* w = v >= 0 ? p.pool_w + (size_t)v * p.pool_stride : p.ver_w + (size_t)(~v) * p.ver_stride;
+        const float bias = v >= 0 ? p.pool_b[v] : p.ver_b[~v];
+        const uint32_t slot0 = p.nfeat[s] + (uint32_t)(2 * p.TR - T + 1);     // oldest of the last T rows (as verifier_kernel)
+        float acc = 0.f;
+        for (int i = lane; i < T * 96; i += 64) {
+            const uint32_t slot = (slot0 + (uint32_t)(i / 96)) % (uint32_t)p.TR;
+            acc = fmaf(p.feat[((size_t)s * p.TR + slot) * 96 + i % 96], w[i], acc);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (lane == j) *dst = 1.0f / (1.0f + expf(-(acc + bias)));
+    }
+}
+
 // polyphase FIR rate conversion of every stream's message to 16 kHz (oww_resample; filter design: openwakeword_amd/resample.py).
 //   out[s][j] = sat_int16(rint(sum_k taps[(j p) % q][k] * in[s][(j p) / q + k - half + 1])),   zero outside the message.
 // A workgroup produces `opb` consecutive outputs of one stream (up to a whole 1280-sample chunk): the input span they touch is staged in LDS once, converted to float

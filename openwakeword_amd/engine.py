@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -141,14 +141,17 @@ class StreamEngine:
     def __init__(self, n_streams: int, heads: Dict[str, dict], embedding: Optional[dict] = None,
                  device: int = 0, max_chunks: int = 1, use_mfma: int = 3, debug_layers: bool = False,
                  feature_ring: int = 0, hip_stream: int = 0, vad: Optional[dict] = None, vad_threshold: float = 0.0,
-                 calibration_pcm: Union[np.ndarray, str, None] = "default", bank_slots: int = 0, bank_capacity: int = 0):
+                 calibration_pcm: Union[np.ndarray, str, None] = "default", bank_slots: int = 0, bank_capacity: int = 0,
+                 verifier_capacity: int = 0):
         """`vad`: weights of the on-device voice-activity stand-in network (weights.synthetic_vad layout); when given, every
         step also runs it on the frame's two 640-sample sub-frames and gates the scores with `vad_threshold` (model.py:366-381).
         `calibration_pcm` (use_mfma = 3): audio of the deployment's domain, int16 [n, k * 1280], that oww_commit adds to its built-in
         probes when it calibrates the activation scales and holds the fp16-split kernels to the exact-fp32 ones; "default" = speech
         (default_calibration_pcm), None = the synthetic probes only.
         `bank_slots` > 0 (use_mfma = 3): a head bank of `bank_capacity` heads, every stream subscribed to up to `bank_slots` of them
-        (oww_bank_configure; bank_add / subscribe / bank_scores below)."""
+        (oww_bank_configure; bank_add / subscribe / bank_scores below).
+        `verifier_capacity` > 0: a pool of that many per-stream custom verifiers (oww_verifier_configure; verifier_add /
+        assign_verifiers below)."""
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self._inflight: List[np.ndarray] = []
@@ -195,6 +198,9 @@ class StreamEngine:
             self.bank_slots = int(bank_slots)
             if self.bank_slots > 0:
                 _lib.check(self._lib.oww_bank_configure(self._h, self.bank_slots, int(bank_capacity) or 1024))
+            self.verifier_capacity = int(verifier_capacity)
+            if self.verifier_capacity > 0:
+                _lib.check(self._lib.oww_verifier_configure(self._h, self.verifier_capacity))
             _lib.check(self._lib.oww_commit(self._h))
             if vad_threshold:
                 _lib.check(self._lib.oww_set_vad_threshold(self._h, float(vad_threshold)))
@@ -413,6 +419,31 @@ class StreamEngine:
             return
         w = np.ascontiguousarray(w, dtype=np.float32).ravel()
         _lib.check(self._lib.oww_set_verifier(self._h, int(label), _ptr(w), int(w.size), float(bias), float(threshold)))
+
+    # ---- per-stream custom verifiers (include/owwhip.h: oww_verifier_*) ----
+    def verifier_add(self, w: np.ndarray, bias: float) -> int:
+        """Folded verifier (w [T*96], bias) into the pool -> id (needs verifier_capacity > 0)."""
+        w = np.ascontiguousarray(w, dtype=np.float32).ravel()
+        rc = self._lib.oww_verifier_add(self._h, _ptr(w), int(w.size), float(bias))
+        _lib.check(rc)
+        return int(rc)
+
+    def verifier_remove(self, verifier_id: int) -> None:
+        _lib.check(self._lib.oww_verifier_remove(self._h, int(verifier_id)))
+
+    def assign_verifiers(self, label: int, stream_ids, verifier_ids, thresholds, bank: bool = False) -> None:
+        """Per-stream verifier ids (>= 0 pool, -1 default, -2 none) and thresholds for score column `label` (bank: bank slot)."""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32).ravel()
+        v = np.ascontiguousarray(verifier_ids, dtype=np.int32).ravel()
+        t = np.ascontiguousarray(thresholds, dtype=np.float32).ravel()
+        fn = self._lib.oww_bank_assign_verifiers if bank else self._lib.oww_assign_verifiers
+        _lib.check(fn(self._h, int(label), _ptr(ids), ids.size, _ptr(v), _ptr(t)))
+
+    def verifier_stats(self) -> Tuple[int, int]:
+        """(pairs with a per-stream assignment, verifier evaluations of the last step)."""
+        out = np.zeros(2, dtype=np.int64)
+        _lib.check(self._lib.oww_verifier_stats(self._h, _ptr(out)))
+        return int(out[0]), int(out[1])
 
     def set_vad_threshold(self, threshold: float) -> None:
         """VAD gate of model.py:366-381 on the device (0 = off); the scores come from push_vad()."""

@@ -23,7 +23,7 @@ import pickle
 import wave
 from collections import defaultdict, deque
 from functools import partial
-from typing import Callable, DefaultDict, Dict, List, Optional, Sequence, Union
+from typing import Callable, DefaultDict, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -596,9 +596,11 @@ class BatchedModel:
     def __init__(self, n_streams: int, wakeword_models: Sequence[str], weights: Union[str, dict, None] = None,
                  device: int = 0, max_chunks: int = 1, hip_stream: int = 0, vad_weights: Optional[dict] = None,
                  vad_threshold: float = 0.0, use_mfma: Optional[int] = None, calibration_pcm="default",
-                 embedding_model_path: str = "", melspec_model_path: str = "", bank_slots: int = 0, bank_capacity: int = 1024):
+                 embedding_model_path: str = "", melspec_model_path: str = "", bank_slots: int = 0, bank_capacity: int = 1024,
+                 verifier_capacity: int = 0):
         # bank_slots > 0: a head bank (bank_add / subscribe / bank_scores): every stream is scored by the bank heads it subscribed to,
         # up to bank_slots of them, beside the fixed `wakeword_models` (which may then be empty)
+        # verifier_capacity > 0: a pool of per-stream custom verifiers (add_verifier / assign_verifiers / assign_bank_verifiers)
         if not wakeword_models and int(bank_slots) <= 0:
             raise ValueError("BatchedModel needs wakeword_models, or a head bank (bank_slots > 0)")
         self._weights = weights
@@ -631,8 +633,12 @@ class BatchedModel:
         # (StreamEngine); "default" = speech shipped with the package
         self.engine = make_engine(n_streams, heads, emb, use_mfma, device=device, max_chunks=max_chunks, hip_stream=hip_stream,
                                   vad=vad_weights, vad_threshold=vad_threshold, calibration_pcm=calibration_pcm,
-                                  bank_slots=int(bank_slots), bank_capacity=int(bank_capacity))
+                                  bank_slots=int(bank_slots), bank_capacity=int(bank_capacity),
+                                  verifier_capacity=int(verifier_capacity))
         self.bank_slots = int(bank_slots)
+        self.verifier_capacity = int(verifier_capacity)
+        self._model_T = {n: int(h["T"]) for n, h in heads.items()}
+        self._verifier_T: Dict[int, int] = {}
         self.labels: List[str] = []
         self._keep: List[int] = []
         col = 0
@@ -759,6 +765,79 @@ class BatchedModel:
         w, b = fold_verifier(verifier)
         for c in cols:
             self.engine.set_verifier(c, w, b, threshold)
+
+    # ---- per-stream custom verifiers (include/owwhip.h: oww_verifier_*) ----
+    def add_verifier(self, verifier) -> int:
+        """Put one user's custom verifier into the pool -> verifier id.  `verifier` is what set_custom_verifier takes: the reference's
+        scikit-learn pipeline (custom_verifier_model.py:95-113) or a folded (w [T*96], bias) pair.  Needs verifier_capacity > 0."""
+        if self.verifier_capacity <= 0:
+            raise ValueError("this BatchedModel has no verifier pool (verifier_capacity = 0)")
+        w, b = fold_verifier(verifier)
+        if w.size == 0 or w.size % 96:
+            raise ValueError(f"a verifier has T x 96 weights, got {w.size}")
+        T = w.size // 96
+        if T > self.engine.feature_ring:
+            raise ValueError(f"the verifier reads T = {T} feature rows, more than the feature ring holds ({self.engine.feature_ring})")
+        vid = self.engine.verifier_add(w, b)
+        self._verifier_T[vid] = T
+        return vid
+
+    def remove_verifier(self, verifier_id: int) -> None:
+        """Drop a pool verifier; every stream assigned to it falls back to the default (the handle-wide set_custom_verifier)."""
+        if int(verifier_id) not in self._verifier_T:
+            raise ValueError(f"{verifier_id} is not a verifier of this BatchedModel's pool")
+        self.engine.verifier_remove(int(verifier_id))
+        del self._verifier_T[int(verifier_id)]
+
+    def _verifier_args(self, stream_ids, verifier_ids, threshold, T: Optional[int]):
+        ids = np.asarray(stream_ids)
+        if ids.ndim != 1 or ids.dtype.kind not in "iu":
+            raise ValueError("stream_ids must be a 1-D integer sequence")
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= self.n_streams):
+            raise ValueError(f"stream ids must lie in 0 .. {self.n_streams - 1}")
+        v = np.asarray(verifier_ids)
+        if v.dtype.kind not in "iu" or v.ndim > 1 or (v.ndim == 1 and v.size != ids.size):
+            raise ValueError(f"verifier_ids must be one integer or {ids.size} of them, got {v.dtype} {v.shape}")
+        v = np.broadcast_to(v, ids.shape).astype(np.int64)
+        if v.size and int(v.min()) < -2:
+            raise ValueError("verifier ids are >= 0, or -1 (default) / -2 (none)")
+        for x in np.unique(v[v >= 0]):
+            if int(x) not in self._verifier_T:
+                raise ValueError(f"{int(x)} is not a verifier of this BatchedModel's pool")
+            if T is not None and self._verifier_T[int(x)] != T:
+                raise ValueError(f"verifier {int(x)} reads T = {self._verifier_T[int(x)]} feature rows, the model has T = {T}")
+        t = np.asarray(threshold)
+        if t.dtype.kind not in "iuf" or t.ndim > 1 or (t.ndim == 1 and t.size != ids.size):
+            raise ValueError(f"threshold must be one number or {ids.size} of them, got {t.dtype} {t.shape}")
+        return ids, v, np.broadcast_to(t, ids.shape).astype(np.float32)
+
+    def assign_verifiers(self, stream_ids: Sequence[int], model_name: str, verifier_ids, threshold=0.1) -> None:
+        """`Model(custom_verifier_models={model_name: ...}, custom_verifier_threshold=threshold)` per stream: the listed streams'
+        columns of `model_name` (every class of a multiclass model) are re-scored by their own pool verifier.  verifier_ids /
+        threshold: one value or one per stream; id -1 = the model's set_custom_verifier setting (if any), -2 = no verifier at all."""
+        if self.verifier_capacity <= 0:
+            raise ValueError("this BatchedModel has no verifier pool (verifier_capacity = 0)")
+        if model_name not in self._parent.values():
+            raise ValueError("Custom verifier models were provided, but some were not matched with a base model!")
+        ids, v, t = self._verifier_args(stream_ids, verifier_ids, threshold, self._model_T[model_name])
+        for c in [c for c, n in self._parent.items() if n == model_name]:
+            self.engine.assign_verifiers(c, ids, v, t)
+
+    def assign_bank_verifiers(self, stream_ids: Sequence[int], slot: int, verifier_ids, threshold=0.1) -> None:
+        """assign_verifiers for bank slot `slot` of the listed streams (the slot must hold a head whose T matches; a slot whose head
+        changes drops its verifier); id -1 and -2 both mean none here."""
+        if self.verifier_capacity <= 0:
+            raise ValueError("this BatchedModel has no verifier pool (verifier_capacity = 0)")
+        if self.bank_slots <= 0:
+            raise ValueError("this BatchedModel has no head bank (bank_slots = 0)")
+        if not 0 <= int(slot) < self.bank_slots:
+            raise ValueError(f"slot {slot} outside 0 .. {self.bank_slots - 1}")
+        ids, v, t = self._verifier_args(stream_ids, verifier_ids, threshold, None)
+        self.engine.assign_verifiers(int(slot), ids, v, t, bank=True)
+
+    def verifier_stats(self) -> Tuple[int, int]:
+        """(pairs of (stream, column / slot) with a per-stream assignment, verifier evaluations of the last step)."""
+        return self.engine.verifier_stats()
 
     def set_vad_threshold(self, threshold: float) -> None:
         """The VAD gate of `Model(vad_threshold=...)` (model.py:366-381) for every stream; 0 switches it off."""
