@@ -315,6 +315,50 @@ int  oww_assign_verifiers(oww_ctx* h, int32_t label, const int32_t* stream_ids, 
 int  oww_bank_assign_verifiers(oww_ctx* h, int32_t slot, const int32_t* stream_ids, int32_t n, const int32_t* verifier_ids, const float* thresholds);
 int  oww_verifier_stats(oww_ctx* h, int64_t out[2]);
 
+/* ---- stream state records: take a live stream's state out, put it in, move it ---------------------------------------------------------
+ * In the reference a stream's state IS its Model object (prediction_buffer model.py:198, reset model.py:226-230; the AudioFeatures
+ * buffers utils.py:163-171): a caller keeps it, hands it to another thread or pickles it.  Here that state lives in HBM in layouts only
+ * the step kernels understand; these entries make it a portable record, so that a server can defragment its slots, drain a worker or
+ * hand a connection to another handle without dropping the stream's context.  A stream that was exported and imported, or moved,
+ * continues BIT FOR BIT as if it had stayed: scores do not depend on the slot or on the neighbours.
+ *   oww_state_info    *record_bytes = size of one record (a multiple of 16), *fingerprint = 64-bit hash of what a record's bits depend
+ *                     on: kernel family and interleave flag, per-layer history lengths, feature ring rows, score columns, bank slots,
+ *                     VAD present or not, the 21 scale exponents of oww_calibration_info, and the bytes of every blob loaded (mel,
+ *                     embedding, heads in order, VAD).  Either pointer may be NULL.
+ *   oww_state_export  records of streams stream_ids[n], back to back in list order, into `out` (n * record_bytes; host, or a 16-byte
+ *                     aligned device pointer when out_on_device).  Record = 32-byte header {magic, record layout version, record_bytes,
+ *                     0, fingerprint, 0} + the stream's own words of every per-stream array that outlives a step, as bits, in a
+ *                     slot-independent order: conv histories (for a grouped array: the words of the group block whose position is the
+ *                     stream's, in ascending block index), PCM tail, feature ring and frame counter, score ring, prediction counter,
+ *                     raw and final scores, VAD ring / counter and, with oww_load_vad, (h, c) and the last VAD score; with a bank, the
+ *                     slots' raw / final scores, rings and counters.  Not carried: what one call writes and consumes (stage hand-over
+ *                     buffers, mel rows, embeddings -- oww_get_mel is undefined after an import until the next step), the handle's
+ *                     sticky range flag, subscriptions and verifier assignments (see oww_move_streams).
+ *   oww_state_import  the reverse, into streams stream_ids[n] (no duplicates).  Every header is checked first: a record of another
+ *                     layout version, record size or fingerprint, a duplicate or out-of-range id -> OWW_EINVAL (the message names
+ *                     both sides) and the handle is untouched.  Writes only the words the target streams own: the other streams of
+ *                     a shared group block keep every bit.  Subscriptions and verifier assignments are the caller's business on the
+ *                     target handle: oww_subscribe first (which restarts the slot), then import (which puts ring and counter back).
+ *   oww_move_streams  export + import inside one handle without the host: stream src[i] becomes stream dst[i].  All reads happen
+ *                     before any write, so swaps, cycles and chains (a->b, b->c) are legal; dst holds no duplicates.  The device state
+ *                     of a source that is nobody's destination keeps its contents (reset it when the slot is reused).  What the
+ *                     LIBRARY keeps per stream travels too: bank subscriptions and per-stream verifier assignments (fixed columns and
+ *                     bank slots) leave the source slot -- a source that is nobody's destination ends up with empty slots and default
+ *                     assignments -- and arrive at the destination; a moved bank slot does NOT restart.  The routing table and the
+ *                     verifier list are rebuilt once per call, and only then is the oww_use_graph graph re-captured on the next step.
+ * All four return OWW_ESTATE before oww_commit.  Export, import and move run on the handle's stream behind every queued step
+ * (oww_submit) and return when they are complete.  A handle that never calls them allocates and launches exactly what it did before;
+ * the first call builds the layout table and hashes the weights (a few ms).
+ * Cost model: pure data movement, ~50 KB per stream and direction.  One launch per array kind, work per (stream, array): 16-byte
+ * accesses on the record side always and on the live side for every array in which a stream's words are contiguous.  The deeper conv
+ * histories interleave 2 / 4 / 8 streams (VAD: 16) in every 64-byte run, so a lone stream touches its whole group block there (about
+ * 4x its own bytes over the record); a list that names every stream of a block is served as full rows, at the cost of a plain copy.
+ * These launches are not counted by oww_kernel_times. */
+int  oww_state_info(oww_ctx* h, size_t* record_bytes, uint64_t* fingerprint);
+int  oww_state_export(oww_ctx* h, const int32_t* stream_ids, int32_t n, void* out, int out_on_device);
+int  oww_state_import(oww_ctx* h, const int32_t* stream_ids, int32_t n, const void* in, int in_on_device);
+int  oww_move_streams(oww_ctx* h, const int32_t* src, const int32_t* dst, int32_t n);
+
 /* ---- multi-GPU: delivery of the scores to one rank over RCCL (xGMI), for binders without torch.distributed ----------------------
  * Streams are independent, so N GPUs = N handles in N processes, each owning a contiguous range of the global streams (the
  * reference's only scale-out, utils.py:502-536 bulk_predict, splits FILES over processes the same way); nothing in the data path

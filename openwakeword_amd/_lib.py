@@ -84,6 +84,10 @@ SYMBOLS = {
     "oww_assign_verifiers": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
     "oww_bank_assign_verifiers": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
     "oww_verifier_stats": (C.c_int, [_P, _P]),
+    "oww_state_info": (C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "oww_state_export": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),
+    "oww_state_import": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),
+    "oww_move_streams": (C.c_int, [_P, _P, _P, C.c_int32]),
     "oww_comm_id": (C.c_int, [_P]),
     "oww_comm_init": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "oww_gather_scores": (C.c_int, [_P, _P, _P]),

@@ -24,6 +24,7 @@
 #include "owwhip_hx.h"
 #include "owwhip_vad.h"
 #include "owwhip_fused.h"
+#include "owwhip_state.h"
 
 using namespace owk;
 
@@ -653,6 +654,16 @@ struct oww_ctx {
     std::vector<float> ver_thr;                  // host copy of d_verthr (the handle-wide verifiers' thresholds)
     SvEntry* d_svlist = nullptr; int sv_n = 0;   // [S * (NL + K)] capacity; sv_n entries in use
     unsigned long long* d_sv_eval = nullptr;     // evaluations of the last step
+    // stream state records (oww_state_*, oww_move_streams; owwhip_state.h): built by the first of those calls, nothing before it
+    struct StateGroupSec { float* live; int spg, ppr; bool il; uint32_t block_words, off; };
+    bool st_ready = false;
+    std::vector<ows::FlatSection> st_flat;       // host copy of d_st_flat
+    std::vector<StateGroupSec> st_group;
+    ows::FlatSection* d_st_flat = nullptr;
+    uint32_t st_record_words = 0, st_flat_quads = 0;
+    uint64_t st_fp = 0;                          // fingerprint of family, layouts, ring sizes, scales and weights
+    int* d_st_items = nullptr; size_t st_items_cap = 0;      // [ids | group items per level] of the call being served
+    uint32_t* d_st_stage = nullptr; size_t st_stage_words = 0;   // records in flight between a host buffer / the two halves of a move
 };
 
 namespace {
@@ -1090,6 +1101,8 @@ void free_all(oww_ctx* h) {
     h->bank_tiles_cap = 0;
     fr(h->d_vpool_w); fr(h->d_vpool_b); fr(h->d_svlist); fr(h->d_sv_eval);
     h->sv_n = 0;
+    fr(h->d_st_flat); fr(h->d_st_items); fr(h->d_st_stage);
+    h->st_items_cap = 0; h->st_stage_words = 0; h->st_ready = false;
     comm_release(h);
 }
 
@@ -2223,6 +2236,189 @@ int alloc_verifiers(oww_ctx* h) {
     h->vthr_bank.assign((size_t)h->S * h->bank_K, 0.f);
     h->vasg_n = 0; h->sv_n = 0;
     HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- stream state records (oww_state_info / oww_state_export / oww_state_import / oww_move_streams; kernels in owwhip_state.h) ---------
+uint64_t fp_mix(uint64_t hsh, const void* data, size_t nbytes) {           // FNV-1a, 64 bit
+    const unsigned char* b = static_cast<const unsigned char*>(data);
+    for (size_t i = 0; i < nbytes; ++i) { hsh ^= b[i]; hsh *= 1099511628211ull; }
+    return hsh;
+}
+
+// Record layout and fingerprint of this handle, and the device copy of the flat section table.  Built by the first call that needs
+// it: a handle that never exports, imports or moves a stream allocates nothing here.
+int state_layout(oww_ctx* h) {
+    if (h->st_ready) return 0;
+    h->st_flat.clear(); h->st_group.clear();
+    uint32_t off = ows::kHeaderWords;
+    auto flat = [&](void* live, size_t stride, size_t len) {
+        if (!live || len == 0) return;
+        h->st_flat.push_back(ows::FlatSection{static_cast<uint32_t*>(live), (uint32_t)stride, (uint32_t)len, off, (uint32_t)(stride % 4 == 0 && len % 4 == 0)});
+        off += (uint32_t)((len + 3) / 4 * 4);
+    };
+    const bool il = h->hx && owh::kInterleave;
+    const size_t NL = (size_t)h->NL, K = (size_t)h->bank_K;
+    for (int a = 0; a < N_STATE; ++a)
+        if (!h->rr || kStateSpgRr[a] == 1) flat(h->d_state[a], h->state_len[a], h->state_len[a]);
+    flat(h->d_tail, 240, 240);                                            // 480 int16 samples
+    flat(h->d_feat, (size_t)h->TR * OWW_EMB_DIM, (size_t)h->TR * OWW_EMB_DIM);
+    flat(h->d_ring, NL * OWW_SCORE_RING, NL * OWW_SCORE_RING);
+    flat(h->d_raw, NL, NL); flat(h->d_scores, NL, NL);
+    flat(h->d_nfeat, 1, 1); flat(h->d_npred, 1, 1);
+    flat(h->d_vadring, 8, 8); flat(h->d_nvad, 1, 1);
+    if (h->vad) flat(h->d_vadlast, 1, 1);
+    if (K) { flat(h->d_bank_raw, K, K); flat(h->d_bank_scores, K, K); flat(h->d_bank_npred, K, K); flat(h->d_bank_ring, K * OWW_SCORE_RING, K * OWW_SCORE_RING); }
+    h->st_flat_quads = off / 4;
+    auto group = [&](float* live, int spg, int ppr, bool inter, uint32_t block_words) -> int {
+        const int R = ppr >= 4 ? 1 : 4 / ppr;
+        if (block_words % (16 * R) || (ppr != 1 && ppr != 2 && ppr != 4 && ppr != 8) || spg * ppr > 16)
+            return fail(OWW_ESTATE, "state records: a group block of %u words, %d streams and %d positions per stream is not a layout the record kernels know", block_words, spg, ppr);
+        h->st_group.push_back(oww_ctx::StateGroupSec{live, spg, ppr, inter, block_words, off});
+        off += block_words / 16 * ppr;
+        return 0;
+    };
+    for (int a = 0; a < N_STATE; ++a)
+        if (h->rr && kStateSpgRr[a] > 1)
+            if (int rc = group(h->d_state[a], kStateSpgRr[a], il ? 16 / kStateSpgRr[a] : kStateFposRr[a], il, (uint32_t)(h->state_len[a] * kStateSpgRr[a]))) return rc;
+    if (h->vad) if (int rc = group(h->d_vadhc, 16, 1, true, 4096)) return rc;      // (h, c): [4 arrays][16 registers][4 j][16 streams]
+    h->st_record_words = off;
+    // fingerprint: what a record's bits depend on
+    uint64_t fp = 1469598103934665603ull;
+    std::vector<int32_t> v = {(int32_t)ows::kLayoutVersion, h->cfg.use_mfma, il ? 1 : 0};
+    for (int a = 0; a < N_STATE; ++a) v.push_back(h->state_len[a]);
+    v.push_back(h->TR); v.push_back(h->NL); v.push_back(h->bank_K); v.push_back(h->vad ? 1 : 0);
+    for (int l = 0; l < 20; ++l) v.push_back(h->hx ? h->hx_e[l] : 0);
+    v.push_back(h->hx ? h->hx_efeat : 0);
+    fp = fp_mix(fp, v.data(), v.size() * sizeof(int32_t));
+    fp = fp_mix(fp, h->mel_blob.data(), h->mel_blob.size() * sizeof(float));
+    fp = fp_mix(fp, h->emb_blob.data(), h->emb_blob.size() * sizeof(float));
+    for (const auto& hh : h->heads) {
+        const int32_t hdr[6] = {hh.kind, hh.T, hh.hidden, hh.n_out, hh.has_ln, hh.n_blocks};
+        fp = fp_mix(fp, hdr, sizeof hdr);
+        fp = fp_mix(fp, hh.blob.data(), hh.blob.size() * sizeof(float));
+    }
+    fp = fp_mix(fp, h->vad_blob.data(), h->vad_blob.size() * sizeof(float));
+    h->st_fp = fp;
+    if (!h->d_st_flat) HIPCHK(dev_alloc(&h->d_st_flat, h->st_flat.size() * sizeof(ows::FlatSection)));
+    HIPCHK(copy_sync(h->d_st_flat, h->st_flat.data(), h->st_flat.size() * sizeof(ows::FlatSection), hipMemcpyHostToDevice));
+    h->st_ready = true;
+    return 0;
+}
+
+// One list of streams as the record kernels want it: the ids in record order, and per group size (2, 4, 8, 16 streams) the touched
+// group blocks with the record index of every place -- found by one sort of the list, so that a block whose streams are all listed
+// is served by one workgroup per array as full rows.  Offsets are into the int buffer the lists are uploaded in.
+constexpr int kStateLevels[4] = {2, 4, 8, 16};
+struct StateList { int n = 0; size_t ids_at = 0; size_t items_at[4] = {}; int n_groups[4] = {}; };
+
+void state_list_build(const oww_ctx* h, const int32_t* ids, int n, std::vector<int>& buf, StateList& L) {
+    L.n = n; L.ids_at = buf.size();
+    buf.insert(buf.end(), ids, ids + n);
+    std::vector<std::pair<int, int>> order(n);
+    for (int i = 0; i < n; ++i) order[i] = {ids[i], i};
+    std::sort(order.begin(), order.end());
+    for (int lv = 0; lv < 4; ++lv) {
+        const int G = kStateLevels[lv];
+        bool used = false;
+        for (const auto& g : h->st_group) used = used || g.spg == G;
+        L.items_at[lv] = buf.size(); L.n_groups[lv] = 0;
+        if (!used) continue;
+        size_t cur = 0; int cur_g = -1;
+        for (const auto& e : order) {
+            const int g = e.first / G, place = e.first % G;
+            if (g != cur_g || buf[cur + 1 + place] >= 0) {            // a new block (or a stream listed twice: a block entry of its own)
+                cur = buf.size(); cur_g = g;
+                buf.push_back(g);
+                buf.insert(buf.end(), G, -1);
+                ++L.n_groups[lv];
+            }
+            buf[cur + 1 + place] = e.second;
+        }
+    }
+}
+
+int state_lists_upload(oww_ctx* h, const std::vector<int>& buf) {
+    if (buf.size() > h->st_items_cap) {
+        if (h->d_st_items) { HIPCHK(hipStreamSynchronize(h->stream)); (void)dev_free(h->d_st_items); }
+        h->d_st_items = nullptr; h->st_items_cap = 0;
+        if (dev_alloc(&h->d_st_items, buf.size() * sizeof(int)) != hipSuccess) return fail(OWW_ENOMEM, "out of device memory for %zu stream list bytes", buf.size() * sizeof(int));
+        h->st_items_cap = buf.size();
+    }
+    HIPCHK(copy_async(h->d_st_items, buf.data(), buf.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+int state_stage(oww_ctx* h, size_t n) {
+    const size_t need = n * (size_t)h->st_record_words;
+    if (need <= h->st_stage_words) return 0;
+    if (h->d_st_stage) { HIPCHK(hipStreamSynchronize(h->stream)); (void)dev_free(h->d_st_stage); }
+    h->d_st_stage = nullptr; h->st_stage_words = 0;
+    if (dev_alloc(&h->d_st_stage, need * 4) != hipSuccess) return fail(OWW_ENOMEM, "out of device memory for %zu bytes of stream state records", need * 4);
+    h->st_stage_words = need;
+    return 0;
+}
+
+// gather (SCATTER = false: live -> rec) or scatter (rec -> live) of one uploaded list, on the handle's stream
+template <bool SCATTER>
+int state_xfer(oww_ctx* h, const StateList& L, uint32_t* rec) {
+    if (L.n == 0) return 0;
+    ows::FlatParams fp{};
+    fp.ids = h->d_st_items + L.ids_at; fp.sec = h->d_st_flat; fp.n_sec = (int)h->st_flat.size(); fp.flat_quads = h->st_flat_quads;
+    fp.rec = rec; fp.record_words = h->st_record_words; fp.record_bytes = h->st_record_words * 4;
+    fp.fp_lo = (uint32_t)h->st_fp; fp.fp_hi = (uint32_t)(h->st_fp >> 32);
+    hipLaunchKernelGGL(ows::state_flat_kernel<SCATTER>, dim3(L.n, (h->st_flat_quads + 255) / 256), dim3(256), 0, h->stream, fp);
+    HIPCHK(hipGetLastError());
+    for (const auto& g : h->st_group) {
+        int lv = 0;
+        while (kStateLevels[lv] != g.spg) ++lv;
+        if (L.n_groups[lv] == 0) continue;
+        ows::GroupParams gp{};
+        const int R = g.ppr >= 4 ? 1 : 4 / g.ppr;
+        gp.live = reinterpret_cast<uint32_t*>(g.live); gp.block_words = g.block_words; gp.items = h->d_st_items + L.items_at[lv];
+        gp.n_chunks = (int)(g.block_words / (16 * R)); gp.rec = rec; gp.record_words = h->st_record_words; gp.off = g.off;
+        const dim3 grid(L.n_groups[lv], (gp.n_chunks + 63) / 64);
+#define OWS_GO(SPG, PPR, IL) hipLaunchKernelGGL((ows::state_group_kernel<SPG, PPR, IL, SCATTER>), grid, dim3(64), 0, h->stream, gp)
+        if (g.il) {
+            if (g.spg == 2) OWS_GO(2, 8, true); else if (g.spg == 4) OWS_GO(4, 4, true); else if (g.spg == 8) OWS_GO(8, 2, true); else OWS_GO(16, 1, true);
+        } else {
+            if (g.spg == 2 && g.ppr == 8) OWS_GO(2, 8, false); else if (g.spg == 4 && g.ppr == 4) OWS_GO(4, 4, false);
+            else if (g.spg == 8 && g.ppr == 2) OWS_GO(8, 2, false); else if (g.spg == 8 && g.ppr == 1) OWS_GO(8, 1, false);
+            else return fail(OWW_ESTATE, "state records: no kernel for %d streams x %d positions per block", g.spg, g.ppr);
+        }
+#undef OWS_GO
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+// ids in [0, S); unique where asked
+int state_check_ids(const oww_ctx* h, const char* fn, const char* what, const int32_t* ids, int n, bool unique) {
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= h->S) return fail(OWW_EINVAL, "%s: %s stream id %d out of range (0..%d)", fn, what, ids[i], h->S - 1);
+    if (unique && n > 1) {
+        std::vector<int32_t> t(ids, ids + n);
+        std::sort(t.begin(), t.end());
+        const auto dup = std::adjacent_find(t.begin(), t.end());
+        if (dup != t.end()) return fail(OWW_EINVAL, "%s: %s stream id %d is listed twice", fn, what, *dup);
+    }
+    return 0;
+}
+
+// the 32-byte headers of n records (host copy) against this handle
+int state_check_headers(const oww_ctx* h, const uint32_t* hdr /*[n][8]*/, int n) {
+    const uint32_t rb = h->st_record_words * 4;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t* q = hdr + (size_t)i * ows::kHeaderWords;
+        if (q[0] != ows::kMagic) return fail(OWW_EINVAL, "oww_state_import: record %d does not start with a stream state header (magic %08x)", i, q[0]);
+        if (q[1] != ows::kLayoutVersion)
+            return fail(OWW_EINVAL, "oww_state_import: record %d has record layout version %u, this library reads version %u", i, q[1], ows::kLayoutVersion);
+        const uint64_t fp = (uint64_t)q[4] | ((uint64_t)q[5] << 32);
+        if (q[2] != rb || fp != h->st_fp)
+            return fail(OWW_EINVAL, "oww_state_import: record %d comes from another configuration: the record carries fingerprint %016llx and %u bytes, "
+                        "this handle has fingerprint %016llx and %u bytes (kernel family, ring sizes, bank slots, VAD, calibration scales or weights differ)",
+                        i, (unsigned long long)fp, q[2], (unsigned long long)h->st_fp, rb);
+    }
     return 0;
 }
 
@@ -3472,6 +3668,123 @@ int oww_verifier_stats(oww_ctx* h, int64_t out[2]) {
     }
     out[0] = h->vasg_n;
     out[1] = (int64_t)n_eval;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+// ---- stream state records -------------------------------------------------------------------------------------------------------------
+#define OWW_STATE_ENTER(fn)                                                                                     \
+    if (!h) return fail(OWW_EINVAL, fn ": null handle");                                                        \
+    if (!h->committed) return fail(OWW_ESTATE, fn ": handle not committed");                                    \
+    HIPCHK(hipSetDevice(h->cfg.device));                                                                        \
+    if (int rc__ = state_layout(h)) return rc__;
+
+int oww_state_info(oww_ctx* h, size_t* record_bytes, uint64_t* fingerprint) {
+    OWW_GUARD_BEGIN
+    OWW_STATE_ENTER("oww_state_info")
+    if (record_bytes) *record_bytes = (size_t)h->st_record_words * 4;
+    if (fingerprint) *fingerprint = h->st_fp;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_state_export(oww_ctx* h, const int32_t* stream_ids, int32_t n, void* out, int out_on_device) {
+    OWW_GUARD_BEGIN
+    OWW_STATE_ENTER("oww_state_export")
+    if (n < 0 || (n > 0 && (!stream_ids || !out))) return fail(OWW_EINVAL, "oww_state_export: bad argument");
+    if (n == 0) return OWW_OK;
+    if (int rc = state_check_ids(h, "oww_state_export", "the", stream_ids, n, false)) return rc;
+    if (out_on_device && (reinterpret_cast<uintptr_t>(out) & 15)) return fail(OWW_EINVAL, "oww_state_export: a device buffer must be 16-byte aligned");
+    std::vector<int> buf;
+    StateList L;
+    state_list_build(h, stream_ids, n, buf, L);
+    if (!out_on_device) if (int rc = state_stage(h, n)) return rc;
+    if (int rc = state_lists_upload(h, buf)) return rc;
+    uint32_t* rec = out_on_device ? static_cast<uint32_t*>(out) : h->d_st_stage;
+    if (int rc = state_xfer<false>(h, L, rec)) return rc;
+    if (!out_on_device) HIPCHK(copy_async(out, rec, (size_t)n * h->st_record_words * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));           // the host list was the upload's source; a host buffer is complete on return
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_state_import(oww_ctx* h, const int32_t* stream_ids, int32_t n, const void* in, int in_on_device) {
+    OWW_GUARD_BEGIN
+    OWW_STATE_ENTER("oww_state_import")
+    if (n < 0 || (n > 0 && (!stream_ids || !in))) return fail(OWW_EINVAL, "oww_state_import: bad argument");
+    if (n == 0) return OWW_OK;
+    if (int rc = state_check_ids(h, "oww_state_import", "the", stream_ids, n, true)) return rc;
+    if (in_on_device && (reinterpret_cast<uintptr_t>(in) & 15)) return fail(OWW_EINVAL, "oww_state_import: a device buffer must be 16-byte aligned");
+    // every header is checked before anything changes
+    const size_t rb = (size_t)h->st_record_words * 4;
+    std::vector<uint32_t> hdr((size_t)n * ows::kHeaderWords);
+    if (in_on_device) {
+        HIPCHK(hipMemcpy2DAsync(hdr.data(), ows::kHeaderWords * 4, in, rb, ows::kHeaderWords * 4, n, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        for (int i = 0; i < n; ++i) memcpy(&hdr[(size_t)i * ows::kHeaderWords], static_cast<const char*>(in) + (size_t)i * rb, ows::kHeaderWords * 4);
+    }
+    if (int rc = state_check_headers(h, hdr.data(), n)) return rc;
+    std::vector<int> buf;
+    StateList L;
+    state_list_build(h, stream_ids, n, buf, L);
+    if (!in_on_device) if (int rc = state_stage(h, n)) return rc;
+    if (int rc = state_lists_upload(h, buf)) return rc;
+    uint32_t* rec = in_on_device ? static_cast<uint32_t*>(const_cast<void*>(in)) : h->d_st_stage;
+    if (!in_on_device) HIPCHK(copy_async(rec, in, (size_t)n * rb, hipMemcpyHostToDevice, h->stream));
+    if (int rc = state_xfer<true>(h, L, rec)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));           // the host list and a host buffer were copy sources
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_move_streams(oww_ctx* h, const int32_t* src, const int32_t* dst, int32_t n) {
+    OWW_GUARD_BEGIN
+    OWW_STATE_ENTER("oww_move_streams")
+    if (n < 0 || (n > 0 && (!src || !dst))) return fail(OWW_EINVAL, "oww_move_streams: bad argument");
+    if (n == 0) return OWW_OK;
+    if (int rc = state_check_ids(h, "oww_move_streams", "source", src, n, false)) return rc;
+    if (int rc = state_check_ids(h, "oww_move_streams", "destination", dst, n, true)) return rc;
+    std::vector<int> buf;
+    StateList Ls, Ld;
+    state_list_build(h, src, n, buf, Ls);
+    state_list_build(h, dst, n, buf, Ld);
+    if (int rc = state_stage(h, n)) return rc;
+    if (int rc = state_lists_upload(h, buf)) return rc;
+    // every read happens before any write: gather all sources into the staging records, then scatter them
+    if (int rc = state_xfer<false>(h, Ls, h->d_st_stage)) return rc;
+    if (int rc = state_xfer<true>(h, Ld, h->d_st_stage)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));           // also: no queued step still reads the routing table or the verifier list
+    // what the library keeps per stream on the host travels too: subscriptions and verifier assignments leave the source slot (a
+    // source that is nobody's destination is left empty / at the default) and arrive at the destination; one rebuild per table
+    if (h->bank_K == 0 && h->vpool_cap == 0) return OWW_OK;
+    std::vector<int32_t> dsorted(dst, dst + n);
+    std::sort(dsorted.begin(), dsorted.end());
+    auto travel = [&](auto& tab, int width, auto empty) -> bool {
+        if (width == 0 || tab.empty()) return false;
+        const auto old = tab;
+        for (int i = 0; i < n; ++i)
+            if (!std::binary_search(dsorted.begin(), dsorted.end(), src[i]))
+                for (int k = 0; k < width; ++k) tab[(size_t)src[i] * width + k] = empty;
+        for (int i = 0; i < n; ++i)
+            for (int k = 0; k < width; ++k) tab[(size_t)dst[i] * width + k] = old[(size_t)src[i] * width + k];
+        return tab != old;
+    };
+    if (h->bank_K > 0 && travel(h->bank_sub, h->bank_K, -1)) {
+        HIPCHK(copy_sync(h->d_bank_sub, h->bank_sub.data(), h->bank_sub.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (int rc = bank_route(h)) return rc;           // (a moved slot does not restart: its ring and counter came with the record)
+    }
+    if (h->vpool_cap > 0) {
+        bool ch = travel(h->vasg_fix, h->NL, (int)OWW_VERIFIER_DEFAULT);
+        ch = travel(h->vthr_fix, h->NL, 0.f) || ch;
+        ch = travel(h->vasg_bank, h->bank_K, (int)OWW_VERIFIER_DEFAULT) || ch;
+        ch = travel(h->vthr_bank, h->bank_K, 0.f) || ch;
+        if (ch) {
+            h->vasg_n = 0;
+            for (const auto* tab : {&h->vasg_fix, &h->vasg_bank}) for (int v : *tab) h->vasg_n += v != OWW_VERIFIER_DEFAULT;
+            if (int rc = sv_rebuild(h)) return rc;
+        }
+    }
     return OWW_OK;
     OWW_GUARD_END
 }

@@ -504,6 +504,51 @@ class StreamEngine:
         return {"tiles": [int(info[0]), int(info[3])], "waves_per_tile": [int(info[1]), int(info[4])],
                 "entries": [int(info[2]), int(info[5])], "weight_bytes": float(wb.value)}
 
+    # ---- stream state records (include/owwhip.h: oww_state_*, oww_move_streams) ----
+    def state_info(self) -> Tuple[int, int]:
+        """(bytes of one stream state record, 64-bit fingerprint of what a record's bits depend on)."""
+        nb, fp = C.c_size_t(0), C.c_uint64(0)
+        _lib.check(self._lib.oww_state_info(self._h, C.byref(nb), C.byref(fp)))
+        return int(nb.value), int(fp.value)
+
+    def export_state(self, stream_ids: Sequence[int], out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Records of the listed streams -> uint8 [n, record_bytes] (host, complete on return)."""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32).ravel()
+        nb = self.state_info()[0]
+        if out is None:
+            out = np.empty((ids.size, nb), dtype=np.uint8)
+        elif out.dtype != np.uint8 or out.shape != (ids.size, nb) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous uint8 [{ids.size}, {nb}] array")
+        _lib.check(self._lib.oww_state_export(self._h, _ptr(ids), ids.size, _ptr(out), 0))
+        return out
+
+    def import_state(self, stream_ids: Sequence[int], records: np.ndarray) -> None:
+        """Put records (export_state of a handle with the same fingerprint) into the listed streams."""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32).ravel()
+        rec = np.ascontiguousarray(records)
+        if rec.dtype != np.uint8 or rec.ndim != 2 or rec.shape[0] != ids.size:
+            raise ValueError(f"records must be uint8 [{ids.size}, record_bytes], got {rec.dtype} {rec.shape}")
+        nb = self.state_info()[0]
+        if rec.shape[1] != nb:
+            raise ValueError(f"records are {rec.shape[1]} bytes each, this handle's records have {nb}")
+        _lib.check(self._lib.oww_state_import(self._h, _ptr(ids), ids.size, _ptr(rec), 0))
+
+    def export_state_device(self, stream_ids: Sequence[int], out_dev_ptr: int) -> None:
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32).ravel()
+        _lib.check(self._lib.oww_state_export(self._h, _ptr(ids), ids.size, C.c_void_p(out_dev_ptr), 1))
+
+    def import_state_device(self, stream_ids: Sequence[int], in_dev_ptr: int) -> None:
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32).ravel()
+        _lib.check(self._lib.oww_state_import(self._h, _ptr(ids), ids.size, C.c_void_p(in_dev_ptr), 1))
+
+    def move_streams(self, src: Sequence[int], dst: Sequence[int]) -> None:
+        """Stream src[i] becomes stream dst[i], with every bit of its state, its subscriptions and its verifier assignments."""
+        s = np.ascontiguousarray(src, dtype=np.int32).ravel()
+        d = np.ascontiguousarray(dst, dtype=np.int32).ravel()
+        if s.size != d.size:
+            raise ValueError(f"src and dst must have the same length ({s.size} != {d.size})")
+        _lib.check(self._lib.oww_move_streams(self._h, _ptr(s), _ptr(d), s.size))
+
     def sync(self):
         _lib.check(self._lib.oww_sync(self._h))
 

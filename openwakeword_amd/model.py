@@ -724,6 +724,45 @@ class BatchedModel:
         collect_batch (an empty slot reads 0.0)."""
         return self.engine.bank_scores()
 
+    # ---- stream state records: a live stream's state as a portable record (include/owwhip.h: oww_state_*, oww_move_streams) ----
+    def _stream_ids(self, ids, what: str = "stream_ids") -> np.ndarray:
+        a = np.asarray(ids)
+        if a.ndim != 1 or a.dtype.kind not in "iu":
+            raise ValueError(f"{what} must be a 1-D integer sequence")
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= self.n_streams):
+            raise ValueError(f"stream ids must lie in 0 .. {self.n_streams - 1}")
+        return a
+
+    def export_streams(self, stream_ids: Sequence[int]) -> np.ndarray:
+        """uint8 [len(stream_ids), record_bytes]: everything the listed streams' future scores depend on (in the reference: the
+        stream's Model object, model.py:226-230, utils.py:163-171).  Records are only meaningful to a BatchedModel with the same
+        kernel family, ring sizes, bank slots, VAD and weights (engine.state_info's fingerprint; import refuses any other)."""
+        return self.engine.export_state(self._stream_ids(stream_ids))
+
+    def import_streams(self, stream_ids: Sequence[int], records: np.ndarray) -> None:
+        """Put exported records into the listed streams: each continues bit for bit where its source stopped.  Subscriptions and
+        verifier assignments are not part of a record: subscribe() first (which restarts the slot), then import."""
+        ids = self._stream_ids(stream_ids)
+        if not isinstance(records, np.ndarray) or records.dtype != np.uint8:
+            raise ValueError(f"records must be a uint8 array (export_streams), got {getattr(records, 'dtype', type(records).__name__)}")
+        nb = self.engine.state_info()[0]
+        if records.ndim != 2 or records.shape != (ids.size, nb):
+            raise ValueError(f"records must have shape ({ids.size}, {nb}), got {records.shape}")
+        if np.unique(ids).size != ids.size:
+            raise ValueError("stream_ids holds a stream twice")
+        self.engine.import_state(ids, records)
+
+    def move_streams(self, src: Sequence[int], dst: Sequence[int]) -> None:
+        """Stream src[i] becomes stream dst[i] inside this model: state, bank subscriptions and verifier assignments travel; swaps,
+        cycles and chains are legal (all reads happen before any write), `dst` holds no duplicates.  Source slots that are nobody's
+        destination keep their device state (reset() them when they are reused) and end up unsubscribed."""
+        s, d = self._stream_ids(src, "src"), self._stream_ids(dst, "dst")
+        if s.size != d.size:
+            raise ValueError(f"src and dst must have the same length ({s.size} != {d.size})")
+        if np.unique(d).size != d.size:
+            raise ValueError("dst holds a stream twice")
+        self.engine.move_streams(s, d)
+
     def reset(self, stream_ids: Optional[Sequence[int]] = None, init_features: Optional[np.ndarray] = None,
               reset_vad: bool = False):
         """Model.reset for the listed streams (None = all).  Like the reference (model.py:226-230) this leaves the VAD state

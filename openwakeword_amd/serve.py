@@ -126,6 +126,43 @@ class SlotAllocator:
     def key_of(self, slot: int):
         return self._tag.get(slot // self.group)
 
+    def plan_compaction(self, max_moves: Optional[int] = None):
+        """Moves that repair placement after clients have come and gone: per cohort key, the sparsest blocks are emptied into the
+        free slots of the fullest blocks of the SAME key (keys are never mixed), until the key's streams sit in as few blocks as
+        they fit in (ceil(used / group) when every block holds `group` slots) or `max_moves` moves are planned.  Returns
+        (src, dst) int32 arrays for `BatchedModel.move_streams(src, dst)`: every src slot is in use and every dst slot free when
+        the call is made, no slot appears twice.  The allocator's own tables are updated as if the moves had happened (an
+        emptied block loses its tag and is fresh again), so the caller must carry them out -- and re-point its connections --
+        before it allocates or releases again.  Pure bookkeeping, no device work."""
+        budget = self.n_slots if max_moves is None else max(0, int(max_moves))
+        src: List[int] = []
+        dst: List[int] = []
+        by_key: Dict[object, List[int]] = {}
+        for b, key in self._tag.items():
+            by_key.setdefault(key, []).append(b)
+        for key, blocks in by_key.items():
+            used = {b: len(self._block_slots(b)) - len(self._free[b]) for b in blocks}
+            order = sorted(blocks, key=lambda b: (used[b], -b))          # sparsest first; among equals the highest block donates
+            lo, hi = 0, len(order) - 1
+            while lo < hi and budget > 0:
+                donor, taker = order[lo], order[hi]
+                if not self._free[taker]:
+                    hi -= 1
+                    continue
+                free = set(self._free[donor])
+                s = next(x for x in self._block_slots(donor) if x not in free)       # (descending: the donor's highest used slot)
+                d = self._free[taker].pop()                                          # the taker's lowest free slot
+                if not self._free[taker]:
+                    self._open[key].remove(taker)
+                self.n_used += 1
+                self.release(s)
+                src.append(s)
+                dst.append(d)
+                budget -= 1
+                if donor not in self._tag:                                           # emptied: fresh again
+                    lo += 1
+        return np.asarray(src, dtype=np.int32), np.asarray(dst, dtype=np.int32)
+
 
 N_PHASE_BINS = 8
 
