@@ -1210,6 +1210,7 @@ int launch_vad(oww_ctx* h, const StepArgs& a, const int16_t* d_pcm, int n_sample
         owv::VadLstmParams p{};
         p.xin = h->d_vadx; p.hc = h->d_vadhc; p.w = h->d_vad_lstmw; p.bias = h->d_vad_lstmb; p.wd = h->d_vad_wd; p.bd = h->vad_bd;
         p.ring = h->d_vadring; p.n_vad = h->d_nvad; p.last = h->d_vadlast; p.S = h->S; p.n_groups = G; p.stream_on = a.on;
+        p.range_flag = h->d_range;
         if (a.lists) { p.glist = a.gl[4]; p.n_groups = a.gn[4]; }
         Timed t(h, 9);
         hipLaunchKernelGGL(owv::vad_lstm_kernel, dim3((p.n_groups + owv::L_WG - 1) / owv::L_WG), dim3(64 * owv::L_WG), 0, h->stream, p);

@@ -292,6 +292,7 @@ struct VadLstmParams {
     int S, n_groups;
     const uint8_t* stream_on;   // see VadFrontParams::stream_on
     const int* glist;           // see owr::RStageParams::glist (groups of 16 streams)
+    int* range_flag;            // owh::raise_range_flag: an encoder output (or an imported h) beyond the f16 range
 };
 
 constexpr int L_WG = 4;                       // waves per workgroup: they share one weight chunk stream
@@ -328,6 +329,7 @@ __global__ __launch_bounds__(64 * L_WG, 2) void vad_lstm_kernel(VadLstmParams p)
         owh::to_ops<4>(hf[l], H[l]);
     }
     float yacc = 0.f;
+    lanemask_t bad = 0;
     chunk_sync();
 #pragma unroll 1
     for (int bt = 0; bt < 4; ++bt) {
@@ -364,6 +366,10 @@ __global__ __launch_bounds__(64 * L_WG, 2) void vad_lstm_kernel(VadLstmParams p)
                     }
                     chunk_sync();
                 }
+                // this kernel is the consumer of the encoder's fp32 output tiles: a value there beyond the f16 range splits into
+                // inf / -inf, every gate accumulator of that stream turns NaN and NaN h, c would go back to the state in silence
+                // (owh::nan_guard: one accumulator per layer and time step sees it, whichever input channel it came from)
+                if (u == 0) owh::nan_guard(bad, acc[0][0]);
                 // gates of hidden units 16u + 4j + e (register e): i, f, g, o = acc[0..3]
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -392,7 +398,8 @@ __global__ __launch_bounds__(64 * L_WG, 2) void vad_lstm_kernel(VadLstmParams p)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // drain the chunk prefetched after the last one
     const int s = g * 16 + pos;
-    if (active && s < p.S && (p.stream_on == nullptr || p.stream_on[s] != 0)) {      // per lane: position = stream
+    const bool mine = active && s < p.S && (p.stream_on == nullptr || p.stream_on[s] != 0);
+    if (mine) {                                                                      // per lane: position = stream
 #pragma unroll
         for (int l = 0; l < 2; ++l) {
             store_tile<4>(hf[l], hc + (2 * l) * 1024, lane);
@@ -406,6 +413,8 @@ __global__ __launch_bounds__(64 * L_WG, 2) void vad_lstm_kernel(VadLstmParams p)
             p.last[s] = score;
         }
     }
+    // only the lanes that store: a stream that sits the step out (stale input tile) or a spare wave raises nothing
+    owh::raise_range_flag(bad & __ballot(mine), p.range_flag, g * 16, 16);
 }
 
 // zero the recurrent state / score ring of the listed streams (ids == nullptr: streams [0, n))
