@@ -448,13 +448,74 @@ const float* parse_dense_net(const float* q, int T, int hidden, int n_out, int h
 // units: examples/custom_model.yml:89).  Every matrix on its own power-of-two scale (hx_weight_exp), undone on the fp32 accumulators.
 struct HxNetPack {
     int e1 = 0, e2 = 0, e3 = 0;           // scales of w1 / w2 / w3 (wide form)
+    int eh = 0;                           // narrow form: scale of the hidden vector between layer 1 and layer 2 (hx_hidden_exp)
     size_t w2 = 0, w3 = 0, pad = 0;       // where pack_hx_net put the pieces, floats from the start of the image
 };
-// the scales of a net's matrices; false when a weight is not finite
-bool hx_net_scales(const NetHost& n, int ht, HxNetPack& p) {
+
+// Up to 64 windows of the commit's probe embeddings (probe_emb [nb * 16 frames][32 probes][96]) as a head of T rows sees them: window w
+// belongs to probe w % 32 of batch w / 32 and ends on the batch's last frame; rows before the batch's first frame stay 0.  What
+// oww_bank_add's self-test scores and what hx_hidden_exp measures.  -> number of windows (>= 1; all zero without probes)
+int probe_windows(const std::vector<float>& probe_emb, int probe_nb, int T, std::vector<float>& win) {
+    const int NP = 32, CT = 16;
+    const int B = std::min(64, std::max(1, probe_nb) * NP);      // (64 windows: ~10 ms of float64 per head)
+    win.assign((size_t)B * T * 96, 0.f);
+    for (int w = 0; w < B && !probe_emb.empty(); ++w) {
+        const int bt0 = (w / NP) * CT, pr = w % NP;
+        for (int r = 0; r < T; ++r) {
+            const int fr = CT - T + r;
+            if (fr < 0) continue;
+            memcpy(&win[((size_t)w * T + r) * 96], &probe_emb[(((size_t)bt0 + fr) * NP + pr) * 96], 96 * sizeof(float));
+        }
+    }
+    return B;
+}
+
+// The narrow form (ht 4) hands its hidden vector relu(ln1(W1 x + b1)) to the second GEMM through the f16 hi / lo split with no scale
+// applied in the kernel, and nothing in a net bounds that vector: ln1's gamma / beta set its magnitude, or W1, b1 and the audio where
+// there is no LayerNorm.  Units of order 1e-4 lose the low halves of their split to the f16 subnormal grid, units beyond 65504 leave
+// the range (tests/test_head_regimes.py: ln1_cold, noln_cold, noln_hot).  ReLU commutes with a positive power of two, so the scale is
+// folded into the weights on the host: 2^eh into ln1's gamma and beta (without LayerNorm: into u1 and b1), 2^-eh into u2 -- exact,
+// and the kernels do not change.  eh puts the largest hidden unit over the probe windows at 2^9 .. 2^10, where oww_commit puts the
+// largest probe embedding (hx_efeat): the same factor 64 below the f16 overflow.  float64 on the host, once per net; 0 without probes
+// or when no unit is ever positive.  The wide form scales each stream's vector in the kernel (owh::scale_own) and needs none.
+int hx_hidden_exp(const NetHost& n, const std::vector<float>& probe_emb, int probe_nb) {
+    if (probe_emb.empty()) return 0;
+    const size_t K = (size_t)n.T * 96, H = n.hidden;
+    std::vector<float> win;
+    const int B = probe_windows(probe_emb, probe_nb, n.T, win);
+    std::vector<double> a(H);
+    double mx = 0.0;
+    for (int w = 0; w < B; ++w) {
+        const float* x = &win[(size_t)w * K];
+        for (size_t j = 0; j < H; ++j) a[j] = n.b1[j];
+        for (size_t k = 0; k < K; ++k) {
+            const double xv = x[k];
+            const float* wr = n.w1 + k * H;
+            for (size_t j = 0; j < H; ++j) a[j] += xv * wr[j];
+        }
+        if (n.has_ln) {
+            double mu = 0.0, var = 0.0;
+            for (size_t j = 0; j < H; ++j) mu += a[j];
+            mu /= (double)H;
+            for (size_t j = 0; j < H; ++j) var += (a[j] - mu) * (a[j] - mu);
+            const double rs = 1.0 / std::sqrt(var / (double)H + 1e-5);
+            for (size_t j = 0; j < H; ++j) a[j] = (a[j] - mu) * rs * n.ln1g[j] + n.ln1b[j];
+        }
+        for (size_t j = 0; j < H; ++j) if (a[j] > mx) mx = a[j];
+    }
+    if (!(mx > 0.0) || !std::isfinite(mx)) return 0;
+    int e2 = 0;
+    std::frexp(mx, &e2);                                   // mx = f 2^e2, f in [0.5, 1)
+    return std::min(60, std::max(-60, 10 - e2));
+}
+
+// the scales of a net's matrices and, narrow form, of its hidden vector; false when a weight is not finite
+bool hx_net_scales(const NetHost& n, int ht, HxNetPack& p, const std::vector<float>& probe_emb, int probe_nb) {
     const size_t K = (size_t)n.T * 96, H = n.hidden;
     p.e1 = hx_weight_exp(n.w1, K * H); p.e2 = hx_weight_exp(n.w2, H * H); p.e3 = ht == 8 ? hx_weight_exp(n.w3, H * n.n_out) : 0;
-    return p.e1 != -1000 && p.e2 != -1000 && p.e3 != -1000;
+    if (p.e1 == -1000 || p.e2 == -1000 || p.e3 == -1000) return false;
+    p.eh = ht == 4 ? hx_hidden_exp(n, probe_emb, probe_nb) : 0;
+    return true;
 }
 
 // First layer: the net's w1[K][H] into columns [c0, c0 + H) of a zeroed [K][NH] matrix (its columns up to c0 + HP stay zero), 2^e1 as
@@ -468,7 +529,7 @@ void place_w1(const NetHost& n, int c0, int HP, int NH, int e1, std::vector<floa
 // Everything behind the first layer, appended to the image in this order: w2 zero-padded to [HP][HP]; in the wide form the output layer
 // as a third split matrix [HP][16] (outputs n_out .. 15 zero); the pad block -- b1, ln1 g / b, b2, ln2 g / b and, in the narrow form, w3
 // at a stride of HP floats, then b3: 16 floats in the wide form, 4 in the narrow form where b3_in_pad (bank heads), none otherwise
-// (the kernel reads a fixed narrow net's b3 from the net's natural array).
+// (the kernel reads a fixed narrow net's b3 from the net's natural array).  Narrow form: 2^eh folded into ln1 g / b, or into b1.
 void pack_hx_net(const NetHost& n, int ht, bool b3_in_pad, HostBuf& hb, HxNetPack& p) {
     const size_t HP = 16 * (size_t)ht, H = n.hidden, O = n.n_out;
     std::vector<float> pk;
@@ -486,6 +547,10 @@ void pack_hx_net(const NetHost& n, int ht, bool b3_in_pad, HostBuf& hb, HxNetPac
     std::vector<float> pad(n_arr * HP + n_b3, 0.f);
     const float* src[7] = {n.b1, n.ln1g, n.ln1b, n.b2, n.ln2g, n.ln2b, n.w3};
     for (size_t a = 0; a < n_arr; ++a) if (src[a]) memcpy(&pad[a * HP], src[a], H * sizeof(float));
+    if (p.eh != 0) {                      // the hidden vector's scale (hx_hidden_exp): ln1 g and b, or b1 (with u1: make_hx_net)
+        if (n.has_ln) for (size_t i = HP; i < 3 * HP; ++i) pad[i] = std::ldexp(pad[i], p.eh);
+        else for (size_t i = 0; i < HP; ++i) pad[i] = std::ldexp(pad[i], p.eh);
+    }
     if (n_b3) memcpy(&pad[n_arr * HP], n.b3, O * sizeof(float));
     p.pad = hb.add(pad);
 }
@@ -500,7 +565,7 @@ owh::HeadHxNet make_hx_net(const NetHost& n, int ht, const HxNetPack& p, const f
     else { o.b3 = pd + 6 * HP; o.w3hx = img + p.w3; o.u3 = std::ldexp(1.0f, -p.e3); }
     o.has_ln = n.has_ln; o.role = n.role; o.head = n.head; o.out_col = n.out_col;
     o.hidden = n.hidden; o.inv_hidden = 1.0f / (float)n.hidden;
-    o.u1 = std::ldexp(1.0f, -(hx_efeat + p.e1)); o.u2 = std::ldexp(1.0f, -p.e2);
+    o.u1 = std::ldexp(1.0f, -(hx_efeat + p.e1) + (n.has_ln ? 0 : p.eh)); o.u2 = std::ldexp(1.0f, -(p.e2 + p.eh));
     o.n_out = n.n_out; o.final_act = n.final_act;
     return o;
 }
@@ -1990,7 +2055,7 @@ int pack_head_nets(oww_ctx* h, HostBuf& hb, WeightOff& off) {
         go.net.resize(g.n_nets);
         for (int gi = 0; gi < g.n_nets; ++gi) {
             const NetHost& n = h->nets[g.nets[gi]];
-            if (h->hx && !hx_net_scales(n, g.ht, go.net[gi])) return fail(OWW_EINVAL, "head weights are not finite");
+            if (h->hx && !hx_net_scales(n, g.ht, go.net[gi], h->probe_emb, h->probe_nb)) return fail(OWW_EINVAL, "head weights are not finite");
             place_w1(n, HP * gi, HP, g.NH, go.net[gi].e1, wcat, colmul);
         }
         if (g.ht == 4) {
@@ -2603,6 +2668,7 @@ int oww_commit(oww_ctx* h) {
     HxCalib cal;
     if (h->hx) {
         if (int rc = calibrate_hx(h, cal)) return rc;
+        h->probe_emb = cal.ref_emb; h->probe_nb = cal.nb;                  // (hx_hidden_exp's and oww_bank_add's self-test inputs)
         clk.lap("calibration (total)");
         if (getenv("OWW_DEBUG_CALIB"))
             for (int l = 0; l < 20; ++l) fprintf(stderr, "calib layer %2d: max|a| %-12.5g e_in %4d e_out %4d\n", l, h->hx_absmax[l], h->hx_ein[l], h->hx_e[l]);
@@ -2629,7 +2695,6 @@ int oww_commit(oww_ctx* h) {
     clk.lap("state allocation");
     // ---- reset state, then reset all ----
     if (int rc = derive_reset_state(h, cal, clk)) return rc;
-    if (h->hx) { h->probe_emb = cal.ref_emb; h->probe_nb = cal.nb; }      // (oww_bank_add's self-test inputs)
     if (h->bank_K > 0) if (int rc = alloc_bank(h)) return rc;
     if (h->vpool_cap > 0) if (int rc = alloc_verifiers(h)) return rc;
     h->committed = true;
@@ -3394,7 +3459,7 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
     parse_dense_net(q, T, H, 1, has_ln, 1, net);
     const int ht = H <= 64 ? 4 : 8, HP = 16 * ht;
     HxNetPack pack;
-    if (!hx_net_scales(net, ht, pack)) return fail(OWW_EINVAL, "oww_bank_add: head weights are not finite");
+    if (!hx_net_scales(net, ht, pack, h->probe_emb, h->probe_nb)) return fail(OWW_EINVAL, "oww_bank_add: head weights are not finite");
     HostBuf hb;
     std::vector<float> wcat(K * HP, 0.f), pk;
     std::vector<double> colmul(HP);
@@ -3414,17 +3479,8 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
     dv.net = make_hx_net(net, ht, pack, d_img, nullptr, h->hx_efeat);
     // ---- self-test: the routed kernel on windows of the commit's probe embeddings against float64, the tolerance oww_commit holds
     //      fixed heads to (1e-3)
-    const int NP = 32, CT = 16;
-    const int B = std::min(64, std::max(1, h->probe_nb) * NP);      // (64 windows: ~10 ms of float64 per head)
-    std::vector<float> win((size_t)B * K, 0.f);
-    for (int w = 0; w < B && !h->probe_emb.empty(); ++w) {
-        const int bt0 = (w / NP) * CT, pr = w % NP;
-        for (int r = 0; r < T; ++r) {
-            const int fr = CT - T + r;                  // window ends on the batch's last frame; rows before its first frame stay 0
-            if (fr < 0) continue;
-            memcpy(&win[((size_t)w * T + r) * 96], &h->probe_emb[(((size_t)bt0 + fr) * NP + pr) * 96], 96 * sizeof(float));
-        }
-    }
+    std::vector<float> win;
+    const int B = probe_windows(h->probe_emb, h->probe_nb, T, win);
     float *d_win = nullptr, *d_out = nullptr; int* d_ent = nullptr; owh::BankTile* d_til = nullptr; owh::BankHeadDev* d_hd = nullptr;
     std::vector<int> ent(B);
     for (int i = 0; i < B; ++i) ent[i] = i;
