@@ -3112,7 +3112,9 @@ int oww_resample(oww_ctx* h, const int16_t* in, int in_on_device, int32_t n_in, 
                  int16_t* out, int out_on_device, int32_t n_out) {
     OWW_GUARD_BEGIN
     if (!h || !h->committed) return fail(OWW_ESTATE, "oww_resample: handle not committed");
-    if (!in || !out || !taps) return fail(OWW_EINVAL, "oww_resample: null argument");
+    if (!in) return fail(OWW_EINVAL, "oww_resample: null argument: in");
+    if (!taps) return fail(OWW_EINVAL, "oww_resample: null argument: taps");
+    if (!out) return fail(OWW_EINVAL, "oww_resample: null argument: out");
     if (n_in < 1 || p < 1 || q < 1 || n_taps < 2 || (n_taps & 1) || n_taps > 4096 || q > 65536)
         return fail(OWW_EINVAL, "oww_resample: bad argument (n_in=%d p=%d q=%d n_taps=%d)", n_in, p, q, n_taps);
     if (n_out != (int32_t)(((long long)n_in * q) / p) || n_out < 1)
