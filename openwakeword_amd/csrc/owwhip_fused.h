@@ -215,16 +215,13 @@ __global__ __launch_bounds__(64 * FA_WG, (FA_WG + 3) / 4) void hmelA_kernel(MelA
             for (int n2 = 0; n2 < 8; ++n2) {
                 const int n = 64 * n2 + lane;
                 const float w = s_hann[n];               // (zero outside [56, 456): the table is padded to the frame)
-                re[n2] = w * sx[n];
-                im[n2] = w * sx[160 + n];
+                re[n2] = owk::windowed(w, sx[n]);
+                im[n2] = owk::windowed(w, sx[160 + n]);
             }
             dft8(re, im);
 #pragma unroll
             for (int k = 1; k < 8; ++k) {
-                const float cr = s_tw1[k * 64 + lane], ci = s_tw1[512 + k * 64 + lane];
-                const float r = re[k] * cr - im[k] * ci;
-                im[k] = re[k] * ci + im[k] * cr;
-                re[k] = r;
+                owk::twiddle(re[k], im[k], s_tw1[k * 64 + lane], s_tw1[512 + k * 64 + lane]);
             }
             wave_sync();                         // every lane has read its samples: the planes may be overwritten
 #pragma unroll
@@ -238,10 +235,7 @@ __global__ __launch_bounds__(64 * FA_WG, (FA_WG + 3) / 4) void hmelA_kernel(MelA
             dft8(re, im);
 #pragma unroll
             for (int k = 1; k < 8; ++k) {
-                const float cr = s_tw2[k * 8 + (lane & 7)], ci = s_tw2[64 + k * 8 + (lane & 7)];
-                const float r = re[k] * cr - im[k] * ci;
-                im[k] = re[k] * ci + im[k] * cr;
-                re[k] = r;
+                owk::twiddle(re[k], im[k], s_tw2[k * 8 + (lane & 7)], s_tw2[64 + k * 8 + (lane & 7)]);
             }
             wave_sync();
             {
@@ -271,7 +265,7 @@ __global__ __launch_bounds__(64 * FA_WG, (FA_WG + 3) / 4) void hmelA_kernel(MelA
                 const float zr = xr[k], zi = xi[k], yr = xr[512 - k], yi = xi[512 - k];
                 const float ar = zr + yr, ai = zi - yi;
                 const float br = zi + yi, bi = zr - yr;
-                const float p0 = 0.25f * (ar * ar + ai * ai), p1 = 0.25f * (br * br + bi * bi);
+                const float p0 = owk::quarter_power(ar, ai), p1 = owk::quarter_power(br, bi);
 #if OWF_COMPACT_TAPS
                 const unsigned d = s_dst[i];                  // every FFT bin feeds at most two (neighbouring) triangular filters
                 pw0[d & 0xffffu] = p0; pw0[d >> 16] = p0;

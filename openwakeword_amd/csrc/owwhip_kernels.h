@@ -643,7 +643,14 @@ struct MelParams {
 __device__ __forceinline__ float db10(float p) { return __builtin_amdgcn_logf(fmaxf(p, 1e-10f)) * 3.0102999566398120f; }
 __device__ __forceinline__ float mel_units(float db, float floor_db) { return fmaf(fmaxf(db, floor_db), 0.1f, 2.0f); }
 
+// The mel arithmetic names every fused multiply-add itself and lets the compiler contract nothing (hipcc's default is
+// -ffp-contract=fast).  In a*b + c*d either product may be the fused one, the choice is the optimiser's, and it was not the same in
+// every copy of this code: hmelA_kernel<false> (the production steps) rounded some of these sums the other way round than
+// hmelA_kernel<true> (debug_layers handles) and mel_kernel, so a debug handle's feature ring differed from a production handle's in the
+// last bits (tests/test_cnn_regimes.py::test_debug_and_production_kernels_agree_bit_for_bit; a build with -ffp-contract=off agreed).
+// The operation count is the contracted one: one multiply and one fma per twiddle component, one fma per rotated butterfly output.
 __device__ __forceinline__ void dft8(float* re, float* im) {
+#pragma clang fp contract(off)
     // forward 8-point DFT, natural order in and out
     const float h = 0.70710678118654752440f;
     float a0r = re[0] + re[4], a0i = im[0] + im[4], a1r = re[0] - re[4], a1i = im[0] - im[4];
@@ -656,14 +663,30 @@ __device__ __forceinline__ void dft8(float* re, float* im) {
     float E1r = a1r + a3r, E1i = a1i + a3i, E3r = a1r - a3r, E3i = a1i - a3i;
     float O0r = b0r + b2r, O0i = b0i + b2i, O2r = b0r - b2r, O2i = b0i - b2i;
     float O1r = b1r + b3r, O1i = b1i + b3i, O3r = b1r - b3r, O3i = b1i - b3i;
-    // twiddles W8^k: 1, (1-i)/sqrt2, -i, (-1-i)/sqrt2
-    float T1r = h * (O1r + O1i), T1i = h * (O1i - O1r);
+    // twiddles W8^k: 1, (1-i)/sqrt2, -i, (-1-i)/sqrt2; T1 = h (S1r, S1i), T3 = h (S3r, -S3i), each fused into the sum it enters
+    float S1r = O1r + O1i, S1i = O1i - O1r;
     float T2r = O2i, T2i = -O2r;
-    float T3r = h * (O3i - O3r), T3i = -h * (O3r + O3i);
+    float S3r = O3i - O3r, S3i = O3r + O3i;
     re[0] = E0r + O0r; im[0] = E0i + O0i; re[4] = E0r - O0r; im[4] = E0i - O0i;
-    re[1] = E1r + T1r; im[1] = E1i + T1i; re[5] = E1r - T1r; im[5] = E1i - T1i;
+    re[1] = fmaf(h, S1r, E1r); im[1] = fmaf(h, S1i, E1i); re[5] = fmaf(-h, S1r, E1r); im[5] = fmaf(-h, S1i, E1i);
     re[2] = E2r + T2r; im[2] = E2i + T2i; re[6] = E2r - T2r; im[6] = E2i - T2i;
-    re[3] = E3r + T3r; im[3] = E3i + T3i; re[7] = E3r - T3r; im[7] = E3i - T3i;
+    re[3] = fmaf(h, S3r, E3r); im[3] = fmaf(-h, S3i, E3i); re[7] = fmaf(-h, S3r, E3r); im[7] = fmaf(h, S3i, E3i);
+}
+// (re + i im) * (cr + i ci) and the power |a|^2 / 4 of the two real frames' spectra, with the fused operation of each sum named
+__device__ __forceinline__ void twiddle(float& re, float& im, float cr, float ci) {
+#pragma clang fp contract(off)
+    const float r = fmaf(re, cr, -(im * ci));
+    im = fmaf(re, ci, im * cr);
+    re = r;
+}
+__device__ __forceinline__ float quarter_power(float ar, float ai) {
+#pragma clang fp contract(off)
+    return 0.25f * fmaf(ar, ar, ai * ai);
+}
+// window times sample: a product that enters dft8's first sums unfused
+__device__ __forceinline__ float windowed(float w, float x) {
+#pragma clang fp contract(off)
+    return w * x;
 }
 
 constexpr int MEL_NT = 256;
@@ -778,16 +801,12 @@ __global__ __launch_bounds__(MEL_NT) void mel_kernel(MelParams p) {
                 const int n = 64 * n2 + lane;
                 const bool in = (n >= 56) && (n < 456);
                 const float w = in ? s_hann[in ? n - 56 : 0] : 0.f;
-                re[n2] = w * sx[n];
-                im[n2] = w * sx[160 + n];
+                re[n2] = windowed(w, sx[n]);
+                im[n2] = windowed(w, sx[160 + n]);
             }
             dft8(re, im);
 #pragma unroll
-            for (int k = 1; k < 8; ++k) {
-                const float r = re[k] * tw1r[k] - im[k] * tw1i[k];
-                im[k] = re[k] * tw1i[k] + im[k] * tw1r[k];
-                re[k] = r;
-            }
+            for (int k = 1; k < 8; ++k) twiddle(re[k], im[k], tw1r[k], tw1i[k]);
 #pragma unroll
             for (int k = 0; k < 8; ++k) { xr[k * 72 + lane] = re[k]; xi[k * 72 + lane] = im[k]; }
             wave_sync();
@@ -798,11 +817,7 @@ __global__ __launch_bounds__(MEL_NT) void mel_kernel(MelParams p) {
             }
             dft8(re, im);
 #pragma unroll
-            for (int k = 1; k < 8; ++k) {
-                const float r = re[k] * tw2r[k] - im[k] * tw2i[k];
-                im[k] = re[k] * tw2i[k] + im[k] * tw2r[k];
-                re[k] = r;
-            }
+            for (int k = 1; k < 8; ++k) twiddle(re[k], im[k], tw2r[k], tw2i[k]);
             wave_sync();
             {
                 const int q = lane >> 3, m0 = lane & 7;
@@ -828,8 +843,8 @@ __global__ __launch_bounds__(MEL_NT) void mel_kernel(MelParams p) {
                 const float zr = xr[k], zi = xi[k], yr = xr[512 - k], yi = xi[512 - k];
                 const float ar = zr + yr, ai = zi - yi;        // 2*A[k]
                 const float br = zi + yi, bi = zr - yr;        // 2*|B[k]| components
-                pw0[i] = 0.25f * (ar * ar + ai * ai);
-                pw1[i] = 0.25f * (br * br + bi * bi);
+                pw0[i] = quarter_power(ar, ai);
+                pw1[i] = quarter_power(br, bi);
             }
             wave_sync();
             // ---- mel + log: thread (fr, mbin), frames of its own wave
