@@ -19,6 +19,7 @@
 #pragma once
 #include <type_traits>
 #include <utility>
+#include "owwhip_layout.h"
 #include "owwhip_rr.h"
 
 namespace owh {
@@ -26,7 +27,6 @@ namespace owh {
 using owr::f32x4;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-constexpr float WSCALE = 256.0f;            // heads / VAD: weights are stored as f16 halves of 2^8 * w
 constexpr float WUNSCALE = 1.0f / 256.0f;
 
 // BatchNorm in the f16-split family is FOLDED: the per-channel scale (sign included) goes into the f16-split weights, the shift is
@@ -162,9 +162,6 @@ __device__ __forceinline__ Op split_some(const f32x4 a, const f32x4 b) {
 //      .h = (xh pairs 0, 1 |  0,  0)             against weights (wl | 0):   xh wl
 // i.e. two MFMAs for that k-step instead of three (pack_hx(..., rem2) packs the weight blocks accordingly).  Stage B: 5 instead of 6
 // MFMAs per tap, output tile and position tile in its three 48-channel-input layers (756 -> 648 per stream-step).
-#ifndef OWH_REM2
-#define OWH_REM2 1
-#endif
 __device__ __forceinline__ Op split_dup(const f32x4 a) {
     typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -230,10 +227,6 @@ __device__ __forceinline__ void store_tile_h(const f32x4 (&t)[NCT], float* __res
 // DPP bound_ctrl zero-fills them and no select is needed (5.3 -> 2.5 VALU per value in the tap combine of stages C, D, E).
 // Everything that maps a lane to a (stream, mel position) goes through tile_stream / tile_mel: the pooled hand-over stores, the
 // per-lane participation mask, the debug dump, and owk::reset_kernel on the host side (owh::kInterleave).
-#ifndef OWH_INTERLEAVE
-#define OWH_INTERLEAVE 1
-#endif
-constexpr bool kInterleave = OWH_INTERLEAVE != 0;
 template <int F> __device__ __forceinline__ int tile_stream(int pos) { return kInterleave ? pos % (16 / F) : pos / F; }
 template <int F> __device__ __forceinline__ int tile_mel(int pos) { return kInterleave ? pos / (16 / F) : pos % F; }
 template <int F> __device__ __forceinline__ int tile_pos(int stream, int mel) { return kInterleave ? mel * (16 / F) + stream : stream * F + mel; }
@@ -298,9 +291,6 @@ __device__ __forceinline__ f16x8 lds_h(const float* buf, int blk, int lane) {
 #endif
 #ifndef OWH_WPS_B
 #define OWH_WPS_B 3
-#endif
-#ifndef OWH_WPS_C
-#define OWH_WPS_C 2
 #endif
 #ifndef OWH_WPS_D
 #define OWH_WPS_D 2
@@ -542,15 +532,9 @@ __device__ __forceinline__ void conv_mel_hx(const Op (&in)[NT][KSI], f32x4 (&out
 // positions p-1, p, p+1 in dwords 0, 1, 2 (two DPP row shifts per tile and part, done once per layer: the operand is the same for
 // every output tile; interleaved position order, so the shifts zero-fill the stream edges themselves).  7 instead of 9 k-steps per
 // output tile; the weights come in pack_hx_tm order (same pair index = tap rule as the time layers).
-#ifndef OWH_KMERGE_MEL
-#define OWH_KMERGE_MEL 1
-#endif
 // NPR = operand dwords (f16 pairs) of the remainder tile per lane: 1 for a half tile (72 = 64 + 8), 2 for a full one (48 = 32 + 16: the
 // three taps' 16-channel remainders fill 2 k-steps instead of 3; 8 more operand registers per tile, so only where the budget has them:
 // layer a of stage C, OWH_KMERGE_MEL2)
-#ifndef OWH_KMERGE_MEL2
-#define OWH_KMERGE_MEL2 1
-#endif
 template <int KSI, int NT, int F, int NPR>
 __device__ __forceinline__ void merge_mel_rems(const Op (&in)[NT][KSI], Op (&M)[NT][(3 * NPR + 3) / 4]) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -754,13 +738,6 @@ __device__ __forceinline__ void conv_time_hx(const Op (&h0)[KSI], const Op (&h1)
 // pair index = tap * NPR + v  (NPR = pairs per remainder tile: 2, or 1 for a half tile); pack_hx_tm (owwhip.hip) packs the weights
 // in the same order.  The 1x3 (mel) layers keep one accumulator chain per tap and cannot merge.
 // ------------------------------------------------------------------------------------------------
-#ifndef OWH_KMERGE
-#define OWH_KMERGE 1
-#endif
-#ifndef OWH_KMERGE_B
-#define OWH_KMERGE_B 0     // stage B too (48 = 32 + 16 channels: 2 merged k-steps per OUTPUT row cost 16 more registers than the 6 source
-                           // rows' separate remainder k-steps -> spills at 3 waves per SIMD); stage C (72 = 64 + 8) always
-#endif
 template <int NCT, bool HALF> struct TimeK {
     static constexpr int KSF = NCT / 2;                         // full k-steps per tap
     static constexpr int NPR = NCT % 2 ? (HALF ? 1 : 2) : 0;    // f16 pairs of the remainder tile
@@ -894,9 +871,6 @@ __device__ __forceinline__ void conv_time_hxm(const Op (&h0)[KSF], const Op (&h1
 // ------------------------------------------------------------------------------------------------
 // stages B..E (parameters, geometry and memory layouts: owr::RStageParams / owr::RCfg, channel tiles NOT re-packed)
 // ------------------------------------------------------------------------------------------------
-#ifndef OWH_KMERGE_MEL2B
-#define OWH_KMERGE_MEL2B 0     // layer c of stage B (48 -> 48) in the same form: see DESIGN.md 5.2 for the measurement
-#endif
 #ifndef OWH_HIST_LDS
 #define OWH_HIST_LDS 1
 #endif

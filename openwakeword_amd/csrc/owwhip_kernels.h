@@ -25,6 +25,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "owwhip_layout.h"
 
 namespace owk {
 
@@ -1174,7 +1175,7 @@ __global__ __launch_bounds__(64 * WAVES, SPW >= 16 ? 2 : 1) void heads_generic_k
 // of them and backward for ONE step only -- out[:, -1] of the reverse direction is its first step, from a zero state.
 // LDS (dynamic): [SPW] x (T x 96 features + T x 128 layer-0 outputs + 64 hidden + 128 last + 8 outputs).
 // ------------------------------------------------------------------------------------------------
-constexpr int RNN_H = 64, RNN_SPW = 2, RNN_TMAX = 64;
+constexpr int RNN_SPW = 2;                 // (RNN_H, RNN_TMAX: owwhip_layout.h)
 inline size_t rnn_lds_bytes(int T) { return (size_t)RNN_SPW * ((size_t)T * (96 + 128) + 64 + 128 + 8) * sizeof(float); }
 
 __device__ __forceinline__ float sigm(float v) { return 1.0f / (1.0f + expf(-v)); }
@@ -1314,8 +1315,7 @@ __global__ __launch_bounds__(64) void heads_rnn_kernel(HeadParams p, int ni) {
 // fast path: every net of the group has hidden == 64, n_out == 1, sigmoid, the same T.
 constexpr int HD_SB = 32;          // streams per workgroup
 constexpr int HD_NW = 8;
-constexpr int HD_NT = HD_NW * 64;
-constexpr int HD_MAXNETS = 8;
+constexpr int HD_NT = HD_NW * 64;           // (HD_MAXNETS: owwhip_layout.h)
 
 __global__ __launch_bounds__(HD_NT) void heads64_kernel(HeadParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];

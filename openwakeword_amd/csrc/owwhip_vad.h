@@ -31,9 +31,7 @@ using owr::f32x4;
 #endif
 constexpr int V_WG = OWV_WG;              // waves per workgroup of the front kernel (12: one workgroup per CU, 3 waves per SIMD)
 constexpr int V_FEAT_STRIDE = 144;        // floats per staged feature row (128 bins + 16: the gather of 16 lanes x 16 B is conflict-free)
-// encoder weight blocks of 1 KB in LDS: layer l = [oct][tap][ks][part]
-constexpr int V_BLK1 = 1 * 3 * 4 * 2, V_BLK2 = 2 * 3 * 1 * 2, V_BLK3 = 2 * 3 * 1 * 2, V_BLK4 = 4 * 3 * 1 * 2;
-constexpr int V_WFLOATS = (V_BLK1 + V_BLK2 + V_BLK3 + V_BLK4) * 256;
+// (encoder weight blocks V_BLK1..4, V_WFLOATS: owwhip_layout.h)
 constexpr int V_WAVE_FLOATS = 640 + 2 * 576;       // samples (1280 int16) + FFT planes (the feature staging rows alias the re plane)
 static_assert(4 * V_FEAT_STRIDE <= 576, "feature rows fit the re plane");
 constexpr int V_LDS_BYTES = (V_WFLOATS + 4 * 64 + 256 + V_WG * V_WAVE_FLOATS) * 4;

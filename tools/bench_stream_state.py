@@ -6,7 +6,7 @@ records, and what a compaction pass buys a masked step at 50 % participation.
 1. Throughput.  `oww_state_export` into a device buffer and `oww_move_streams`, for (a) n random streams and (b) n streams as whole
    32-stream blocks.  Yardstick, same process: hipMemcpyAsync device-to-device of n x record_bytes (what park_state does).  Allowed
    time = yardstick x (bytes the call must touch / 2 n record_bytes) + the yardstick's own spread over the five alternating rounds.
-   The bytes come from the layout (history lengths and streams per group block are read from csrc/owwhip.hip) with 128-byte
+   The bytes come from the layout (history lengths and streams per group block are read from csrc/owwhip_layout.h) with 128-byte
    requests: a listed stream drags in its whole group block for every grouped array unless its group mates are listed too.
    Times are GPU times: events on the handle's stream behind a filler that keeps the stream busy while the host builds and queues
    the call, so the host's list building is not in them; `wall_ms` is the whole call from the host, synchronised either side.
@@ -32,7 +32,7 @@ LINE = 128                     # bytes per memory request
 
 
 def layout_constants():
-    src = open(os.path.join(ROOT, "openwakeword_amd", "csrc", "owwhip.hip")).read()
+    src = open(os.path.join(ROOT, "openwakeword_amd", "csrc", "owwhip_layout.h")).read()
 
     def arr(name):
         m = re.search(name + r"\[N_STATE\]\s*=\s*\{([^}]*)\}", src)
