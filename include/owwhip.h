@@ -359,6 +359,64 @@ int  oww_state_export(oww_ctx* h, const int32_t* stream_ids, int32_t n, void* ou
 int  oww_state_import(oww_ctx* h, const int32_t* stream_ids, int32_t n, const void* in, int in_on_device);
 int  oww_move_streams(oww_ctx* h, const int32_t* src, const int32_t* dst, int32_t n);
 
+/* ---- detection events: the hits of a call as ordered device-side records, with the feature window the head saw ---------------------
+ * A caller of oww_step otherwise copies [S][n_labels] (and [S][K] bank) scores back and scans them for score >= threshold, and the
+ * evidence of a detection -- the feature rows behind it, for a second-stage verifier, a log or custom-verifier training (the reference:
+ * examples/capture_activations.py, Model._get_positive_prediction_frames model.py:428-476) -- is gone from the ring by the time a
+ * pipelined caller sees the score.  With events configured, two small launches behind every step compact the hits into records and
+ * copy each hit's last feature rows in the step that detected.
+ *   oww_events_configure  before oww_commit: room for `capacity` events per call (1 .. 1<<20) and `feature_rows` snapshot rows per event
+ *                       (0 = none .. the handle's feature ring; a value beyond the ring, which is only known once every head is loaded,
+ *                       makes oww_commit return OWW_EINVAL).  Allocates capacity x (32 + feature_rows x 384) bytes on the device, and
+ *                       again per pipeline slot at the first oww_submit.  Every pipelined step (oww_submit) then brings the slot's whole
+ *                       record buffer, capacity x 32 bytes, to page-locked host memory behind its scores WHATEVER the hit count (the
+ *                       count is not known to the host when the copy is queued): 128 KB at capacity 4,096, 32 MB at 1 << 20 -- size the
+ *                       capacity to the hits one call can have, not to the limit.  A handle that never calls it allocates and launches
+ *                       exactly what it did before, and the other entries return OWW_ESTATE.
+ *   oww_events_set_thresholds  after commit: fixed[n_labels] event thresholds of the score columns (NULL = keep) and the one of every
+ *                       bank slot (NaN = keep).  Default 0.5 everywhere; a NaN column threshold = the column never reports.
+ *   oww_get_events      up to `cap` records of the last call into `out` (host), *n_stored = records the call stored = min(*n_total,
+ *                       capacity), *n_total = hits the call had; n_stored < n_total is the overflow signal, not an error.  Any of the
+ *                       three pointers may be NULL.  Which call: after oww_step / oww_step_masked that call (waits for the handle's
+ *                       stream); after oww_collect the collected step, whose counts and records came to page-locked host memory behind
+ *                       its scores (a memcpy, whatever is in flight by then).  Valid until the next step or submit; before any call,
+ *                       and between a submit and the next collect: zero events.
+ *   oww_get_event_features  snapshots of records [first, first + n) of that same call: fp32 [n][feature_rows][96], oldest row first --
+ *                       bit for bit what oww_get_features(stream, feature_rows) read right after the detecting step.  Host pointer, or a
+ *                       16-byte aligned device pointer with out_on_device.  Snapshots stay on the device until asked for; the copy runs
+ *                       on the handle's stream (behind a step that is in flight).  first + n beyond n_stored, or feature_rows == 0:
+ *                       OWW_EINVAL.
+ *   oww_events_dev      device records of the last synchronous call (oww_step / oww_step_masked), *count_dev = device {n_stored,
+ *                       n_total}; valid until the next step; for consumers on the device (enqueue behind the step on the handle's
+ *                       stream).  oww_event_features_dev: the snapshots of the same call, [capacity][feature_rows][96] (NULL with
+ *                       feature_rows == 0): the supported way for a second-stage verifier on the device to read the windows of
+ *                       records [0, n_stored) without the copy of oww_get_event_features.  Both buffers hold one spare record /
+ *                       snapshot behind index capacity - 1 that the library never writes.
+ * Hit: a (stream, fixed score column) or (stream, bank slot with a subscription) pair whose stream took part in the call and whose
+ * post-processed score -- after verifier, patience / debounce and VAD gate: bit for bit what oww_step returns or oww_bank_scores reads
+ * -- is >= its event threshold.  A stream that sits a masked step out reports nothing although its score row repeats; a multi-chunk or
+ * long call reports once, with the call's score; debounce_frames gives one event per utterance.
+ * Order: ascending stream; within a stream the fixed columns ascending, then the slots ascending.  The first min(n_total, capacity)
+ * hits in that order are stored.  `frame` is the stream's prediction counter after the call (the number of calls the stream took part
+ * in since its reset; a handle without fixed heads advances it too).
+ * Cost model: 2 launches of ceil(S x (n_labels + K) / 256) workgroups, timed under kernel class 7; each reads the pairs' scores (4
+ * bytes per pair, twice) and writes 32 + feature_rows x 384 bytes per stored hit.  Not part of the oww_use_graph graph. */
+typedef struct oww_event {     /* 32 bytes */
+    int32_t  stream;
+    int32_t  column;           /* fixed head: score column >= 0; bank: ~slot (negative) */
+    int32_t  bank_id;          /* subscribed bank id for a slot, -1 for a fixed column */
+    float    score;            /* the post-processed score, bit for bit what oww_step returns */
+    uint32_t frame;            /* the stream's prediction counter after this call */
+    int32_t  feature_index;    /* index of this event's snapshot, -1 when feature_rows == 0 */
+    int32_t  reserved[2];      /* 0 */
+} oww_event;
+int  oww_events_configure(oww_ctx* h, int32_t capacity, int32_t feature_rows);
+int  oww_events_set_thresholds(oww_ctx* h, const float* fixed, float bank);
+int  oww_get_events(oww_ctx* h, oww_event* out, int32_t cap, int32_t* n_stored, int32_t* n_total);
+int  oww_get_event_features(oww_ctx* h, int32_t first, int32_t n, float* out, int out_on_device);
+const oww_event* oww_events_dev(const oww_ctx* h, const int32_t** count_dev);
+const float* oww_event_features_dev(const oww_ctx* h);
+
 /* ---- multi-GPU: delivery of the scores to one rank over RCCL (xGMI), for binders without torch.distributed ----------------------
  * Streams are independent, so N GPUs = N handles in N processes, each owning a contiguous range of the global streams (the
  * reference's only scale-out, utils.py:502-536 bulk_predict, splits FILES over processes the same way); nothing in the data path

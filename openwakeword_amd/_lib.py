@@ -88,6 +88,12 @@ SYMBOLS = {
     "oww_state_export": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),
     "oww_state_import": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),
     "oww_move_streams": (C.c_int, [_P, _P, _P, C.c_int32]),
+    "oww_events_configure": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "oww_events_set_thresholds": (C.c_int, [_P, _P, C.c_float]),
+    "oww_get_events": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "oww_get_event_features": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int]),
+    "oww_events_dev": (_P, [_P, C.POINTER(_P)]),
+    "oww_event_features_dev": (_P, [_P]),
     "oww_comm_id": (C.c_int, [_P]),
     "oww_comm_init": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "oww_gather_scores": (C.c_int, [_P, _P, _P]),

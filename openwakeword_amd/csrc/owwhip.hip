@@ -25,6 +25,7 @@
 #include "owwhip_vad.h"
 #include "owwhip_fused.h"
 #include "owwhip_state.h"
+#include "owwhip_events.h"
 
 using namespace owk;
 using namespace owp;
@@ -201,6 +202,18 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
         hipEvent_t up = nullptr, done = nullptr, down = nullptr;
         bool busy = false;
     } slot[2];
+    // detection events (oww_events_*; owwhip_events.h): one buffer set for the synchronous calls and one per ingest slot, the latter
+    // with page-locked mirrors of counts and records that ride down behind the slot's scores
+    struct EventBuf {
+        oww_event* d_rec = nullptr; int* d_count = nullptr; float* d_snap = nullptr;     // [cap + 1], {n_stored, n_total}, [cap + 1][rows][96]
+        oww_event* h_rec = nullptr; int* h_count = nullptr;                              // ingest slots only
+    };
+    int evt_cap = 0, evt_rows = 0;               // 0 = no events (oww_events_configure)
+    float* d_evt_thr = nullptr; float evt_bank_thr = 0.5f;
+    int* d_evblock = nullptr; int evt_blocks = 0;
+    EventBuf evt_sync, evt_slot[2];
+    const EventBuf* evt_cur = nullptr;           // what oww_get_events refers to: the last synchronous call or the last collected step
+
     hipStream_t up_stream = nullptr, down_stream = nullptr;
     uint64_t n_submit = 0, n_collect = 0;
     float* d_featinit = nullptr;
@@ -736,6 +749,13 @@ void free_all(oww_ctx* h) {
     h->sv_n = 0;
     fr(h->d_st_flat); fr(h->d_st_items); fr(h->d_st_stage);
     h->st_items_cap = 0; h->st_stage_words = 0; h->st_ready = false;
+    for (oww_ctx::EventBuf* b : {&h->evt_sync, &h->evt_slot[0], &h->evt_slot[1]}) {
+        fr(b->d_rec); fr(b->d_count); fr(b->d_snap);
+        if (b->h_rec) { (void)hipHostFree(b->h_rec); b->h_rec = nullptr; }
+        if (b->h_count) { (void)hipHostFree(b->h_count); b->h_count = nullptr; }
+    }
+    fr(h->d_evt_thr); fr(h->d_evblock);
+    h->evt_cur = nullptr;
     comm_release(h);
 }
 
@@ -979,6 +999,61 @@ int launch_postproc(oww_ctx* h, const StepArgs& a) {
     {
         Timed t(h, 7);
         hipLaunchKernelGGL(postproc_kernel, dim3((h->Spad + 127) / 128), dim3(128), 0, h->stream, pp);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- detection events (oww_events_*; kernels in owwhip_events.h).  Not part of launch_step, hence of no captured graph: the entry
+//      points call launch_events behind the step's launches and before the score copy, on handles that configured events only.
+bool events_on(const oww_ctx* h) { return h->evt_cap > 0; }
+
+// device buffers of one set: records and snapshots with one spare entry behind the capacity (never written), counts zeroed
+int alloc_event_buf(oww_ctx* h, oww_ctx::EventBuf& b, bool host_mirror) {
+    if (int rc = dalloc(h->stream, &b.d_rec, (size_t)h->evt_cap + 1)) return rc;
+    if (int rc = dalloc(h->stream, &b.d_count, 2)) return rc;
+    if (h->evt_rows > 0) if (int rc = dalloc(h->stream, &b.d_snap, ((size_t)h->evt_cap + 1) * h->evt_rows * OWW_EMB_DIM, false)) return rc;
+    if (host_mirror) {
+        HIPCHK(hipHostMalloc((void**)&b.h_rec, (size_t)h->evt_cap * sizeof(oww_event), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void**)&b.h_count, 2 * sizeof(int), hipHostMallocDefault));
+        b.h_count[0] = b.h_count[1] = 0;
+    }
+    return 0;
+}
+
+int alloc_events(oww_ctx* h) {
+    const long long pairs = (long long)h->S * (h->NL + h->bank_K);
+    if (pairs > 0x7fffffffLL - owe::EV_WG) return fail(OWW_EINVAL, "oww_events_configure: %lld (stream, column) pairs are more than the event kernels index", pairs);
+    h->evt_blocks = (int)((pairs + owe::EV_WG - 1) / owe::EV_WG);
+    if (int rc = dalloc(h->stream, &h->d_evblock, (size_t)std::max(h->evt_blocks, 1))) return rc;
+    if (int rc = dalloc(h->stream, &h->d_evt_thr, (size_t)std::max(h->NL, 1), false)) return rc;
+    std::vector<float> half(std::max(h->NL, 1), 0.5f);
+    HIPCHK(copy_async(h->d_evt_thr, half.data(), half.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (int rc = alloc_event_buf(h, h->evt_sync, false)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// The events of the call whose launches were just enqueued, into `buf`.  any_on = false: a masked call nobody takes part in.
+int launch_events(oww_ctx* h, const StepArgs& a, const oww_ctx::EventBuf& buf, bool any_on = true) {
+    if (!any_on || h->evt_blocks == 0) {
+        HIPCHK(hipMemsetAsync(buf.d_count, 0, 2 * sizeof(int), h->stream));
+        return 0;
+    }
+    owe::EventsParams p{};
+    p.scores = h->d_scores; p.bank_scores = h->d_bank_scores; p.bank_sub = h->d_bank_sub;
+    p.thr_fixed = h->d_evt_thr; p.thr_bank = h->evt_bank_thr; p.stream_on = a.on;
+    p.npred = h->d_npred; p.nfeat = h->d_nfeat; p.feat = h->d_feat;
+    p.TR = h->TR; p.NL = h->NL; p.K = h->bank_K;
+    p.n_pairs = h->S * (h->NL + h->bank_K); p.n_blocks = h->evt_blocks; p.block_count = h->d_evblock;
+    p.rec = buf.d_rec; p.count = buf.d_count; p.snap = buf.d_snap; p.capacity = h->evt_cap; p.rows = h->evt_rows;
+    {
+        Timed t(h, 7);
+        hipLaunchKernelGGL(owe::events_count_kernel, dim3(h->evt_blocks), dim3(owe::EV_WG), 0, h->stream, p);
+    }
+    {
+        Timed t(h, 7);
+        hipLaunchKernelGGL(owe::events_write_kernel, dim3(h->evt_blocks), dim3(owe::EV_WG), 0, h->stream, p);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1838,6 +1913,8 @@ int oww_commit(oww_ctx* h) {
     HIPCHK(hipSetDevice(h->cfg.device));
     h->feature_ring = h->cfg.feature_ring;
     if (int rc = build_nets(*h, h->NL, h->TR, h->generic_hmax)) return rc;
+    if (h->evt_rows > h->TR)                     // (the ring is known only now)
+        return fail(OWW_EINVAL, "oww_events_configure: feature_rows = %d exceeds the handle's feature ring (%d rows)", h->evt_rows, h->TR);
     // ---- f16-split family: per-layer activation scales from a calibration run on the exact-fp32 kernels (calibrate_hx) ----
     CommitClock clk(h->hx ? "f16-split" : "family");
     HxCalib cal;
@@ -1879,6 +1956,7 @@ int oww_commit(oww_ctx* h) {
     if (int rc = derive_reset_state(h, cal, clk)) return rc;
     if (h->bank_K > 0) if (int rc = alloc_bank(h)) return rc;
     if (h->vpool_cap > 0) if (int rc = alloc_verifiers(h)) return rc;
+    if (events_on(h)) if (int rc = alloc_events(h)) return rc;
     h->committed = true;
     return OWW_OK;
     OWW_GUARD_END
@@ -1958,6 +2036,7 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
             d_call = h->d_long;
         }
         if (int rc = launch_step_long(h, a, d_call, n_chunks)) return rc;
+        if (events_on(h)) { if (int rc = launch_events(h, a, h->evt_sync)) return rc; h->evt_cur = &h->evt_sync; }
         if (scores) {
             const size_t nb = (size_t)h->S * h->NL * sizeof(float);
             if (nb) HIPCHK(copy_async(scores, h->d_scores, nb, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
@@ -1990,6 +2069,7 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
     } else {
         if (int rc = launch_step(h, a, d_pcm, n_chunks)) return rc;
     }
+    if (events_on(h)) { if (int rc = launch_events(h, a, h->evt_sync)) return rc; h->evt_cur = &h->evt_sync; }
     if (scores) {
         const size_t nb = (size_t)h->S * h->NL * sizeof(float);
         if (nb) HIPCHK(copy_async(scores, h->d_scores, nb, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
@@ -2032,6 +2112,7 @@ int oww_step_masked(oww_ctx* h, const int16_t* pcm, int pcm_on_device, const uin
     }
     if (n_act != 0)                                             // (nobody takes part: nothing moves)
         if (int rc = launch_step(h, a, d_pcm, 1)) return rc;
+    if (events_on(h)) { if (int rc = launch_events(h, a, h->evt_sync, n_act != 0)) return rc; h->evt_cur = &h->evt_sync; }
     if (scores) {
         const size_t nb = (size_t)h->S * h->NL * sizeof(float);
         if (nb) HIPCHK(copy_async(scores, h->d_scores, nb, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
@@ -2057,6 +2138,10 @@ static int ensure_ingest(oww_ctx* h) {
         HIPCHK(hipEventCreateWithFlags(&sl.up, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&sl.down, hipEventDisableTiming));
+    }
+    if (events_on(h)) {
+        for (auto& b : h->evt_slot) if (int rc = alloc_event_buf(h, b, true)) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));          // (the buffers' zero fill: before the first download reads the counts)
     }
     return 0;
 }
@@ -2103,11 +2188,17 @@ static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const u
     }
     if (n_act != 0)
         if (int rc = launch_step(h, a, sl.d_pcm, n_chunks)) return rc;
+    const oww_ctx::EventBuf& eb = h->evt_slot[h->n_submit & 1];
+    if (events_on(h)) { if (int rc = launch_events(h, a, eb, n_act != 0)) return rc; h->evt_cur = nullptr; }
     const size_t nb = (size_t)h->S * h->NL * sizeof(float);
     if (nb) HIPCHK(copy_async(sl.d_scores, h->d_scores, nb, hipMemcpyDeviceToDevice, h->stream));   // d_scores is rewritten by the next step
     HIPCHK(hipEventRecord(sl.done, h->stream));
     HIPCHK(hipStreamWaitEvent(h->down_stream, sl.done, 0));
     if (nb) HIPCHK(copy_async(sl.h_scores, sl.d_scores, nb, hipMemcpyDeviceToHost, h->down_stream));
+    if (events_on(h)) {           // counts and records behind the scores; the slot's buffers are not reused before its oww_collect
+        HIPCHK(copy_async(eb.h_count, eb.d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, h->down_stream));
+        HIPCHK(copy_async(eb.h_rec, eb.d_rec, (size_t)h->evt_cap * sizeof(oww_event), hipMemcpyDeviceToHost, h->down_stream));
+    }
     HIPCHK(hipEventRecord(sl.down, h->down_stream));
     sl.busy = true;
     ++h->n_submit;
@@ -2122,6 +2213,7 @@ int oww_collect(oww_ctx* h, float* scores) {
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipEventSynchronize(sl.down));
     if (scores) memcpy(scores, sl.h_scores, (size_t)h->S * h->NL * sizeof(float));
+    if (events_on(h)) h->evt_cur = &h->evt_slot[h->n_collect & 1];
     sl.busy = false;
     ++h->n_collect;
     if (int rc = range_check(h, "oww_collect")) return rc;      // the step is consumed; its scores are suspect
@@ -2600,6 +2692,94 @@ int oww_use_graph(oww_ctx* h, int on) {
 
 // ---- multi-GPU delivery of results over RCCL, without torch.distributed -----------------------------------------------------------
 // ---- head bank ------------------------------------------------------------------------------------------------------------------------
+int oww_events_configure(oww_ctx* h, int32_t capacity, int32_t feature_rows) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "oww_events_configure: null handle");
+    if (h->committed) return fail(OWW_ESTATE, "oww_events_configure: call before oww_commit");
+    if (capacity < 1 || capacity > (1 << 20)) return fail(OWW_EINVAL, "oww_events_configure: capacity = %d outside [1, %d]", capacity, 1 << 20);
+    // (the upper limit is the handle's feature ring, which is known once every head is loaded: oww_commit refuses what exceeds it)
+    if (feature_rows < 0) return fail(OWW_EINVAL, "oww_events_configure: feature_rows = %d outside [0, the feature ring]", feature_rows);
+    h->evt_cap = capacity; h->evt_rows = feature_rows;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_events_set_thresholds(oww_ctx* h, const float* fixed, float bank) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "oww_events_set_thresholds: null handle");
+    if (!h->committed || !events_on(h)) return fail(OWW_ESTATE, "oww_events_set_thresholds: needs oww_events_configure and oww_commit");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (fixed && h->NL > 0) {
+        HIPCHK(copy_async(h->d_evt_thr, fixed, (size_t)h->NL * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));     // the caller's array is free again
+    }
+    if (bank == bank) h->evt_bank_thr = bank;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+// {n_stored, n_total} of the call oww_get_events refers to
+static int event_counts(oww_ctx* h, int cnt[2]) {
+    cnt[0] = cnt[1] = 0;
+    const oww_ctx::EventBuf* b = h->evt_cur;
+    if (!b) return 0;
+    if (b->h_count) { cnt[0] = b->h_count[0]; cnt[1] = b->h_count[1]; return 0; }
+    HIPCHK(copy_async(cnt, b->d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int oww_get_events(oww_ctx* h, oww_event* out, int32_t cap, int32_t* n_stored, int32_t* n_total) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "oww_get_events: null handle");
+    if (!h->committed || !events_on(h)) return fail(OWW_ESTATE, "oww_get_events: the handle has no events (oww_events_configure before oww_commit)");
+    if (cap < 0 || (cap > 0 && !out)) return fail(OWW_EINVAL, "oww_get_events: cap = %d with out = %p", cap, (void*)out);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    int cnt[2];
+    if (int rc = event_counts(h, cnt)) return rc;
+    const int n = std::min(std::min(cnt[0], h->evt_cap), (int)cap);
+    if (n > 0 && out) {
+        const oww_ctx::EventBuf* b = h->evt_cur;
+        if (b->h_rec) memcpy(out, b->h_rec, (size_t)n * sizeof(oww_event));
+        else {
+            HIPCHK(copy_async(out, b->d_rec, (size_t)n * sizeof(oww_event), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+        }
+    }
+    if (n_stored) *n_stored = cnt[0];
+    if (n_total) *n_total = cnt[1];
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_get_event_features(oww_ctx* h, int32_t first, int32_t n, float* out, int out_on_device) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "oww_get_event_features: null handle");
+    if (!h->committed || !events_on(h)) return fail(OWW_ESTATE, "oww_get_event_features: the handle has no events (oww_events_configure before oww_commit)");
+    if (h->evt_rows == 0) return fail(OWW_EINVAL, "oww_get_event_features: the handle keeps no snapshots (feature_rows = 0)");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    int cnt[2];
+    if (int rc = event_counts(h, cnt)) return rc;
+    const int stored = std::min(cnt[0], h->evt_cap);
+    if (first < 0 || n < 0 || (long long)first + n > stored) return fail(OWW_EINVAL, "oww_get_event_features: events [%d, %d + %d) of %d stored", first, first, n, stored);
+    if (n == 0) return OWW_OK;
+    if (!out) return fail(OWW_EINVAL, "oww_get_event_features: out is null");
+    const size_t per = (size_t)h->evt_rows * OWW_EMB_DIM;
+    HIPCHK(copy_async(out, h->evt_cur->d_snap + (size_t)first * per, (size_t)n * per * sizeof(float),
+                      out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+const oww_event* oww_events_dev(const oww_ctx* h, const int32_t** count_dev) {
+    const bool ok = h && h->committed && events_on(h);
+    if (count_dev) *count_dev = ok ? h->evt_sync.d_count : nullptr;
+    return ok ? h->evt_sync.d_rec : nullptr;
+}
+
+const float* oww_event_features_dev(const oww_ctx* h) { return h && h->committed && events_on(h) ? h->evt_sync.d_snap : nullptr; }
+
 int oww_bank_configure(oww_ctx* h, int32_t slots, int32_t capacity) {
     OWW_GUARD_BEGIN
     if (!h) return fail(OWW_EINVAL, "null handle");

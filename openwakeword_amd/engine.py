@@ -25,6 +25,10 @@ _KIND = {"binary": 0, "gated": 1, "multiclass": 2, "rnn": 3}
 # rows x mel-width x channels that each CNN layer produces per 80 ms step (incremental form)
 LAYER_NEW_SHAPES = ([(8, 32, 24)] * 3 + [(4, 16, 48)] * 4 + [(4, 8, 72)] * 4 + [(2, 4, 96)] * 4 +
                     [(2, 2, 96)] * 4 + [(1, 1, 96)])
+# oww_event of include/owwhip.h (32 bytes): what events() returns
+EVENT_DTYPE = np.dtype([("stream", np.int32), ("column", np.int32), ("bank_id", np.int32), ("score", np.float32),
+                        ("frame", np.uint32), ("feature_index", np.int32), ("reserved", np.int32, (2,))])
+EVENT_CAPACITY_MAX = 1 << 20
 KERNEL_CLASSES = ["mel", "stageA", "stageB", "stageC", "stageD", "stageE", "heads", "postproc", "vad_front", "vad_lstm"]
 
 
@@ -105,6 +109,49 @@ def pack_vad_blob(vad: dict) -> np.ndarray:
     return np.concatenate([np.ascontiguousarray(p, dtype=np.float32).ravel() for p in parts])
 
 
+def events_from_scores(scores, bank_scores=None, bank_sub=None, thresholds=0.5, bank_thr=0.5, participating=None):
+    """The definition of a call's detection events (include/owwhip.h: oww_get_events), restated on host arrays: for users and tests
+    without a GPU, and the reference the device path is held to.
+
+    scores [S, n_labels] and bank_scores [S, K] are the call's post-processed scores (either may be None), bank_sub [S, K] the bank id
+    subscribed to each slot (< 0 = empty), thresholds one value or [n_labels] (NaN = the column never reports), bank_thr the bank
+    slots' threshold, participating [S] which streams took part in the call (None = all).  A pair is a hit when its stream took part,
+    the pair exists and score >= threshold.  Returns [(stream, column, bank_id, score)] in the library's order: ascending stream, then
+    the fixed columns ascending, then the slots ascending; a fixed hit carries (column, -1), a bank hit (~slot, bank id)."""
+    sc = None if scores is None else np.asarray(scores, dtype=np.float32)
+    bs = None if bank_scores is None else np.asarray(bank_scores, dtype=np.float32)
+    if sc is None and bs is None:
+        return []
+    if sc is not None and sc.ndim != 2 or bs is not None and bs.ndim != 2:
+        raise ValueError("scores and bank_scores are 2-D [streams, columns] arrays")
+    S = (sc if sc is not None else bs).shape[0]
+    NL = 0 if sc is None else sc.shape[1]
+    K = 0 if bs is None else bs.shape[1]
+    if sc is not None and bs is not None and bs.shape[0] != S:
+        raise ValueError("scores and bank_scores must cover the same streams")
+    thr = np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (NL,))
+    sub = None
+    if K:
+        if bank_sub is None:
+            raise ValueError("bank_scores need bank_sub, the bank id subscribed to every slot")
+        sub = np.asarray(bank_sub)
+        if sub.shape != (S, K):
+            raise ValueError(f"bank_sub must be [{S}, {K}], got {sub.shape}")
+    on = np.ones(S, dtype=bool) if participating is None else np.asarray(participating) != 0
+    if on.shape != (S,):
+        raise ValueError(f"participating must be [{S}], got {on.shape}")
+    bank_thr = np.float32(bank_thr)
+    out = []
+    for s in np.flatnonzero(on):
+        for c in range(NL):
+            if sc[s, c] >= thr[c]:                    # (False for a NaN threshold)
+                out.append((int(s), c, -1, np.float32(sc[s, c])))
+        for k in range(K):
+            if sub[s, k] >= 0 and bs[s, k] >= bank_thr:
+                out.append((int(s), ~k, int(sub[s, k]), np.float32(bs[s, k])))
+    return out
+
+
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -131,6 +178,21 @@ def default_calibration_pcm() -> Optional[np.ndarray]:
     return np.stack(rows)
 
 
+def check_event_config(event_capacity, event_features, feature_ring: int) -> Tuple[int, int]:
+    """The limits of oww_events_configure, checked before the library is touched -> (capacity, rows)."""
+    for name, v in (("event_capacity", event_capacity), ("event_features", event_features)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    cap, rows = int(event_capacity), int(event_features)
+    if cap < 0 or cap > EVENT_CAPACITY_MAX:
+        raise ValueError(f"event_capacity must lie in 0 .. {EVENT_CAPACITY_MAX} (0 = no events), got {cap}")
+    if rows < 0 or rows > int(feature_ring):
+        raise ValueError(f"event_features must lie in 0 .. {int(feature_ring)} (the feature ring), got {rows}")
+    if rows > 0 and cap == 0:
+        raise ValueError("event_features needs event_capacity > 0")
+    return cap, rows
+
+
 class StreamEngine:
     """One GPU, S streams.  `heads` maps model name -> head dict (see weights.synthetic_head).
 
@@ -142,7 +204,7 @@ class StreamEngine:
                  device: int = 0, max_chunks: int = 1, use_mfma: int = 3, debug_layers: bool = False,
                  feature_ring: int = 0, hip_stream: int = 0, vad: Optional[dict] = None, vad_threshold: float = 0.0,
                  calibration_pcm: Union[np.ndarray, str, None] = "default", bank_slots: int = 0, bank_capacity: int = 0,
-                 verifier_capacity: int = 0):
+                 verifier_capacity: int = 0, event_capacity: int = 0, event_features: int = 0):
         """`vad`: weights of the on-device voice-activity stand-in network (weights.synthetic_vad layout); when given, every
         step also runs it on the frame's two 640-sample sub-frames and gates the scores with `vad_threshold` (model.py:366-381).
         `calibration_pcm` (use_mfma = 3): audio of the deployment's domain, int16 [n, k * 1280], that oww_commit adds to its built-in
@@ -151,7 +213,11 @@ class StreamEngine:
         `bank_slots` > 0 (use_mfma = 3): a head bank of `bank_capacity` heads, every stream subscribed to up to `bank_slots` of them
         (oww_bank_configure; bank_add / subscribe / bank_scores below).
         `verifier_capacity` > 0: a pool of that many per-stream custom verifiers (oww_verifier_configure; verifier_add /
-        assign_verifiers below)."""
+        assign_verifiers below).
+        `event_capacity` > 0: detections are reported as ordered device-side events, up to that many per call, each with a snapshot of
+        the stream's last `event_features` feature rows (oww_events_configure; set_event_thresholds / events / event_features below)."""
+        self.event_capacity, self.event_rows = check_event_config(event_capacity, event_features,
+                                                                  max([16] + [int(h["T"]) for h in heads.values()] + [int(feature_ring)]))
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self._inflight: List[np.ndarray] = []
@@ -201,6 +267,8 @@ class StreamEngine:
             self.verifier_capacity = int(verifier_capacity)
             if self.verifier_capacity > 0:
                 _lib.check(self._lib.oww_verifier_configure(self._h, self.verifier_capacity))
+            if self.event_capacity > 0:
+                _lib.check(self._lib.oww_events_configure(self._h, self.event_capacity, self.event_rows))
             _lib.check(self._lib.oww_commit(self._h))
             if vad_threshold:
                 _lib.check(self._lib.oww_set_vad_threshold(self._h, float(vad_threshold)))
@@ -503,6 +571,52 @@ class StreamEngine:
         _lib.check(self._lib.oww_bank_routing(self._h, _ptr(info), C.byref(wb)))
         return {"tiles": [int(info[0]), int(info[3])], "waves_per_tile": [int(info[1]), int(info[4])],
                 "entries": [int(info[2]), int(info[5])], "weight_bytes": float(wb.value)}
+
+    # ---- detection events (include/owwhip.h: oww_events_*) ----
+    def set_event_thresholds(self, fixed: Optional[Sequence[float]] = None, bank: Optional[float] = None) -> None:
+        """Event thresholds of the score columns ([n_labels]; NaN = the column never reports; None = keep) and of the bank slots."""
+        thr = None
+        if fixed is not None:
+            thr = np.ascontiguousarray(fixed, dtype=np.float32)
+            if thr.shape != (self.n_labels,):
+                raise ValueError(f"need one event threshold per label ({self.n_labels})")
+        _lib.check(self._lib.oww_events_set_thresholds(self._h, _ptr(thr), float("nan") if bank is None else float(bank)))
+
+    def events(self) -> Tuple[np.ndarray, int]:
+        """(records, n_total) of the last step / step_masked / collect: records is a structured array (EVENT_DTYPE) of the stored events
+        in ascending (stream, column, slot) order, n_total counts every hit; len(records) < n_total = the call overflowed the capacity."""
+        rec = np.zeros(self.event_capacity, dtype=EVENT_DTYPE)
+        n_stored, n_total = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.oww_get_events(self._h, _ptr(rec), rec.size, C.byref(n_stored), C.byref(n_total)))
+        return rec[:n_stored.value].copy(), int(n_total.value)
+
+    def event_features(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """float32 [n, event_features, 96]: the feature rows (oldest first) behind stored events first .. first + n - 1 of the call
+        events() refers to, as the ring held them right after the detecting step; n = None: up to the last stored event."""
+        if n is None:
+            n_stored = C.c_int32(0)
+            _lib.check(self._lib.oww_get_events(self._h, None, 0, C.byref(n_stored), None))
+            n = max(0, n_stored.value - int(first))
+        out = np.empty((int(n), self.event_rows, EMB_DIM), dtype=np.float32)
+        _lib.check(self._lib.oww_get_event_features(self._h, int(first), int(n), _ptr(out), 0))
+        return out
+
+    def events_dev_ptrs(self) -> Tuple[int, int, int]:
+        """Device addresses (records, {n_stored, n_total}, snapshots) of the last synchronous step's events; 0 where there is none."""
+        cnt = C.c_void_p()
+        rec = self._lib.oww_events_dev(self._h, C.byref(cnt))
+        return int(rec or 0), int(cnt.value or 0), int(self._lib.oww_event_features_dev(self._h) or 0)
+
+    def event_label(self, record) -> Union[str, int]:
+        """The score column's name for a fixed-head event ("name" or "name:j" for output j of a multi-output head), the bank id for a
+        bank event."""
+        col = int(record["column"])
+        if col < 0:
+            return int(record["bank_id"])
+        for name, (lo, hi) in self.head_cols.items():
+            if lo <= col < hi:
+                return name if hi - lo == 1 else f"{name}:{col - lo}"
+        raise ValueError(f"no score column {col}")
 
     # ---- stream state records (include/owwhip.h: oww_state_*, oww_move_streams) ----
     def state_info(self) -> Tuple[int, int]:

@@ -28,7 +28,7 @@ from typing import Callable, DefaultDict, Dict, List, Optional, Sequence, Tuple,
 import numpy as np
 
 from . import weights as W
-from .engine import CHUNK, EMB_DIM, StreamEngine
+from .engine import CHUNK, EMB_DIM, StreamEngine, check_event_config
 
 # openwakeword/__init__.py:26-60 (names only; the files are release assets that are not in the checkout)
 MODELS = {name: {"model_path": os.path.join(os.path.dirname(os.path.abspath(__file__)), "resources", "models",
@@ -597,12 +597,15 @@ class BatchedModel:
                  device: int = 0, max_chunks: int = 1, hip_stream: int = 0, vad_weights: Optional[dict] = None,
                  vad_threshold: float = 0.0, use_mfma: Optional[int] = None, calibration_pcm="default",
                  embedding_model_path: str = "", melspec_model_path: str = "", bank_slots: int = 0, bank_capacity: int = 1024,
-                 verifier_capacity: int = 0):
+                 verifier_capacity: int = 0, event_capacity: int = 0, event_features: int = 0):
         # bank_slots > 0: a head bank (bank_add / subscribe / bank_scores): every stream is scored by the bank heads it subscribed to,
         # up to bank_slots of them, beside the fixed `wakeword_models` (which may then be empty)
         # verifier_capacity > 0: a pool of per-stream custom verifiers (add_verifier / assign_verifiers / assign_bank_verifiers)
+        # event_capacity > 0: detections as ordered device-side events, each with the stream's last event_features feature rows
+        # (set_event_thresholds / events / event_features / event_label)
         if not wakeword_models and int(bank_slots) <= 0:
             raise ValueError("BatchedModel needs wakeword_models, or a head bank (bank_slots > 0)")
+        check_event_config(event_capacity, event_features, 1 << 30)       # (the ring itself is known once the heads are loaded)
         self._weights = weights
         self._debounce_frames = 0
         # same weight resolution as Model: real .onnx files (heads AND the shared embedding network) unless synthetic
@@ -634,7 +637,9 @@ class BatchedModel:
         self.engine = make_engine(n_streams, heads, emb, use_mfma, device=device, max_chunks=max_chunks, hip_stream=hip_stream,
                                   vad=vad_weights, vad_threshold=vad_threshold, calibration_pcm=calibration_pcm,
                                   bank_slots=int(bank_slots), bank_capacity=int(bank_capacity),
-                                  verifier_capacity=int(verifier_capacity))
+                                  verifier_capacity=int(verifier_capacity), event_capacity=int(event_capacity),
+                                  event_features=int(event_features))
+        self.event_capacity, self.event_rows = int(event_capacity), int(event_features)
         self.bank_slots = int(bank_slots)
         self.verifier_capacity = int(verifier_capacity)
         self._model_T = {n: int(h["T"]) for n, h in heads.items()}
@@ -651,6 +656,7 @@ class BatchedModel:
                     self.labels.append(cls)
                     self._keep.append(col + int(int_label))
             col += h["n_out"]
+        self._event_thr = np.full(self.engine.n_labels, 0.5, dtype=np.float32)
         self._parent = {}
         col = 0
         for n, h in heads.items():
@@ -723,6 +729,40 @@ class BatchedModel:
         """float32 [n_streams, bank_slots]: the post-processed bank scores of the last predict_batch / predict_active /
         collect_batch (an empty slot reads 0.0)."""
         return self.engine.bank_scores()
+
+    # ---- detection events: the hits of a call as ordered records with feature snapshots (include/owwhip.h: oww_events_*) ----
+    def set_event_thresholds(self, thresholds: Optional[dict] = None, bank: Optional[float] = None) -> None:
+        """Event thresholds by label ({label: value}; labels not named keep theirs, NaN = the label never reports) and for the bank
+        slots (`bank`; None = keep).  Default 0.5 everywhere."""
+        if self.event_capacity <= 0:
+            raise ValueError("this BatchedModel reports no events (event_capacity = 0)")
+        thresholds = thresholds or {}
+        unknown = [k for k in thresholds if k not in self.labels]
+        if unknown:
+            raise ValueError(f"unknown labels {unknown}; this model's labels are {self.labels}")
+        for label, v in thresholds.items():
+            self._event_thr[self._keep[self.labels.index(label)]] = np.float32(v)
+        self.engine.set_event_thresholds(self._event_thr if thresholds else None, bank)
+
+    def events(self) -> Tuple[np.ndarray, int]:
+        """(records, n_total) of the last predict_batch / predict_active / collect_batch: a structured array (engine.EVENT_DTYPE:
+        stream, column, bank_id, score, frame, feature_index) of the stored detections in ascending (stream, column, slot) order, and
+        the number of detections the call had; fewer records than that = the call overflowed event_capacity."""
+        return self.engine.events()
+
+    def event_features(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """float32 [n, event_features, 96]: the feature window behind stored events first .. first + n - 1, taken on the device in the
+        step that detected (what Model._get_positive_prediction_frames collects, model.py:428-476)."""
+        return self.engine.event_features(first, n)
+
+    def event_label(self, record) -> Union[str, int]:
+        """The label of a fixed-head event (as in `labels`), the bank id of a bank event."""
+        col = int(record["column"])
+        if col < 0:
+            return int(record["bank_id"])
+        if col in self._keep:
+            return self.labels[self._keep.index(col)]
+        return self.engine.event_label(record)
 
     # ---- stream state records: a live stream's state as a portable record (include/owwhip.h: oww_state_*, oww_move_streams) ----
     def _stream_ids(self, ids, what: str = "stream_ids") -> np.ndarray:
