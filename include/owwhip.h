@@ -235,6 +235,55 @@ int  oww_get_raw(oww_ctx* h, float* out);
 int  oww_resample(oww_ctx* h, const int16_t* in, int in_on_device, int32_t n_in, int32_t p, int32_t q, const float* taps, int32_t n_taps,
                   int16_t* out, int out_on_device, int32_t n_out);
 
+/* ---- stateful stream ingest: G.711 / PCM16 decode and CONTINUOUS rate conversion on the device, straight into the step ------------
+ * oww_resample above converts every message on its own, like the serving example: each message is zero-padded on both sides, so
+ * every 80 ms frame starts and ends inside the filter's transient (35.9 dB SNR against conversion of the whole recording at 8 kHz
+ * with 640-sample messages).  These entries keep the filter running across messages, per stream, and take what telephony gateways
+ * deliver (G.711 at 8 kHz) without a host decode.
+ * Definition.  X = every decoded sample a stream has received since its last reset, message after message; p / q = input rate /
+ * 16000 in lowest terms; taps float [q][n_taps] (n_taps even; resample.py::design or any other).  Output sample J of the stream is
+ *   out[J] = sat_int16(rint(sum_k taps[(J p) % q][k] * X[(J p) / q + k - (n_taps - 1)])),   X[i] = 0 for i < 0,
+ * k over the row padded with zeros to a multiple of 4, in order, an fp32 fmaf chain started at 0: oww_resample's definition applied to
+ * the whole recording behind n_taps / 2 zeros, bit for bit.  So the latency is n_taps / 2 INPUT samples (13 samples = 1.6 ms at 8 kHz
+ * with resample.py's bank), no output depends on a sample that has not arrived, and how the recording is cut into messages changes
+ * nothing.  A message must hold a whole number of output samples, (n_in * q) % p == 0 (OWW_EINVAL otherwise; every standard rate has
+ * such an 80 ms frame: 640 at 8 kHz, 882 at 11.025, 1764 at 22.05, 3528 at 44.1, 3840 at 48 kHz); every message then starts at filter
+ * phase 0, n_out = n_in * q / p, and the only per-stream state is the last n_taps - 1 decoded samples.
+ * Encodings: OWW_ENC_PCM16 (int16), OWW_ENC_ULAW / OWW_ENC_ALAW (one byte per sample, the G.711 expansion to 16 bit):
+ *   mu-law  u = ~b; t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7); value = u & 0x80 ? 0x84 - t : t - 0x84
+ *   A-law   a = b ^ 0x55; t = (a & 15) << 4; seg = (a >> 4) & 7; seg 0: t += 8; seg 1: t += 0x108; else t = (t + 0x108) << (seg - 1);
+ *           value = a & 0x80 ? t : -t
+ * p = q = 1 with n_taps = 0 (taps ignored) means decode only: no filter, no history.
+ *   oww_ingest_configure  after oww_commit.  Allocates the history int16 [S][Hpad] (Hpad = n_taps - 1 rounded up to 8 samples, zeroed),
+ *                       a 16-byte aligned staging buffer for the 16 kHz output (grown on demand) and uploads the padded bank.  Calling
+ *                       it again reconfigures and zeroes every history.  Unknown encoding, odd n_taps, n_taps > 4096, q > 65536: OWW_EINVAL.
+ *   oww_ingest          in: [S][n_in] in the configured encoding, host or device.  out: int16 [S][n_out], host or device; NULL = the
+ *                       handle's staging buffer, which oww_ingest_dev returns (valid until the next ingest call).  stream_on: uint8 [S]
+ *                       or NULL (host or device); a stream with stream_on[s] == 0 is not read, its history does not move and its output
+ *                       row is not written.  One workgroup converts one stream's message out of LDS: a message whose history + samples
+ *                       exceed 96 KB as floats (about 24,000 samples) is refused with OWW_EINVAL naming the numbers.  Asynchronous when
+ *                       every pointer is a device pointer (or NULL); a host `out` with a mask is copied run by run of participants.
+ *   oww_step_ingest     oww_ingest into the staging buffer, then oww_step (n_out / 1280 chunks; stream_on == NULL) or oww_step_masked
+ *                       (one chunk) from that device pointer: the 16 kHz audio never leaves the device, and the staging buffer is
+ *                       aligned, so the step takes its fast path.  n_out must be a positive multiple of 1280 (OWW_EINVAL naming it;
+ *                       nothing has moved then).  With oww_use_graph the ingest launch precedes the replay on the handle's stream.
+ * oww_reset also zeroes the ingest history of the streams it resets (a new caller starts from silence); oww_move_streams,
+ * oww_state_export and oww_state_import carry it: once ingest is configured the record has one more flat section of Hpad / 2 words
+ * behind the existing ones, and the fingerprint also covers encoding, p, q and the bank's bytes (configuring ingest rebuilds the
+ * layout table).  A handle that never configures ingest has the records, fingerprint, allocations and launches it had before.
+ * Cost model: bandwidth.  Per stream and 80 ms step at 8 kHz mu-law 640 B in, 2,560 B out and 2 x 64 B of history against about
+ * 36 k FMAs out of LDS; loads are 16 codes (or 8 samples) per lane, stores 8 outputs per lane, the history moves in 16-byte pieces
+ * (rows that do not start on 16-byte boundaries take element-wise accesses).  Not counted by oww_kernel_times. */
+#define OWW_ENC_PCM16 0
+#define OWW_ENC_ULAW  1
+#define OWW_ENC_ALAW  2
+int  oww_ingest_configure(oww_ctx* h, int32_t encoding, int32_t p, int32_t q, const float* taps, int32_t n_taps);
+int  oww_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const uint8_t* stream_on, int stream_on_on_device,
+                int16_t* out, int out_on_device);
+const int16_t* oww_ingest_dev(const oww_ctx* h);
+int  oww_step_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const uint8_t* stream_on, int stream_on_on_device,
+                     float* scores, int scores_on_device);
+
 /* ---- head bank: each stream scored only by the wake-word models it subscribed to -----------------------------------------------------
  * openWakeWord's training pipeline (train.py, examples/custom_model.yml) yields one small binary head per phrase; a server that carries
  * many users' own phrases scores each connection with ITS heads, not with every head of the handle.  The embedding CNN (~94 % of a step)

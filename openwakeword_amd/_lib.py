@@ -58,6 +58,10 @@ SYMBOLS = {
     "oww_scores_dev": (_P, [_P]),
     "oww_get_raw": (C.c_int, [_P, _P]),
     "oww_resample": (C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int, C.c_int32]),
+    "oww_ingest_configure": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "oww_ingest": (C.c_int, [_P, _P, C.c_int, C.c_int32, _P, C.c_int, _P, C.c_int]),
+    "oww_ingest_dev": (_P, [_P]),
+    "oww_step_ingest": (C.c_int, [_P, _P, C.c_int, C.c_int32, _P, C.c_int, _P, C.c_int]),
     "oww_mel": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "oww_mel_clips": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "oww_embed": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),

@@ -234,6 +234,15 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     int* d_range = nullptr;          // the same word as the kernels address it
     void* d_rs = nullptr; size_t rs_bytes = 0;     // oww_resample scratch: [taps | in | out] as needed
     std::vector<float> rs_taps;                    // the padded filter bank of the last oww_resample call (upload source)
+    // stateful stream ingest (oww_ingest_configure / oww_ingest / oww_step_ingest; owk::ingest_kernel): nothing before the first configure
+    bool ing_ready = false;
+    int ing_enc = 0, ing_p = 1, ing_q = 1, ing_n_taps = 0, ing_ntp = 0, ing_Hpad = 0;
+    std::vector<float> ing_taps;                   // the padded bank [q][ntp] (upload source, fingerprint)
+    float* d_ing_taps = nullptr;
+    int16_t* d_ing_hist = nullptr;                 // [S][Hpad]: each stream's last n_taps - 1 decoded samples, oldest first, zero padded
+    int16_t* d_ing_out = nullptr; size_t ing_out_cap = 0;      // 16 kHz staging [S][n_out] (oww_ingest_dev), grown on demand
+    void* d_ing_in = nullptr; size_t ing_in_cap = 0;           // a host message on its way in
+    uint8_t* d_ing_on = nullptr;                   // [S] a host mask on its way in
     uint8_t* d_on = nullptr;         // oww_step_masked: [Spad] participation mask of the step being launched (pad streams 0)
     // masked step with few participants: the device copy of the group lists (StepArgs::gl) and its two page-locked staging buffers,
     // used in turn (build_active_lists)
@@ -727,6 +736,8 @@ void free_all(oww_ctx* h) {
     }
     h->lists_cap = 0;
     if (h->d_rs) { (void)dev_free(h->d_rs); h->d_rs = nullptr; h->rs_bytes = 0; }
+    fr(h->d_ing_taps); fr(h->d_ing_hist); fr(h->d_ing_out); fr(h->d_ing_in); fr(h->d_ing_on);
+    h->ing_out_cap = 0; h->ing_in_cap = 0; h->ing_ready = false;
     if (h->h_range) { (void)hipHostFree(h->h_range); h->h_range = nullptr; h->d_range = nullptr; }
     for (auto& sl : h->slot) {
         fr(sl.d_pcm); fr(sl.d_scores);
@@ -1628,6 +1639,7 @@ int state_layout(oww_ctx* h) {
     flat(h->d_vadring, 8, 8); flat(h->d_nvad, 1, 1);
     if (h->vad) flat(h->d_vadlast, 1, 1);
     if (K) { flat(h->d_bank_raw, K, K); flat(h->d_bank_scores, K, K); flat(h->d_bank_npred, K, K); flat(h->d_bank_ring, K * OWW_SCORE_RING, K * OWW_SCORE_RING); }
+    if (h->ing_ready && h->ing_Hpad) flat(h->d_ing_hist, (size_t)h->ing_Hpad / 2, (size_t)h->ing_Hpad / 2);   // oww_ingest history (int16 pairs)
     h->st_flat_quads = off / 4;
     auto group = [&](float* live, int spg, int ppr, bool inter, uint32_t block_words) -> int {
         const int R = ppr >= 4 ? 1 : 4 / ppr;
@@ -1658,6 +1670,11 @@ int state_layout(oww_ctx* h) {
         fp = fp_mix(fp, hh.blob.data(), hh.blob.size() * sizeof(float));
     }
     fp = fp_mix(fp, h->vad_blob.data(), h->vad_blob.size() * sizeof(float));
+    if (h->ing_ready) {                          // a handle that never configured ingest hashes what it always hashed
+        const int32_t ig[4] = {h->ing_enc, h->ing_p, h->ing_q, h->ing_n_taps};
+        fp = fp_mix(fp, ig, sizeof ig);
+        fp = fp_mix(fp, h->ing_taps.data(), h->ing_taps.size() * sizeof(float));
+    }
     h->st_fp = fp;
     if (!h->d_st_flat) HIPCHK(dev_alloc(&h->d_st_flat, h->st_flat.size() * sizeof(ows::FlatSection)));
     HIPCHK(copy_sync(h->d_st_flat, h->st_flat.data(), h->st_flat.size() * sizeof(ows::FlatSection), hipMemcpyHostToDevice));
@@ -1985,6 +2002,11 @@ int oww_reset(oww_ctx* h, const int32_t* stream_ids, int32_t n, const float* ini
         }
         HIPCHK(copy_async(h->d_ids, stream_ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
         if (int rc = do_reset(h, h->d_ids, n, d_init)) return rc;
+    }
+    if (h->ing_ready && h->ing_Hpad) {           // stateful ingest: a new caller starts from silence
+        hipLaunchKernelGGL(ingest_hist_reset_kernel, dim3(stream_ids ? n : h->S), dim3(64), 0, h->stream, h->d_ing_hist, h->ing_Hpad,
+                           stream_ids ? h->d_ids : nullptr, stream_ids ? n : h->S);
+        HIPCHK(hipGetLastError());
     }
     std::vector<int> slots;                      // head bank: Model.reset() empties every prediction buffer, the subscriptions stay
     if (h->bank_K > 0) {
@@ -2438,6 +2460,163 @@ int oww_resample(oww_ctx* h, const int16_t* in, int in_on_device, int32_t n_in, 
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     return OWW_OK;
+    OWW_GUARD_END
+}
+
+// ---- stateful stream ingest (header: oww_ingest_configure / oww_ingest / oww_step_ingest; kernel: ingest_kernel in owwhip_kernels.h) ----
+int oww_ingest_configure(oww_ctx* h, int32_t encoding, int32_t p, int32_t q, const float* taps, int32_t n_taps) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed) return fail(OWW_ESTATE, "oww_ingest_configure: handle not committed");
+    if (encoding != OWW_ENC_PCM16 && encoding != OWW_ENC_ULAW && encoding != OWW_ENC_ALAW)
+        return fail(OWW_EINVAL, "oww_ingest_configure: unknown encoding %d (OWW_ENC_PCM16 = 0, OWW_ENC_ULAW = 1, OWW_ENC_ALAW = 2)", encoding);
+    if (n_taps == 0) {
+        if (p != 1 || q != 1) return fail(OWW_EINVAL, "oww_ingest_configure: n_taps = 0 (decode only) needs p = q = 1, got p=%d q=%d", p, q);
+    } else {
+        if (p < 1 || q < 1 || n_taps < 2 || (n_taps & 1) || n_taps > 4096 || q > 65536)
+            return fail(OWW_EINVAL, "oww_ingest_configure: bad argument (p=%d q=%d n_taps=%d)", p, q, n_taps);
+        if (!taps) return fail(OWW_EINVAL, "oww_ingest_configure: null argument: taps");
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));               // an earlier oww_ingest may still read the old bank and history
+    auto drop = [](auto*& ptr) { if (ptr) { (void)dev_free((void*)ptr); ptr = nullptr; } };
+    drop(h->d_ing_taps); drop(h->d_ing_hist);
+    h->ing_ready = false;
+    drop(h->d_st_flat); h->st_ready = false;               // the record layout gains, loses or resizes its history section: rebuilt on demand
+    const int ntp = (n_taps + 3) / 4 * 4, Hpad = n_taps ? (n_taps - 1 + 7) / 8 * 8 : 0;
+    h->ing_taps.assign((size_t)q * ntp, 0.f);
+    for (int r = 0; r < q && n_taps; ++r) memcpy(&h->ing_taps[(size_t)r * ntp], taps + (size_t)r * n_taps, n_taps * sizeof(float));
+    if (n_taps) {
+        if (dev_alloc(&h->d_ing_taps, h->ing_taps.size() * sizeof(float)) != hipSuccess ||
+            dev_alloc(&h->d_ing_hist, (size_t)h->S * Hpad * sizeof(int16_t)) != hipSuccess) {
+            drop(h->d_ing_taps);
+            return fail(OWW_ENOMEM, "oww_ingest_configure: out of device memory for %d streams x %d history samples", h->S, Hpad);
+        }
+        HIPCHK(copy_sync(h->d_ing_taps, h->ing_taps.data(), h->ing_taps.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(h->d_ing_hist, 0, (size_t)h->S * Hpad * sizeof(int16_t), h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    if (!h->d_ing_out) {
+        h->ing_out_cap = (size_t)h->S * OWW_CHUNK;
+        if (dev_alloc(&h->d_ing_out, h->ing_out_cap * sizeof(int16_t)) != hipSuccess) { h->ing_out_cap = 0; return fail(OWW_ENOMEM, "oww_ingest_configure: out of device memory"); }
+        HIPCHK(hipMemset(h->d_ing_out, 0, h->ing_out_cap * sizeof(int16_t)));
+    }
+    h->ing_enc = encoding; h->ing_p = p; h->ing_q = q; h->ing_n_taps = n_taps; h->ing_ntp = ntp; h->ing_Hpad = Hpad;
+    h->ing_ready = true;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+const int16_t* oww_ingest_dev(const oww_ctx* h) { return h ? h->d_ing_out : nullptr; }
+
+// argument checks shared by oww_ingest and oww_step_ingest: nothing has moved when they refuse
+static int ingest_check(const oww_ctx* h, const char* fn, const void* in, int32_t n_in, long long* n_out) {
+    if (!h || !h->committed) return fail(OWW_ESTATE, "%s: handle not committed", fn);
+    if (!h->ing_ready) return fail(OWW_ESTATE, "%s: ingest is not configured (oww_ingest_configure)", fn);
+    if (!in) return fail(OWW_EINVAL, "%s: null argument: in", fn);
+    if (n_in < 1) return fail(OWW_EINVAL, "%s: bad argument (n_in=%d)", fn, n_in);
+    if (((long long)n_in * h->ing_q) % h->ing_p)
+        return fail(OWW_EINVAL, "%s: a message must hold a whole number of output samples: n_in * q = %d * %d is no multiple of p = %d", fn, n_in, h->ing_q, h->ing_p);
+    *n_out = (long long)n_in * h->ing_q / h->ing_p;
+    if (*n_out > (1 << 24)) return fail(OWW_EINVAL, "%s: n_out = %lld is beyond 2^24 samples per message", fn, *n_out);
+    return 0;
+}
+
+int oww_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const uint8_t* stream_on, int stream_on_on_device,
+               int16_t* out, int out_on_device) {
+    OWW_GUARD_BEGIN
+    long long n_out_ll = 0;
+    if (int rc = ingest_check(h, "oww_ingest", in, n_in, &n_out_ll)) return rc;
+    const int n_out = (int)n_out_ll, H = h->ing_n_taps ? h->ing_n_taps - 1 : 0, Hoff = (H + 3) / 4 * 4;
+    const int xs_len = (Hoff + n_in + 8 + 3) / 4 * 4;        // (+ 8: what the zero-padded taps, and the sliding form's look-ahead quad, read on)
+    const size_t lds_x = (size_t)xs_len * sizeof(float), lds_y = (size_t)IG_TILE * sizeof(int16_t), lds_t = (size_t)h->ing_q * h->ing_ntp * sizeof(float);
+    if (lds_x > 96 * 1024)
+        return fail(OWW_EINVAL, "oww_ingest: a message of n_in = %d samples behind a history of %d needs %zu bytes of LDS, the one-workgroup-per-stream "
+                                "kernel stages at most %d: send shorter messages", n_in, H, lds_x, 96 * 1024);
+    const int taps_in_lds = h->ing_n_taps && lds_x + lds_y + lds_t <= 150 * 1024;
+    const size_t lds = lds_x + lds_y + (taps_in_lds ? lds_t : 0);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t bps = h->ing_enc == OWW_ENC_PCM16 ? 2 : 1, in_bytes = (size_t)h->S * n_in * bps;
+    auto grow = [&](auto*& ptr, size_t& cap, size_t need, bool zero) -> int {
+        if (need <= cap) return 0;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (ptr) (void)dev_free((void*)ptr);
+        ptr = nullptr; cap = 0;
+        if (dev_alloc(&ptr, need) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest: out of device memory for %zu bytes", need);
+        if (zero) HIPCHK(hipMemset(ptr, 0, need));
+        cap = need;
+        return 0;
+    };
+    IngestParams a{};
+    a.in = in;
+    if (!in_on_device) {
+        if (int rc = grow(h->d_ing_in, h->ing_in_cap, in_bytes, false)) return rc;
+        HIPCHK(copy_async(h->d_ing_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
+        a.in = h->d_ing_in;
+    }
+    a.on = stream_on;
+    if (stream_on && !stream_on_on_device) {
+        if (!h->d_ing_on) HIPCHK(dev_alloc(&h->d_ing_on, h->S));
+        HIPCHK(copy_async(h->d_ing_on, stream_on, h->S, hipMemcpyHostToDevice, h->stream));
+        a.on = h->d_ing_on;
+    }
+    const bool to_staging = !out || !out_on_device;
+    if (to_staging) {
+        size_t cap_bytes = h->ing_out_cap * sizeof(int16_t);
+        if (int rc = grow(h->d_ing_out, cap_bytes, (size_t)h->S * n_out * sizeof(int16_t), true)) { h->ing_out_cap = cap_bytes / sizeof(int16_t); return rc; }
+        h->ing_out_cap = cap_bytes / sizeof(int16_t);
+    }
+    a.out = to_staging ? h->d_ing_out : out;
+    a.hist = h->d_ing_hist; a.taps = h->d_ing_taps;
+    a.enc = h->ing_enc; a.n_in = n_in; a.n_out = n_out; a.p = h->ing_p; a.q = h->ing_q; a.n_taps = h->ing_n_taps; a.ntp = h->ing_ntp;
+    a.Hpad = h->ing_Hpad; a.xs_len = xs_len; a.taps_in_lds = taps_in_lds;
+    a.vec_in = !(reinterpret_cast<uintptr_t>(a.in) & 15) && ((size_t)n_in * bps) % 16 == 0;
+    a.vec_out = !(reinterpret_cast<uintptr_t>(a.out) & 15) && n_out % 8 == 0;
+    a.slide = h->ing_n_taps && h->ing_p == 1 && (h->ing_q == 1 || h->ing_q == 2 || h->ing_q == 4 || h->ing_q == 8);
+    const dim3 grid(h->S), block(RS_NT);
+#define OWW_IG_GO(ENC)                                                                                                                        \
+    do {                                                                                                                                      \
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ingest_kernel<ENC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+        hipLaunchKernelGGL(ingest_kernel<ENC>, grid, block, lds, h->stream, a);                                                              \
+    } while (0)
+    if (h->ing_enc == OWW_ENC_PCM16) OWW_IG_GO(IG_PCM16); else if (h->ing_enc == OWW_ENC_ULAW) OWW_IG_GO(IG_ULAW); else OWW_IG_GO(IG_ALAW);
+#undef OWW_IG_GO
+    HIPCHK(hipGetLastError());
+    if (out && !out_on_device) {
+        const size_t row = (size_t)n_out * sizeof(int16_t);
+        if (!stream_on) {
+            HIPCHK(copy_async(out, h->d_ing_out, (size_t)h->S * row, hipMemcpyDeviceToHost, h->stream));
+        } else {                                             // only the rows of the streams that took part reach the caller's buffer, run by run
+            std::vector<uint8_t> on(h->S);
+            if (stream_on_on_device) HIPCHK(hipMemcpy(on.data(), stream_on, h->S, hipMemcpyDeviceToHost)); else memcpy(on.data(), stream_on, h->S);
+            for (int s = 0; s < h->S;) {
+                if (!on[s]) { ++s; continue; }
+                int e = s;
+                while (e < h->S && on[e]) ++e;
+                HIPCHK(copy_async(out + (size_t)s * n_out, h->d_ing_out + (size_t)s * n_out, (size_t)(e - s) * row, hipMemcpyDeviceToHost, h->stream));
+                s = e;
+            }
+        }
+    }
+    if (!in_on_device || (stream_on && !stream_on_on_device) || (out && !out_on_device)) HIPCHK(hipStreamSynchronize(h->stream));   // host buffers are the caller's again
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_step_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const uint8_t* stream_on, int stream_on_on_device,
+                    float* scores, int scores_on_device) {
+    OWW_GUARD_BEGIN
+    long long n_out = 0;
+    if (int rc = ingest_check(h, "oww_step_ingest", in, n_in, &n_out)) return rc;
+    if (n_out < OWW_CHUNK || n_out % OWW_CHUNK)
+        return fail(OWW_EINVAL, "oww_step_ingest: n_out = n_in * q / p = %lld must be a positive multiple of %d", n_out, OWW_CHUNK);
+    const int n_chunks = (int)(n_out / OWW_CHUNK);
+    if (stream_on && n_chunks != 1) return fail(OWW_EINVAL, "oww_step_ingest: a masked step takes one chunk, n_out = %lld", n_out);
+    if (stream_on && !h->rr) return fail(OWW_EINVAL, "oww_step_ingest: a masked step needs the register-resident kernel families (use_mfma = 3 or 1)");
+    if (n_chunks > OWW_MAX_CALL_CHUNKS) return fail(OWW_EINVAL, "oww_step_ingest: n_chunks=%d outside [1,%d]", n_chunks, OWW_MAX_CALL_CHUNKS);
+    if (int rc = range_check(h, "oww_step_ingest")) return rc;             // (before any history moves)
+    if (int rc = oww_ingest(h, in, in_on_device, n_in, stream_on, stream_on_on_device, nullptr, 1)) return rc;
+    if (stream_on) return oww_step_masked(h, h->d_ing_out, 1, stream_on, stream_on_on_device, scores, scores_on_device);
+    return oww_step(h, h->d_ing_out, 1, n_chunks, scores, scores_on_device);
     OWW_GUARD_END
 }
 

@@ -1661,6 +1661,176 @@ __global__ __launch_bounds__(RS_NT) void resample_kernel(ResampleParams a) {
     }
 }
 
+// stateful stream ingest (oww_ingest): G.711 / PCM16 decode and CONTINUOUS rate conversion to 16 kHz.  With X = every decoded sample
+// the stream received since its reset and J the global output index,
+//   out[J] = sat_int16(rint(sum_k taps[(J p) % q][k] * X[(J p) / q + k - (n_taps - 1)])),   X[i] = 0 for i < 0
+// -- resample_kernel's definition on the whole recording behind n_taps / 2 zeros, same k-ordered fmaf chain over the padded row.  A
+// message holds a whole number of outputs ((n_in q) % p == 0), so every message starts at phase 0 and the only state is the last
+// H = n_taps - 1 decoded samples: hist[s][i] = X[first sample of the next message - H + i], int16, rows of Hpad (H rounded up to 8).
+// One workgroup owns one stream's message, so the history has one reader and one writer:
+//   xs[x0 + i] = i < H ? hist[i] : decode(in[i - H])   as float, x0 = Hoff - H so that the message starts on a 16-byte LDS boundary,
+//   output j of the message reads xs[x0 + (j p) / q + k], tiles of IG_TILE outputs go through ys and leave as 16-byte stores,
+//   hist'[i] = xs[x0 + n_in + i] behind the barrier of the last tile (for n_in < H that is the old history moved down).
+// vec_in / vec_out: rows start on 16-byte boundaries (16 codes or 8 samples per lane and load, 8 outputs per lane and store); any other
+// geometry takes the element-wise forms.  A stream with on[s] == 0 is not read, and neither its history nor its output row is written.
+constexpr int IG_TILE = RS_NT * 8;
+constexpr int IG_PCM16 = 0, IG_ULAW = 1, IG_ALAW = 2;          // = OWW_ENC_* (include/owwhip.h)
+struct IngestParams {
+    const void* in; int16_t* out; int16_t* hist; const float* taps; const uint8_t* on;
+    int enc, n_in, n_out, p, q, n_taps, ntp, Hpad, xs_len, taps_in_lds, vec_in, vec_out;
+    int slide;               // p == 1 and q in {1, 2, 4, 8} (8 kHz telephony: q = 2): four neighbouring windows per thread, see 3a
+};
+
+__device__ __forceinline__ float g711_ulaw(uint32_t b) {
+    const int u = (int)(~b & 0xffu);
+    const int t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7);
+    return (float)((u & 0x80) ? 0x84 - t : t - 0x84);
+}
+__device__ __forceinline__ float g711_alaw(uint32_t b) {
+    const int a = (int)((b ^ 0x55u) & 0xffu);
+    const int seg = (a >> 4) & 7;
+    int t = (a & 15) << 4;
+    t = seg == 0 ? t + 8 : seg == 1 ? t + 0x108 : (t + 0x108) << (seg - 1);
+    return (float)((a & 0x80) ? t : -t);
+}
+template <int ENC> __device__ __forceinline__ float4 g711_word(uint32_t w) {
+    if (ENC == IG_ULAW) return make_float4(g711_ulaw(w), g711_ulaw(w >> 8), g711_ulaw(w >> 16), g711_ulaw(w >> 24));
+    return make_float4(g711_alaw(w), g711_alaw(w >> 8), g711_alaw(w >> 16), g711_alaw(w >> 24));
+}
+__device__ __forceinline__ float pcm_lo(uint32_t w) { return (float)(int16_t)(w & 0xffffu); }
+__device__ __forceinline__ float pcm_hi(uint32_t w) { return (float)(int16_t)(w >> 16); }
+__device__ __forceinline__ uint32_t pcm_pack(float lo, float hi) { return ((uint32_t)(int)lo & 0xffffu) | ((uint32_t)(int)hi << 16); }
+
+template <int ENC>
+__global__ __launch_bounds__(RS_NT) void ingest_kernel(IngestParams a) {
+    extern __shared__ __attribute__((aligned(16))) float ig_lds[];
+    const int s = blockIdx.x, t = threadIdx.x;
+    if (a.on && !a.on[s]) return;
+    const int H = a.n_taps > 0 ? a.n_taps - 1 : 0, Hoff = (H + 3) / 4 * 4, x0 = Hoff - H;
+    float* xs = ig_lds;                                               // [xs_len]: x0 spare words | history | message | >= 8 zeros
+    int16_t* ys = reinterpret_cast<int16_t*>(ig_lds + a.xs_len);      // [IG_TILE]
+    float* ts = ig_lds + a.xs_len + IG_TILE / 2;                      // [q][ntp] when taps_in_lds
+    float* xm = xs + Hoff;                                            // the message, 16-byte aligned
+    // ---- 1. history | decoded message, as float
+    if (t < x0) xs[t] = 0.f;
+    if (a.Hpad) {
+        const uint4* hq = reinterpret_cast<const uint4*>(a.hist + (size_t)s * a.Hpad);
+        for (int c = t; c < a.Hpad / 8; c += RS_NT) {
+            const uint4 v = hq[c];
+            const float f[8] = {pcm_lo(v.x), pcm_hi(v.x), pcm_lo(v.y), pcm_hi(v.y), pcm_lo(v.z), pcm_hi(v.z), pcm_lo(v.w), pcm_hi(v.w)};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) if (c * 8 + i < H) xs[x0 + c * 8 + i] = f[i];
+        }
+    }
+    if (ENC == IG_PCM16) {
+        const int16_t* x = static_cast<const int16_t*>(a.in) + (size_t)s * a.n_in;
+        if (a.vec_in) {
+            for (int c = t; c < a.n_in / 8; c += RS_NT) {
+                const uint4 v = reinterpret_cast<const uint4*>(x)[c];
+                reinterpret_cast<float4*>(xm)[2 * c] = make_float4(pcm_lo(v.x), pcm_hi(v.x), pcm_lo(v.y), pcm_hi(v.y));
+                reinterpret_cast<float4*>(xm)[2 * c + 1] = make_float4(pcm_lo(v.z), pcm_hi(v.z), pcm_lo(v.w), pcm_hi(v.w));
+            }
+        } else {
+            for (int i = t; i < a.n_in; i += RS_NT) xm[i] = (float)x[i];
+        }
+    } else {
+        const uint8_t* x = static_cast<const uint8_t*>(a.in) + (size_t)s * a.n_in;
+        if (a.vec_in) {
+            for (int c = t; c < a.n_in / 16; c += RS_NT) {
+                const uint4 v = reinterpret_cast<const uint4*>(x)[c];
+                float4* d = reinterpret_cast<float4*>(xm) + 4 * c;
+                d[0] = g711_word<ENC>(v.x); d[1] = g711_word<ENC>(v.y); d[2] = g711_word<ENC>(v.z); d[3] = g711_word<ENC>(v.w);
+            }
+        } else {
+            for (int i = t; i < a.n_in; i += RS_NT) xm[i] = ENC == IG_ULAW ? g711_ulaw(x[i]) : g711_alaw(x[i]);
+        }
+    }
+    for (int i = Hoff + a.n_in + t; i < a.xs_len; i += RS_NT) xs[i] = 0.f;     // what the zero-padded taps multiply
+    // ---- 2. the bank
+    if (a.taps_in_lds)
+        for (int i = t; i < a.q * a.ntp; i += RS_NT) ts[i] = a.taps[i];
+    __syncthreads();
+    // ---- 3. tiles of outputs: every output is resample_kernel's chain; they leave LDS eight at a time
+    int16_t* y = a.out + (size_t)s * a.n_out;
+    for (int j0 = 0; j0 < a.n_out; j0 += IG_TILE) {
+        const int nt = min(IG_TILE, a.n_out - j0);
+        if (a.slide) {
+            // 3a. p == 1: output pos * q + ph reads xs[x0 + pos + k], so the windows of four neighbouring input positions of one phase
+            // are one window moved by a word.  A thread takes the four positions whose first window starts on a 16-byte LDS boundary
+            // (pos = 4 G - x0 + r): per four taps one ds_read_b128 of samples and one of taps feed 16 fmaf, against 16 + 4 words read
+            // one output at a time.  Each output's chain is still k-ordered from 0.  (A group that straddles a tile edge is computed
+            // by both tiles and stored by the one that owns the position.)
+            const int tp = IG_TILE / a.q, pos0 = j0 / a.q, pos1 = min(pos0 + tp, a.n_in);
+            const int G0 = (pos0 + x0) / 4, ng = (pos1 - 1 + x0) / 4 - G0 + 1;
+            for (int it = t; it < ng * a.q; it += RS_NT) {
+                const int ph = it / ng, G = G0 + it % ng;
+                const float* w = (a.taps_in_lds ? ts : a.taps) + (size_t)ph * a.ntp;
+                const float4* xv = reinterpret_cast<const float4*>(xs + 4 * G);
+                float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+                float4 xa = xv[0];
+                for (int k = 0; k < a.ntp; k += 4) {
+                    const float4 xb = xv[k / 4 + 1];
+                    const float4 w4 = *reinterpret_cast<const float4*>(w + k);
+                    acc0 = fmaf(w4.x, xa.x, acc0); acc0 = fmaf(w4.y, xa.y, acc0); acc0 = fmaf(w4.z, xa.z, acc0); acc0 = fmaf(w4.w, xa.w, acc0);
+                    acc1 = fmaf(w4.x, xa.y, acc1); acc1 = fmaf(w4.y, xa.z, acc1); acc1 = fmaf(w4.z, xa.w, acc1); acc1 = fmaf(w4.w, xb.x, acc1);
+                    acc2 = fmaf(w4.x, xa.z, acc2); acc2 = fmaf(w4.y, xa.w, acc2); acc2 = fmaf(w4.z, xb.x, acc2); acc2 = fmaf(w4.w, xb.y, acc2);
+                    acc3 = fmaf(w4.x, xa.w, acc3); acc3 = fmaf(w4.y, xb.x, acc3); acc3 = fmaf(w4.z, xb.y, acc3); acc3 = fmaf(w4.w, xb.z, acc3);
+                    xa = xb;
+                }
+                const float acc[4] = {acc0, acc1, acc2, acc3};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int pos = 4 * G - x0 + r;
+                    if (pos >= pos0 && pos < pos1) ys[(pos - pos0) * a.q + ph] = (int16_t)fminf(fmaxf(rintf(acc[r]), -32768.f), 32767.f);
+                }
+            }
+        } else
+        for (int jj = t; jj < nt; jj += RS_NT) {
+            const long long jp = (long long)(j0 + jj) * a.p;
+            const float* xw = xs + x0 + (int)(jp / a.q);
+            float acc = 0.f;
+            if (a.ntp == 0) acc = xw[0];                                        // decode only
+            else {
+                const float* w = (a.taps_in_lds ? ts : a.taps) + (size_t)(jp % a.q) * a.ntp;
+                for (int k = 0; k < a.ntp; k += 4) {
+                    const float4 w4 = *reinterpret_cast<const float4*>(w + k);
+                    acc = fmaf(w4.x, xw[k], acc);
+                    acc = fmaf(w4.y, xw[k + 1], acc);
+                    acc = fmaf(w4.z, xw[k + 2], acc);
+                    acc = fmaf(w4.w, xw[k + 3], acc);
+                }
+            }
+            ys[jj] = (int16_t)fminf(fmaxf(rintf(acc), -32768.f), 32767.f);
+        }
+        __syncthreads();
+        if (a.vec_out) {                                                        // (n_out is a multiple of 8 then, and so is nt)
+            if (t * 8 < nt) reinterpret_cast<uint4*>(y + j0)[t] = reinterpret_cast<const uint4*>(ys)[t];
+        } else {
+            for (int jj = t; jj < nt; jj += RS_NT) y[j0 + jj] = ys[jj];
+        }
+        __syncthreads();                                                        // ys is free again; behind the last tile: xs has no reader left
+    }
+    // ---- 4. the new history, from LDS (every read of the old one happened in 1.)
+    if (a.Hpad) {
+        uint4* hq = reinterpret_cast<uint4*>(a.hist + (size_t)s * a.Hpad);
+        const float* nx = xs + x0 + a.n_in;
+        for (int c = t; c < a.Hpad / 8; c += RS_NT) {
+            float f[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) f[i] = c * 8 + i < H ? nx[c * 8 + i] : 0.f;
+            hq[c] = make_uint4(pcm_pack(f[0], f[1]), pcm_pack(f[2], f[3]), pcm_pack(f[4], f[5]), pcm_pack(f[6], f[7]));
+        }
+    }
+}
+
+// oww_reset: the listed streams (ids == nullptr: streams [0, n)) start from silence again
+__global__ void ingest_hist_reset_kernel(int16_t* hist, int Hpad, const int* ids, int n) {
+    const int k = blockIdx.x;
+    if (k >= n) return;
+    uint4* hq = reinterpret_cast<uint4*>(hist + (size_t)(ids ? ids[k] : k) * Hpad);
+    for (int c = threadIdx.x; c < Hpad / 8; c += blockDim.x) hq[c] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // forget the VAD score history of the listed streams (ids == nullptr: streams [0, n)); oww_reset itself leaves it alone (model.py:226-230)
 __global__ void vad_ring_reset_kernel(float* ring, uint32_t* n_vad, const int* ids, int n) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;

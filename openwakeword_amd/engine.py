@@ -369,6 +369,63 @@ class StreamEngine:
         _lib.check(self._lib.oww_resample(self._h, _ptr(pcm), 0, pcm.shape[1], p, q, _ptr(taps), taps.shape[1], _ptr(out), 0, n_out))
         return out
 
+    # ---- stateful stream ingest (include/owwhip.h: oww_ingest_configure / oww_ingest / oww_step_ingest) ----
+    def configure_ingest(self, sample_rate: int, encoding: str = "pcm16") -> None:
+        """Per-stream decode ("pcm16", "ulaw", "alaw") and CONTINUOUS conversion of `sample_rate` Hz to 16 kHz on the device with the
+        bank of resample.design; 16000 Hz = decode only.  Zeroes every stream's filter history; may be called again."""
+        from . import resample as R
+        if encoding not in R.ENCODINGS:
+            raise ValueError(f"unknown encoding {encoding!r} (one of {sorted(R.ENCODINGS)})")
+        if int(sample_rate) == 16000:
+            p, q, taps, n_taps = 1, 1, None, 0
+        else:
+            p, q, taps = R.design(int(sample_rate))
+            n_taps = taps.shape[1]
+        _lib.check(self._lib.oww_ingest_configure(self._h, R.ENCODINGS[encoding], p, q, _ptr(taps), n_taps))
+        self._ingest = (encoding, p, q, n_taps)
+
+    def _ingest_args(self, data: np.ndarray, stream_on):
+        if getattr(self, "_ingest", None) is None:
+            raise _lib.OwwError("ingest is not configured: call configure_ingest(sample_rate, encoding) first")
+        encoding, p, q, _ = self._ingest
+        data = np.ascontiguousarray(data)
+        want = np.int16 if encoding == "pcm16" else np.uint8
+        if data.dtype != want or data.ndim != 2 or data.shape[0] != self.n_streams or data.shape[1] == 0:
+            raise ValueError(f"{encoding} data must be {np.dtype(want).name} [n_streams={self.n_streams}, n], got {data.dtype} {data.shape}")
+        if (data.shape[1] * q) % p:
+            raise ValueError(f"a message must hold a whole number of output samples: {data.shape[1]} * {q} is no multiple of {p}")
+        on = None
+        if stream_on is not None:
+            on = np.ascontiguousarray(np.asarray(stream_on) != 0, dtype=np.uint8)
+            if on.shape != (self.n_streams,):
+                raise ValueError(f"stream_on must be [n_streams={self.n_streams}], got {on.shape}")
+        return data, on, (data.shape[1] * q) // p
+
+    def ingest(self, data: np.ndarray, stream_on: Optional[np.ndarray] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """One message per stream, [S, n_in] in the configured encoding -> 16 kHz int16 [S, n_in * q / p], continuous with the stream's
+        earlier messages (host, blocking).  A stream with stream_on[s] == 0 is not read, keeps its history and its row of `out` is not
+        written (a fresh `out` holds zeros there)."""
+        data, on, n_out = self._ingest_args(data, stream_on)
+        if out is None:
+            out = np.zeros((self.n_streams, n_out), dtype=np.int16)
+        elif out.dtype != np.int16 or out.shape != (self.n_streams, n_out) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous int16 [{self.n_streams}, {n_out}] array")
+        _lib.check(self._lib.oww_ingest(self._h, _ptr(data), 0, data.shape[1], _ptr(on), 0, _ptr(out), 0))
+        return out
+
+    def step_ingest(self, data: np.ndarray, stream_on: Optional[np.ndarray] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """ingest + step without the 16 kHz audio leaving the device (oww_step_ingest): scores fp32 [S, n_labels].  The message must
+        convert to 1280 * k samples (k = 1 with `stream_on`, which is step_masked's mask)."""
+        data, on, n_out = self._ingest_args(data, stream_on)
+        if out is None:
+            out = np.empty((self.n_streams, self.n_labels), dtype=np.float32)
+        _lib.check(self._lib.oww_step_ingest(self._h, _ptr(data), 0, data.shape[1], _ptr(on), 0, _ptr(out), 0))
+        return out
+
+    def ingest_dev_ptr(self) -> int:
+        """Device address of the 16 kHz staging buffer the last ingest without `out` wrote (16-byte aligned; 0 before configure_ingest)."""
+        return int(self._lib.oww_ingest_dev(self._h) or 0)
+
     def step_raw(self, pcm: np.ndarray) -> np.ndarray:
         """Like step(), but returns the head outputs before post-processing (model.py:313-317)."""
         pcm = np.ascontiguousarray(pcm)

@@ -821,6 +821,19 @@ class BatchedModel:
             pcm = self.engine.resample(pcm, sample_rate)
         return self.engine.step(pcm)[:, self._keep]
 
+    def configure_ingest(self, sample_rate: int, encoding: str = "pcm16") -> None:
+        """Streams that arrive as `encoding` ("pcm16", "ulaw", "alaw") at `sample_rate` Hz: decode and continuous rate conversion per
+        stream on the device (engine.configure_ingest); feed them with predict_ingest."""
+        self.engine.configure_ingest(sample_rate, encoding)
+
+    def predict_ingest(self, data: np.ndarray, active=None) -> np.ndarray:
+        """predict_batch on one encoded message per stream (e.g. uint8 [n_streams, 640] of 8 kHz G.711 = one 80 ms step).  Unlike
+        predict_batch(sample_rate=...), the conversion filter runs on across messages, so no frame starts or ends in its transient;
+        `active` ([n_streams] bool): only those streams are fed, as in predict_active."""
+        if not isinstance(data, np.ndarray):
+            raise ValueError(f"The input audio data (x) must by a Numpy array, instead received an object of type {type(data)}.")
+        return self.engine.step_ingest(data, active)[:, self._keep]
+
     def predict_active(self, pcm: np.ndarray, active) -> np.ndarray:
         """predict_batch for the streams flagged in `active` ([n_streams] bool) only; the others do not advance at all and
         repeat their previous scores (the reference's per-client behaviour: no audio, no predict() call)."""

@@ -65,3 +65,52 @@ def apply_numpy(x: np.ndarray, rate_in: int) -> np.ndarray:
     xs = np.where(ok, x[..., np.clip(idx, 0, n_in - 1)].astype(np.float64), 0.0)
     y = (xs * taps[ph].astype(np.float64)).sum(-1)
     return np.clip(np.rint(y), -32768, 32767).astype(np.int16)
+
+
+# ---- stateful stream ingest (include/owwhip.h: oww_ingest_configure / oww_ingest): G.711 decode and continuous conversion ----------
+ENCODINGS = {"pcm16": 0, "ulaw": 1, "alaw": 2}          # OWW_ENC_PCM16 / OWW_ENC_ULAW / OWW_ENC_ALAW
+
+
+def decode_ulaw(codes) -> np.ndarray:
+    """G.711 mu-law bytes -> int16 (audioop.ulaw2lin): u = ~b; t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7); 0x84 - t if u & 0x80 else t - 0x84."""
+    u = (~np.asarray(codes).astype(np.int32)) & 0xFF
+    t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7)
+    return np.where(u & 0x80, 0x84 - t, t - 0x84).astype(np.int16)
+
+
+def decode_alaw(codes) -> np.ndarray:
+    """G.711 A-law bytes -> int16 (audioop.alaw2lin): a = b ^ 0x55; t = (a & 15) << 4; seg = (a >> 4) & 7; seg 0: t + 8, seg 1: t + 0x108,
+    else (t + 0x108) << (seg - 1); positive if a & 0x80."""
+    a = (np.asarray(codes).astype(np.int32) ^ 0x55) & 0xFF
+    t = (a & 15) << 4
+    seg = (a >> 4) & 7
+    t = np.where(seg == 0, t + 8, np.where(seg == 1, t + 0x108, (t + 0x108) << np.maximum(seg - 1, 0)))
+    return np.where(a & 0x80, t, -t).astype(np.int16)
+
+
+def decode(data, encoding: str) -> np.ndarray:
+    """A message in one of ENCODINGS -> int16."""
+    if encoding not in ENCODINGS:
+        raise ValueError(f"unknown encoding {encoding!r} (one of {sorted(ENCODINGS)})")
+    if encoding == "pcm16":
+        return np.asarray(data).astype(np.int16)
+    return decode_ulaw(data) if encoding == "ulaw" else decode_alaw(data)
+
+
+def ingest_numpy(x_decoded: np.ndarray, rate: int, history: np.ndarray = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Host restatement of one oww_ingest message in float64, BEFORE rounding: decoded samples [..., n_in] at `rate` Hz and the
+    stream's history [..., n_taps - 1] (the decoded samples before this message, oldest first; None = a fresh stream: zeros) ->
+    (y float64 [..., n_in * q / p], new history).  The caller rounds: np.clip(np.rint(y), -32768, 32767).  With X = history | message,
+    y[j] = sum_k taps[(j p) % q][k] * X[(j p) // q + k]: every message starts at phase 0, so n_in * q must be a multiple of p."""
+    p, q, taps = design(rate)
+    x = np.asarray(x_decoded, dtype=np.float64)
+    n_in, n_taps = x.shape[-1], taps.shape[1]
+    if (n_in * q) % p:
+        raise ValueError(f"a message must hold a whole number of output samples: n_in * q = {n_in} * {q} is no multiple of p = {p}")
+    if history is None:
+        history = np.zeros(x.shape[:-1] + (n_taps - 1,), np.float64)
+    ext = np.concatenate([np.asarray(history, np.float64), x], axis=-1)
+    jp = np.arange((n_in * q) // p, dtype=np.int64) * p
+    idx = (jp // q)[:, None] + np.arange(n_taps)[None, :]                  # [n_out, n_taps] into ext
+    y = (ext[..., idx] * taps[jp % q].astype(np.float64)).sum(-1)
+    return y, ext[..., ext.shape[-1] - (n_taps - 1):]
