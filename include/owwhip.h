@@ -131,7 +131,7 @@ int  oww_set_postproc(oww_ctx* h, const int32_t* patience, const float* threshol
  * (T x 96 values, oldest row first).  Scaler and regression fold into one affine map, which is what this entry takes:
  * w[T*96] = coef / scale, bias = intercept - sum(coef * mean / scale); the label then reads sigmoid(w . features + bias)
  * (= predict_proba(...)[0][-1]) whenever its head output is >= threshold, before the post-processing rules.  w == NULL removes
- * the label's verifier.  Host pointers; call after oww_commit. */
+ * the label's verifier.  Weights and bias must be finite (OWW_EINVAL, as oww_verifier_add).  Host pointers; call after oww_commit. */
 int  oww_set_verifier(oww_ctx* h, int32_t label, const float* w, int32_t n_w, float bias, float threshold);
 
 /* ---- VAD gate of Model.predict (model.py:366-381) for the batched path -------------------------------------------------

@@ -2266,6 +2266,10 @@ int oww_set_verifier(oww_ctx* h, int32_t label, const float* w, int32_t n_w, flo
     int T = 0;                                         // feature rows of the model that owns this label
     for (const auto& hh : h->heads) if (label >= hh.out_col && label < hh.out_col + hh.n_out) T = hh.T;
     if (w && n_w != T * OWW_EMB_DIM) return fail(OWW_EINVAL, "oww_set_verifier: %d weights given, the label's model has %d x 96 = %d features", n_w, T, T * OWW_EMB_DIM);
+    if (w) {                                           // (as oww_verifier_add: a NaN or an infinity would re-score every hit to NaN, 0 or 1)
+        for (int i = 0; i < n_w; ++i) if (!std::isfinite(w[i])) return fail(OWW_EINVAL, "oww_set_verifier: weight %d is not finite", i);
+        if (!std::isfinite(bias)) return fail(OWW_EINVAL, "oww_set_verifier: the bias is not finite");
+    }
     if (!h->d_verw) {
         int maxT = 1;
         for (const auto& hh : h->heads) maxT = std::max(maxT, hh.T);

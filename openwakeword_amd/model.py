@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import os
 import pickle
+import warnings
 import wave
 from collections import defaultdict, deque
 from functools import partial
@@ -135,9 +136,33 @@ def resolve_embedding(embedding: Optional[dict], seed: Optional[int], embedding_
     raise ValueError(f"{path} does not exist; pass weights='synthetic' for random-init weights of the same architecture")
 
 
+class VerifierFoldWarning(UserWarning):
+    """fold_verifier: the folded verifier's device score is predicted to leave the pipeline's by more than the 1e-4 score class."""
+
+
+SCORE_CLASS = 1e-4           # the parity class of scores (DESIGN.md 3)
+# max |z_fp32 - z_float64| / (sum |w_i x_i| + |b|) of the verifier kernels' summation order, in units of 2^-24: the largest of
+# tests/verifier_budget.py::E32 (tests/test_verifier_budget_cpu.py::test_e32_and_a_are_the_measured_envelope measures it, and
+# test_model_constant_is_the_budget_s holds this copy to it)
+VERIFIER_E32 = 1.35
+
+
+def verifier_fold_deviation(w, b, mean, scale):
+    """(predicted |device score - pipeline score|, kappa_hat, the three feature indices that carry most of it) of a folded verifier.
+    kappa_hat = sum |w_i| (|mean_i| + scale_i) + |b| is the mass the device's fp32 sum has to cancel on data the scaler was fitted
+    to; the fp32 rounding of w and b moves the logit by up to 4 * 2^-24 * kappa_hat, the device's summation by 4 * VERIFIER_E32 * 2^-24
+    * kappa_hat, and the sigmoid passes on a quarter of that."""
+    mass = np.abs(np.asarray(w, np.float64)) * (np.abs(np.asarray(mean, np.float64)) + np.asarray(scale, np.float64))
+    kappa_hat = float(mass.sum() + abs(b))
+    return 0.25 * (4.0 * VERIFIER_E32 + 4.0) * 2.0 ** -24 * kappa_hat, kappa_hat, np.argsort(-mass, kind="stable")[:3]
+
+
 def fold_verifier(verifier):
     """(w, bias) of a custom verifier: the reference's scikit-learn pipeline FunctionTransformer(flatten) -> StandardScaler ->
-    LogisticRegression (custom_verifier_model.py:95-113) folded into one affine map, or a ready (w, bias) pair."""
+    LogisticRegression (custom_verifier_model.py:95-113) folded into one affine map, or a ready (w, bias) pair.  The fold removes the
+    scaler's centring, so the device's fp32 sum has to cancel sum w_i x_i against the bias: where that is predicted to cost more than
+    the 1e-4 score class (a feature column that was nearly constant in the training data: a tiny scale_ next to a large mean_), a
+    VerifierFoldWarning names the columns.  The result is the same either way."""
     if isinstance(verifier, (tuple, list)) and len(verifier) == 2:
         return np.asarray(verifier[0], np.float32).ravel(), float(verifier[1])
     steps = getattr(verifier, "steps", None)
@@ -166,6 +191,14 @@ def fold_verifier(verifier):
             raise ValueError(f"verifier pipeline: scaler has {scale.size} features, the classifier {coef.size}")
         b -= float(np.sum(coef * mean / scale))
         coef = coef / scale
+        dev, kappa_hat, worst = verifier_fold_deviation(coef.astype(np.float32), b, mean, scale)
+        if dev > SCORE_CLASS:
+            warnings.warn(f"custom verifier: the device score may differ from the pipeline's by about {dev:.1e} (more than {SCORE_CLASS:g}): the "
+                          f"folded map has to cancel a mass of {kappa_hat:.3g} in fp32.  Largest contributions: features "
+                          f"{', '.join(str(int(i)) for i in worst)} (scale_ = {', '.join(f'{scale[i]:.3g}' for i in worst)}; mean_ = "
+                          f"{', '.join(f'{mean[i]:.3g}' for i in worst)}); a column that was nearly constant in training (a tiny scale_ "
+                          "next to a large mean_) is the usual cause: drop it before fitting, or keep the host-side hook of "
+                          "openwakeword_amd.Model", VerifierFoldWarning, stacklevel=2)
     return coef.astype(np.float32), b
 
 
