@@ -19,6 +19,7 @@
 
 #include "owwhip.h"
 #include "owwhip_pack.h"
+#include "owwhip_mem.h"
 #include "owwhip_kernels.h"
 #include "owwhip_rr.h"
 #include "owwhip_hx.h"
@@ -29,6 +30,8 @@
 
 using namespace owk;
 using namespace owp;
+using owm::DevBuf;
+using owm::PinnedBuf;
 
 namespace {
 
@@ -89,10 +92,9 @@ hipError_t guard_alloc(void** p, size_t n, int line) {
     *p = user;
     return hipSuccess;
 }
-template <class T>
-hipError_t dev_alloc(T** p, size_t n, int line = __builtin_LINE()) {
-    if (!guard_mode()) return hipMalloc(reinterpret_cast<void**>(p), n);
-    return guard_alloc(reinterpret_cast<void**>(p), n, line);
+hipError_t dev_alloc(void** p, size_t n, int line) {
+    if (!guard_mode()) return hipMalloc(p, n);
+    return guard_alloc(p, n, line);
 }
 hipError_t dev_free(void* p) {
     if (!guard_mode() || !p) return hipFree(p);
@@ -110,13 +112,29 @@ hipError_t dev_free(void* p) {
     (void)hipMemRelease(g.hnd);
     return hipMemAddressFree(g.base, g.reserve);
 }
+}  // namespace
+
+// ---- owwhip_mem.h's seam: what DevBuf / PinnedBuf / Event / Stream release goes through here and nowhere else
+namespace owm {
+int dev_alloc_raw(void** p, size_t bytes, int line) { return dev_alloc(p, bytes, line); }
+int dev_free_raw(void* p) { return dev_free(p); }
+int pinned_alloc_raw(void** p, size_t bytes, unsigned flags) { return hipHostMalloc(p, bytes, flags); }
+int pinned_free_raw(void* p) { return hipHostFree(p); }
+int event_create_raw(hipEvent_t* e, unsigned flags) { return hipEventCreateWithFlags(e, flags); }
+int event_destroy_raw(hipEvent_t e) { return hipEventDestroy(e); }
+int stream_create_raw(hipStream_t* s, unsigned flags) { return hipStreamCreateWithFlags(s, flags); }
+int stream_destroy_raw(hipStream_t s) { return hipStreamDestroy(s); }
+}  // namespace owm
+
+namespace {
+inline hipError_t herr(int e) { return static_cast<hipError_t>(e); }      // (the seam's codes are the runtime's)
 
 // Copies between host memory and a hipMemMap'ed range: the runtime's path for PAGEABLE host memory drops bytes at some sizes /
 // alignments (tools/experiments/vmm_copy_probe.hip: 5,000,000 bytes from a range that ends at its mapping's end), its pinned path does
 // not -- under OWW_GUARD_ALLOC host <-> device copies therefore go through a page-locked bounce buffer, synchronously.
 hipError_t guard_copy(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t st) {
-    void* pin = nullptr;
-    hipError_t e = hipHostMalloc(&pin, std::max<size_t>(n, 1), hipHostMallocDefault);
+    PinnedBuf<char> pin;
+    hipError_t e = herr(pin.alloc(n, hipHostMallocDefault));
     if (e != hipSuccess) return e;
     if (kind == hipMemcpyHostToDevice) {
         memcpy(pin, src, n);
@@ -127,7 +145,6 @@ hipError_t guard_copy(void* dst, const void* src, size_t n, hipMemcpyKind kind, 
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e == hipSuccess) memcpy(dst, pin, n);
     }
-    (void)hipHostFree(pin);
     return e;
 }
 inline hipError_t copy_async(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t st) {
@@ -144,8 +161,8 @@ inline hipError_t copy_sync(void* dst, const void* src, size_t n, hipMemcpyKind 
 constexpr int kSmallLaunchWgs = 2 * 256;      // stage / heads launches of at most two workgroups per CU (MI355X: 256 CUs) use the deep weight rings
 
 struct FastGroup : HeadGroup {           // + where bind_weights put the group's pieces on the device
-    NetDesc* d_nets = nullptr;
-    const float* d_w1pk = nullptr;
+    DevBuf<NetDesc> d_nets;
+    const float* d_w1pk = nullptr;    // (this and the next two: views into d_w)
     const float* d_b1cat = nullptr;
     const float* d_w1hx = nullptr;    // fp16-split k-step-major layer-1 weights (heads_hx_kernel)
     std::vector<owh::HeadHxNet> hx_net;   // per net: what the kernel reads behind the first layer (make_hx_net; built once at commit)
@@ -166,87 +183,87 @@ owh::HeadHxNet make_hx_net(const NetHost& n, int ht, const HxNetPack& p, const f
     return o;
 }
 
-struct EventRec { hipEvent_t a, b; int cls; };
+struct EventRec { owm::Event a, b; int cls = 0; };
 
 }  // namespace
 
 struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the family flags mfma / rr / hx, the f16-split scales)
+    // Teardown (~oww_ctx): the body drains the three streams and releases communicator and graph, then the members release themselves
+    // in reverse order of declaration -- the streams, declared first, go last.  stream: the caller's (cfg.stream, borrowed) or our own.
+    owm::Stream stream, up_stream, down_stream;   // (up / down: the host-fed pipeline's uploads and score downloads)
     oww_config cfg{};
     int S = 0, Spad = 0, kmax = 1, TR = 16, NL = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false, committed = false;
+    bool committed = false;
     const int* state_len = kStateLenRr;
-    // device weights
-    float* d_w = nullptr;
+    ~oww_ctx();
+    // device weights; the const pointers below are views into d_w
+    DevBuf<float> d_w;
     const float *d_hann = nullptr, *d_taps = nullptr;
     const int* d_mstart = nullptr;
     const int* d_meloff = nullptr; const unsigned* d_meldst = nullptr;   // fused front end: compact tap table (oww_commit)
     const float* d_conv[20] = {};     // layer 0: natural [9][24]; 1..19: packed (mfma) or natural (valu)
     const float* d_scale[20] = {};
     const float* d_shift[20] = {};
-    NetDesc* d_allnets = nullptr;
+    DevBuf<NetDesc> d_allnets;
     std::vector<FastGroup> groups;
     std::vector<int> generic_nets;    // indices into nets (with verifier right after its primary)
     std::vector<int> rnn_nets;        // recurrent heads (train.py:85-98): owk::heads_rnn_kernel, one launch per head
     int generic_hmax = 0;
     int generic_spw = 0;              // OWW_GENERIC_SPW: 4 / 16 pins the generic heads kernel's shape, 0 = by launch size
     // state
-    float* d_state[N_STATE] = {};
-    float* d_tmpl[N_STATE] = {};
-    float *d_xA = nullptr, *d_xB = nullptr, *d_xC = nullptr, *d_xD = nullptr;
-    float *d_mel = nullptr, *d_feat = nullptr, *d_emb = nullptr, *d_raw = nullptr, *d_scores = nullptr, *d_ring = nullptr;
+    DevBuf<float> d_state[N_STATE], d_tmpl[N_STATE];
+    DevBuf<float> d_xA, d_xB, d_xC, d_xD;
+    DevBuf<float> d_mel, d_feat, d_emb, d_raw, d_scores, d_ring;
     // host-fed pipeline (oww_submit / oww_collect): two steps in flight, uploads and score downloads on their own streams
     struct IngestSlot {
-        int16_t* d_pcm = nullptr; float* d_scores = nullptr; float* h_scores = nullptr;
-        uint8_t* h_on = nullptr;     // page-locked staging of a masked submit's participation mask
-        hipEvent_t up = nullptr, done = nullptr, down = nullptr;
+        DevBuf<int16_t> d_pcm; DevBuf<float> d_scores; PinnedBuf<float> h_scores;
+        PinnedBuf<uint8_t> h_on;     // page-locked staging of a masked submit's participation mask
+        owm::Event up, done, down;
         bool busy = false;
     } slot[2];
     // detection events (oww_events_*; owwhip_events.h): one buffer set for the synchronous calls and one per ingest slot, the latter
     // with page-locked mirrors of counts and records that ride down behind the slot's scores
     struct EventBuf {
-        oww_event* d_rec = nullptr; int* d_count = nullptr; float* d_snap = nullptr;     // [cap + 1], {n_stored, n_total}, [cap + 1][rows][96]
-        oww_event* h_rec = nullptr; int* h_count = nullptr;                              // ingest slots only
+        DevBuf<oww_event> d_rec; DevBuf<int> d_count; DevBuf<float> d_snap;     // [cap + 1], {n_stored, n_total}, [cap + 1][rows][96]
+        PinnedBuf<oww_event> h_rec; PinnedBuf<int> h_count;                     // ingest slots only
     };
     int evt_cap = 0, evt_rows = 0;               // 0 = no events (oww_events_configure)
-    float* d_evt_thr = nullptr; float evt_bank_thr = 0.5f;
-    int* d_evblock = nullptr; int evt_blocks = 0;
+    DevBuf<float> d_evt_thr; float evt_bank_thr = 0.5f;
+    DevBuf<int> d_evblock; int evt_blocks = 0;
     EventBuf evt_sync, evt_slot[2];
     const EventBuf* evt_cur = nullptr;           // what oww_get_events refers to: the last synchronous call or the last collected step
 
-    hipStream_t up_stream = nullptr, down_stream = nullptr;
     uint64_t n_submit = 0, n_collect = 0;
-    float* d_featinit = nullptr;
-    float* d_dbg = nullptr;
-    long long* d_prof = nullptr;     // [4 stages][16 waves][16 marks], allocated when OWW_PROF_BLOCK is set
+    DevBuf<float> d_featinit, d_dbg;
+    DevBuf<long long> d_prof;        // [4 stages][16 waves][16 marks], allocated when OWW_PROF_BLOCK is set
     int prof_block = -1;
-    uint32_t *d_nfeat = nullptr, *d_npred = nullptr;
-    float* d_vadring = nullptr; uint32_t* d_nvad = nullptr; float* d_vadin = nullptr; float vad_threshold = 0.f;   // VAD gate (oww_push_vad)
+    DevBuf<uint32_t> d_nfeat, d_npred, d_nvad;
+    DevBuf<float> d_vadring, d_vadin; float vad_threshold = 0.f;   // VAD gate (oww_push_vad)
     // voice-activity stand-in network on the device (oww_load_vad; owwhip_vad.h)
     bool vad = false;
     const float *d_vad_hann = nullptr, *d_vad_encw = nullptr, *d_vad_encb = nullptr, *d_vad_lstmw = nullptr, *d_vad_lstmb = nullptr, *d_vad_wd = nullptr;
     float vad_bd = 0.f, vad_gain = 50.f;
-    float *d_vadx = nullptr, *d_vadhc = nullptr, *d_vadlast = nullptr;
-    int16_t *d_tail = nullptr, *d_pcm = nullptr;
-    int16_t* d_long = nullptr; size_t long_cap = 0;      // oww_step with n_chunks > max_chunks: the whole call's PCM when it arrives from the host
-    float* d_callmax = nullptr;                          // ... and the call's per-stream mel maximum (launch_step_long)
-    int* h_range = nullptr;          // sticky f16-range flag: one page-locked, device-mapped word the f16-split kernels raise
-    int* d_range = nullptr;          // the same word as the kernels address it
-    void* d_rs = nullptr; size_t rs_bytes = 0;     // oww_resample scratch: [taps | in | out] as needed
+    DevBuf<float> d_vadx, d_vadhc, d_vadlast;
+    DevBuf<int16_t> d_tail, d_pcm;
+    DevBuf<int16_t> d_long;          // oww_step with n_chunks > max_chunks: the whole call's PCM when it arrives from the host
+    DevBuf<float> d_callmax;         // ... and the call's per-stream mel maximum (launch_step_long)
+    PinnedBuf<int> h_range;          // sticky f16-range flag: one page-locked, device-mapped word the f16-split kernels raise
+    int* d_range = nullptr;          // the same word as the kernels address it (a view: the device alias of h_range)
+    DevBuf<char> d_rs;               // oww_resample scratch: [taps | in | out] as needed, in bytes
     std::vector<float> rs_taps;                    // the padded filter bank of the last oww_resample call (upload source)
     // stateful stream ingest (oww_ingest_configure / oww_ingest / oww_step_ingest; owk::ingest_kernel): nothing before the first configure
     bool ing_ready = false;
     int ing_enc = 0, ing_p = 1, ing_q = 1, ing_n_taps = 0, ing_ntp = 0, ing_Hpad = 0;
     std::vector<float> ing_taps;                   // the padded bank [q][ntp] (upload source, fingerprint)
-    float* d_ing_taps = nullptr;
-    int16_t* d_ing_hist = nullptr;                 // [S][Hpad]: each stream's last n_taps - 1 decoded samples, oldest first, zero padded
-    int16_t* d_ing_out = nullptr; size_t ing_out_cap = 0;      // 16 kHz staging [S][n_out] (oww_ingest_dev), grown on demand
-    void* d_ing_in = nullptr; size_t ing_in_cap = 0;           // a host message on its way in
-    uint8_t* d_ing_on = nullptr;                   // [S] a host mask on its way in
-    uint8_t* d_on = nullptr;         // oww_step_masked: [Spad] participation mask of the step being launched (pad streams 0)
+    DevBuf<float> d_ing_taps;
+    DevBuf<int16_t> d_ing_hist;                    // [S][Hpad]: each stream's last n_taps - 1 decoded samples, oldest first, zero padded
+    DevBuf<int16_t> d_ing_out;                     // 16 kHz staging [S][n_out] (oww_ingest_dev), grown on demand
+    DevBuf<char> d_ing_in;                         // a host message on its way in, in bytes
+    DevBuf<uint8_t> d_ing_on;                      // [S] a host mask on its way in
+    DevBuf<uint8_t> d_on;            // oww_step_masked: [Spad] participation mask of the step being launched (pad streams 0)
     // masked step with few participants: the device copy of the group lists (StepArgs::gl) and its two page-locked staging buffers,
     // used in turn (build_active_lists)
-    int* d_lists = nullptr; int* h_lists[2] = {nullptr, nullptr}; hipEvent_t lists_ev[2] = {nullptr, nullptr}; size_t lists_cap = 0; unsigned lists_turn = 0;
+    DevBuf<int> d_lists; PinnedBuf<int> h_lists[2]; owm::Event lists_ev[2]; unsigned lists_turn = 0;
     int k_last = 1;                  // n_chunks of the last step (row stride of d_mel)
     float hx_absmax[20] = {};        // largest |activation| of each layer in the calibration run (exact-fp32 kernels)
     std::vector<int16_t> cal_user;   // oww_set_calibration: caller's calibration audio as [n_seg][CAL_T * 1280] segments
@@ -254,15 +271,14 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     float hx_selftest_err = 0.f, hx_selftest_ref = 0.f, hx_selftest_score_err = 0.f;   // commit-time f16-split vs exact-fp32 comparison
     bool fuse = false;               // f16-split family: mel front end fused into stage A for one-chunk streaming steps (owwhip_fused.h)
     // custom verifiers on the device (oww_set_verifier)
-    float *d_verw = nullptr, *d_verb = nullptr, *d_verthr = nullptr; int* d_verT = nullptr;
+    DevBuf<float> d_verw, d_verb, d_verthr; DevBuf<int> d_verT;
     int ver_stride = 0, n_verifiers = 0;
     std::vector<int> ver_T;
     bool post_in_heads = false;          // one group of sigmoid heads covers every label: post-processing + counter advance ride in the heads launch
-    float* d_save = nullptr; size_t save_floats = 0;      // streaming state parked by oww_embed / oww_embed_clips
-    int* d_ids = nullptr;
-    int ids_cap = 0;
-    int *d_patience = nullptr;
-    float* d_threshold = nullptr;
+    DevBuf<float> d_save;                // streaming state parked by oww_embed / oww_embed_clips
+    DevBuf<int> d_ids;                   // the stream ids of oww_reset / oww_reset_vad (upload_ids)
+    DevBuf<int> d_patience;
+    DevBuf<float> d_threshold;
     int debounce_frames = 0;
     // RCCL communicator of oww_comm_init (multi-GPU delivery of results without Python)
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;
@@ -281,18 +297,18 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
         bool live = false;
         int T = 0, hidden = 0, has_ln = 0, ht = 4, patience = 0;
         float threshold = NAN;
-        float* d_img = nullptr;                  // w1hx | the pieces of pack_hx_net: the packing of a fixed net of the same width
+        DevBuf<float> d_img;                     // w1hx | the pieces of pack_hx_net: the packing of a fixed net of the same width
         size_t w1_bytes = 0;                     // first-layer weight bytes one tile streams
         owh::BankHeadDev dev{};
     };
     int bank_K = 0, bank_cap = 0;                // 0 = no bank (oww_bank_configure)
     std::vector<BankHead> bank;
     std::vector<int> bank_sub;                   // host copy of d_bank_sub: [S][K] bank head per slot, -1 = empty
-    int* d_bank_sub = nullptr; int* d_bank_idx = nullptr;
-    float *d_bank_raw = nullptr, *d_bank_scores = nullptr, *d_bank_ring = nullptr;
-    uint32_t* d_bank_npred = nullptr;
-    owh::BankHeadDev* d_bank_heads = nullptr; int* d_bank_pat = nullptr; float* d_bank_thr = nullptr;
-    owh::BankTile* d_bank_tiles = nullptr; int* d_bank_entries = nullptr; size_t bank_tiles_cap = 0;
+    DevBuf<int> d_bank_sub, d_bank_idx;
+    DevBuf<float> d_bank_raw, d_bank_scores, d_bank_ring;
+    DevBuf<uint32_t> d_bank_npred;
+    DevBuf<owh::BankHeadDev> d_bank_heads; DevBuf<int> d_bank_pat; DevBuf<float> d_bank_thr;
+    DevBuf<owh::BankTile> d_bank_tiles; DevBuf<int> d_bank_entries;
     // routing table, per width class (0: <= 64 hidden units, 1: <= 128): tiles [tile0, tile0 + ntiles) of d_bank_tiles, WG waves each
     int bank_ntiles[2] = {}, bank_tile0[2] = {}, bank_wg[2] = {1, 1}, bank_entries_n[2] = {};
     std::vector<std::pair<int, int>> bank_head_tiles[2];   // OWH_BANK_PER_HEAD builds: [first tile, count] of every subscribed head
@@ -302,23 +318,23 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     int vpool_cap = 0;                           // 0 = not configured (oww_verifier_configure)
     int vpool_stride = 0;                        // floats per pool entry: feature ring x 96
     std::vector<int> vpool_T;                    // [cap] feature rows of each pool verifier; 0 = free
-    float *d_vpool_w = nullptr, *d_vpool_b = nullptr;
+    DevBuf<float> d_vpool_w, d_vpool_b;
     std::vector<int> vasg_fix, vasg_bank;        // [S][NL], [S][K]: pool id, OWW_VERIFIER_DEFAULT or OWW_VERIFIER_NONE
     std::vector<float> vthr_fix, vthr_bank;      // thresholds of the pool assignments
     long long vasg_n = 0;                        // pairs whose assignment is not the default: > 0 switches to stream_verifier_kernel
     std::vector<float> ver_thr;                  // host copy of d_verthr (the handle-wide verifiers' thresholds)
-    SvEntry* d_svlist = nullptr; int sv_n = 0;   // [S * (NL + K)] capacity; sv_n entries in use
-    unsigned long long* d_sv_eval = nullptr;     // evaluations of the last step
+    DevBuf<SvEntry> d_svlist; int sv_n = 0;      // [S * (NL + K)] capacity; sv_n entries in use
+    DevBuf<unsigned long long> d_sv_eval;        // evaluations of the last step
     // stream state records (oww_state_*, oww_move_streams; owwhip_state.h): built by the first of those calls, nothing before it
-    struct StateGroupSec { float* live; int spg, ppr; bool il; uint32_t block_words, off; };
+    struct StateGroupSec { float* live /* a view */; int spg, ppr; bool il; uint32_t block_words, off; };
     bool st_ready = false;
     std::vector<ows::FlatSection> st_flat;       // host copy of d_st_flat
     std::vector<StateGroupSec> st_group;
-    ows::FlatSection* d_st_flat = nullptr;
+    DevBuf<ows::FlatSection> d_st_flat;
     uint32_t st_record_words = 0, st_flat_quads = 0;
     uint64_t st_fp = 0;                          // fingerprint of family, layouts, ring sizes, scales and weights
-    int* d_st_items = nullptr; size_t st_items_cap = 0;      // [ids | group items per level] of the call being served
-    uint32_t* d_st_stage = nullptr; size_t st_stage_words = 0;   // records in flight between a host buffer / the two halves of a move
+    DevBuf<int> d_st_items;                      // [ids | group items per level] of the call being served
+    DevBuf<uint32_t> d_st_stage;                 // records in flight between a host buffer / the two halves of a move
 };
 
 namespace {
@@ -362,9 +378,9 @@ struct Timed {          // RAII: records a start event now and a stop event at s
         if (h->ev_used == h->ev.size()) {
             if (h->ev.size() >= 8192) { flush_events(h); }
             else {
-                EventRec e{};
-                if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return;
-                h->ev.push_back(e);
+                EventRec e;
+                if (e.a.create(hipEventDefault) || e.b.create(hipEventDefault)) return;
+                h->ev.push_back(std::move(e));
             }
         }
         r = &h->ev[h->ev_used++];
@@ -656,14 +672,25 @@ int do_reset(oww_ctx* h, const int* d_ids, int n, const float* d_featinit) {
     return 0;
 }
 
+// one-shot allocation of max(n, 1) elements, zero-filled unless told otherwise
 template <class T>
-int dalloc(hipStream_t st, T** p, size_t n, bool zero = true, int line = __builtin_LINE()) {
-    HIPCHK(dev_alloc(p, std::max<size_t>(n, 1) * sizeof(T), line));
+int dalloc(hipStream_t st, DevBuf<T>& b, size_t n, bool zero = true, int line = __builtin_LINE()) {
+    HIPCHK(herr(b.alloc(n, line)));
     // the zero fill runs ON THE HANDLE'S STREAM: ordered in front of every kernel the handle will launch on it (its other streams are
     // forked from it by events), and no host round trip per buffer -- a legacy-stream fill would need one, because nothing orders
     // the handle's non-blocking streams behind the legacy stream (round 4: ~90 synchronisations per handle creation)
-    if (zero) HIPCHK(hipMemsetAsync(*p, 0, std::max<size_t>(n, 1) * sizeof(T), st));
+    if (zero) HIPCHK(hipMemsetAsync(b, 0, b.capacity() * sizeof(T), st));
     return 0;
+}
+
+// The one growth rule of the handle's scratch buffers.  n elements fit: nothing happens, no synchronisation (every hot-path call).
+// Otherwise the handle's stream is drained -- queued work may still read the old block; hipFree would wait for it as well, this says
+// so -- and the buffer becomes exactly n elements, contents not kept; on failure it is empty.  The caller words the error.
+template <class T>
+hipError_t grow(oww_ctx* h, DevBuf<T>& b, size_t n, int line = __builtin_LINE()) {
+    if (n <= b.capacity()) return hipSuccess;
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    return e != hipSuccess ? e : herr(b.reserve(n, line));
 }
 
 // ---- RCCL (librccl.so: ncclSend / ncclRecv over xGMI), bound at run time: the library is only needed by callers that shard streams
@@ -711,64 +738,6 @@ int rccl_load() {
         if (e__ != 0) return fail(OWW_EHIP, "%s failed: %s", #expr, g_rccl.GetErrorString ? g_rccl.GetErrorString(e__) : "?"); \
     } while (0)
 void comm_release(oww_ctx* h);
-
-void free_all(oww_ctx* h) {
-    // Nothing of this handle may still be queued when its buffers go: every stream the handle ever launched on is drained first
-    // (hipFree would wait for the whole device as well, but the page-locked words -- h_range, which the f16-split kernels write at
-    // exit, h_lists, the ingest slots -- and the streams and events themselves are released by calls that promise no such wait).
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipStream_t st : {h->up_stream, h->down_stream})
-        if (st) (void)hipStreamSynchronize(st);
-    auto fr = [](auto*& p) { if (p) { (void)dev_free((void*)p); p = nullptr; } };
-    fr(h->d_w); fr(h->d_allnets);
-    for (auto& g : h->groups) fr(g.d_nets);
-    for (int a = 0; a < N_STATE; ++a) { fr(h->d_state[a]); fr(h->d_tmpl[a]); }
-    fr(h->d_xA); fr(h->d_xB); fr(h->d_xC); fr(h->d_xD); fr(h->d_mel); fr(h->d_feat); fr(h->d_emb); fr(h->d_raw);
-    fr(h->d_scores); fr(h->d_ring); fr(h->d_featinit); fr(h->d_dbg); fr(h->d_nfeat); fr(h->d_npred); fr(h->d_tail); fr(h->d_vadring); fr(h->d_nvad); fr(h->d_vadin); fr(h->d_vadx); fr(h->d_vadhc); fr(h->d_vadlast); fr(h->d_verw); fr(h->d_verb); fr(h->d_verthr); fr(h->d_verT);
-    fr(h->d_prof); fr(h->d_pcm); fr(h->d_ids); fr(h->d_patience); fr(h->d_threshold); fr(h->d_save); fr(h->d_long); fr(h->d_callmax);
-    h->long_cap = 0;
-    h->save_floats = 0;
-    if (h->d_on) { (void)dev_free(h->d_on); h->d_on = nullptr; }
-    if (h->d_lists) { (void)dev_free(h->d_lists); h->d_lists = nullptr; }
-    for (int i = 0; i < 2; ++i) {
-        if (h->h_lists[i]) { (void)hipHostFree(h->h_lists[i]); h->h_lists[i] = nullptr; }
-        if (h->lists_ev[i]) { (void)hipEventDestroy(h->lists_ev[i]); h->lists_ev[i] = nullptr; }
-    }
-    h->lists_cap = 0;
-    if (h->d_rs) { (void)dev_free(h->d_rs); h->d_rs = nullptr; h->rs_bytes = 0; }
-    fr(h->d_ing_taps); fr(h->d_ing_hist); fr(h->d_ing_out); fr(h->d_ing_in); fr(h->d_ing_on);
-    h->ing_out_cap = 0; h->ing_in_cap = 0; h->ing_ready = false;
-    if (h->h_range) { (void)hipHostFree(h->h_range); h->h_range = nullptr; h->d_range = nullptr; }
-    for (auto& sl : h->slot) {
-        fr(sl.d_pcm); fr(sl.d_scores);
-        if (sl.h_scores) { (void)hipHostFree(sl.h_scores); sl.h_scores = nullptr; }
-        if (sl.h_on) { (void)hipHostFree(sl.h_on); sl.h_on = nullptr; }
-        for (hipEvent_t* e : {&sl.up, &sl.done, &sl.down}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
-        sl.busy = false;
-    }
-    if (h->up_stream) { (void)hipStreamDestroy(h->up_stream); h->up_stream = nullptr; }
-    if (h->down_stream) { (void)hipStreamDestroy(h->down_stream); h->down_stream = nullptr; }
-    for (auto& e : h->ev) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    h->ev.clear();
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-    for (auto& b : h->bank) fr(b.d_img);
-    fr(h->d_bank_sub); fr(h->d_bank_idx); fr(h->d_bank_raw); fr(h->d_bank_scores); fr(h->d_bank_ring); fr(h->d_bank_npred);
-    fr(h->d_bank_heads); fr(h->d_bank_pat); fr(h->d_bank_thr); fr(h->d_bank_tiles); fr(h->d_bank_entries);
-    h->bank_tiles_cap = 0;
-    fr(h->d_vpool_w); fr(h->d_vpool_b); fr(h->d_svlist); fr(h->d_sv_eval);
-    h->sv_n = 0;
-    fr(h->d_st_flat); fr(h->d_st_items); fr(h->d_st_stage);
-    h->st_items_cap = 0; h->st_stage_words = 0; h->st_ready = false;
-    for (oww_ctx::EventBuf* b : {&h->evt_sync, &h->evt_slot[0], &h->evt_slot[1]}) {
-        fr(b->d_rec); fr(b->d_count); fr(b->d_snap);
-        if (b->h_rec) { (void)hipHostFree(b->h_rec); b->h_rec = nullptr; }
-        if (b->h_count) { (void)hipHostFree(b->h_count); b->h_count = nullptr; }
-    }
-    fr(h->d_evt_thr); fr(h->d_evblock);
-    h->evt_cur = nullptr;
-    comm_release(h);
-}
 
 // ---- head bank: the routed heads launch (one per width class that has subscribers) and its post-processing
 bool bank_active(const oww_ctx* h) { return h->bank_ntiles[0] + h->bank_ntiles[1] > 0; }
@@ -897,20 +866,13 @@ int build_active_lists(oww_ctx* h, const uint8_t* on, StepArgs& a) {
     if (!h->hx || !h->fuse || !h->generic_nets.empty() || !h->rnn_nets.empty()) return -1;       // the group lists are read by the default family's launches only
     if ((long long)n_act * 8 > (long long)S * 7) return -1;
     const size_t need = (size_t)S + S / 2 + S / 4 + S / 8 + S / 16 + 64;       // (regions of the five lists, see below)
-    if (need > h->lists_cap) {
-        if (h->d_lists) (void)dev_free(h->d_lists);
-        h->d_lists = nullptr;
-        for (int i = 0; i < 2; ++i) {
+    if (grow(h, h->d_lists, need) != hipSuccess) return fail(OWW_ENOMEM, "oww_step_masked: out of device memory") - 100;
+    for (int i = 0; i < 2; ++i) {
+        if (need > h->h_lists[i].capacity()) {                    // (its own double buffering: the copy that read the old block has run)
             if (h->lists_ev[i]) (void)hipEventSynchronize(h->lists_ev[i]);
-            if (h->h_lists[i]) { (void)hipHostFree(h->h_lists[i]); h->h_lists[i] = nullptr; }
+            if (h->h_lists[i].reserve(need, hipHostMallocDefault)) return fail(OWW_ENOMEM, "oww_step_masked: out of page-locked memory") - 100;
         }
-        h->lists_cap = 0;
-        if (dev_alloc(&h->d_lists, need * sizeof(int)) != hipSuccess) return fail(OWW_ENOMEM, "oww_step_masked: out of device memory") - 100;
-        for (int i = 0; i < 2; ++i) {
-            if (hipHostMalloc((void**)&h->h_lists[i], need * sizeof(int), hipHostMallocDefault) != hipSuccess) return fail(OWW_ENOMEM, "oww_step_masked: out of page-locked memory") - 100;
-            if (!h->lists_ev[i] && hipEventCreateWithFlags(&h->lists_ev[i], hipEventDisableTiming) != hipSuccess) return fail(OWW_EHIP, "hipEventCreate failed") - 100;
-        }
-        h->lists_cap = need;
+        if (!h->lists_ev[i] && h->lists_ev[i].create(hipEventDisableTiming)) return fail(OWW_EHIP, "hipEventCreate failed") - 100;
     }
     const unsigned turn = h->lists_turn++ & 1u;
     (void)hipEventSynchronize(h->lists_ev[turn]);              // the copy that last read this staging buffer has run
@@ -988,7 +950,7 @@ int launch_step(oww_ctx* h, const StepArgs& args, const int16_t* d_pcm, int k) {
 // chunks of the call -- and one post-processing pass.  d_pcm: [S][1280 K] on the device.
 int launch_step_long(oww_ctx* h, const StepArgs& a, const int16_t* d_pcm, int K) {
     if (h->vad) return fail(OWW_EINVAL, "with the on-device VAD network a step carries exactly one 1280-sample chunk per stream (got %d)", K);
-    if (!h->d_callmax) if (int rc = dalloc(h->stream, &h->d_callmax, (size_t)h->Spad)) return rc;
+    if (!h->d_callmax) if (int rc = dalloc(h->stream, h->d_callmax, (size_t)h->Spad)) return rc;
     if (int rc = launch_mel(h, a, d_pcm, h->S, OWW_CHUNK * K, 8 * K, 1, nullptr, h->d_callmax, 0, 1, nullptr)) return rc;
     for (int o = 0; o < K; o += h->kmax) {
         const int ks = std::min(h->kmax, K - o);
@@ -1021,12 +983,12 @@ bool events_on(const oww_ctx* h) { return h->evt_cap > 0; }
 
 // device buffers of one set: records and snapshots with one spare entry behind the capacity (never written), counts zeroed
 int alloc_event_buf(oww_ctx* h, oww_ctx::EventBuf& b, bool host_mirror) {
-    if (int rc = dalloc(h->stream, &b.d_rec, (size_t)h->evt_cap + 1)) return rc;
-    if (int rc = dalloc(h->stream, &b.d_count, 2)) return rc;
-    if (h->evt_rows > 0) if (int rc = dalloc(h->stream, &b.d_snap, ((size_t)h->evt_cap + 1) * h->evt_rows * OWW_EMB_DIM, false)) return rc;
+    if (int rc = dalloc(h->stream, b.d_rec, (size_t)h->evt_cap + 1)) return rc;
+    if (int rc = dalloc(h->stream, b.d_count, 2)) return rc;
+    if (h->evt_rows > 0) if (int rc = dalloc(h->stream, b.d_snap, ((size_t)h->evt_cap + 1) * h->evt_rows * OWW_EMB_DIM, false)) return rc;
     if (host_mirror) {
-        HIPCHK(hipHostMalloc((void**)&b.h_rec, (size_t)h->evt_cap * sizeof(oww_event), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc((void**)&b.h_count, 2 * sizeof(int), hipHostMallocDefault));
+        HIPCHK(herr(b.h_rec.alloc((size_t)h->evt_cap, hipHostMallocDefault)));
+        HIPCHK(herr(b.h_count.alloc(2, hipHostMallocDefault)));
         b.h_count[0] = b.h_count[1] = 0;
     }
     return 0;
@@ -1036,8 +998,8 @@ int alloc_events(oww_ctx* h) {
     const long long pairs = (long long)h->S * (h->NL + h->bank_K);
     if (pairs > 0x7fffffffLL - owe::EV_WG) return fail(OWW_EINVAL, "oww_events_configure: %lld (stream, column) pairs are more than the event kernels index", pairs);
     h->evt_blocks = (int)((pairs + owe::EV_WG - 1) / owe::EV_WG);
-    if (int rc = dalloc(h->stream, &h->d_evblock, (size_t)std::max(h->evt_blocks, 1))) return rc;
-    if (int rc = dalloc(h->stream, &h->d_evt_thr, (size_t)std::max(h->NL, 1), false)) return rc;
+    if (int rc = dalloc(h->stream, h->d_evblock, (size_t)std::max(h->evt_blocks, 1))) return rc;
+    if (int rc = dalloc(h->stream, h->d_evt_thr, (size_t)std::max(h->NL, 1), false)) return rc;
     std::vector<float> half(std::max(h->NL, 1), 0.5f);
     HIPCHK(copy_async(h->d_evt_thr, half.data(), half.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     if (int rc = alloc_event_buf(h, h->evt_sync, false)) return rc;
@@ -1084,13 +1046,8 @@ int park_state(oww_ctx* h, int n_streams, bool save) {
     const size_t n8 = std::min<size_t>(h->Spad, ((size_t)n_streams + 7) / 8 * 8);
     size_t need = h->Spad + n8 * (size_t)h->TR * 96;
     for (int a = 0; a < N_STATE; ++a) need += n8 * (size_t)h->state_len[a];
-    if (save && need > h->save_floats) {
-        if (h->d_save) (void)dev_free(h->d_save);
-        h->d_save = nullptr; h->save_floats = 0;
-        if (dev_alloc(&h->d_save, need * sizeof(float)) != hipSuccess) return fail(OWW_ENOMEM, "out of device memory for %zu parked state bytes", need * sizeof(float));
-        h->save_floats = need;
-    }
-    if (!h->d_save || need > h->save_floats) return fail(OWW_ESTATE, "park_state: nothing parked");
+    if (save && grow(h, h->d_save, need) != hipSuccess) return fail(OWW_ENOMEM, "out of device memory for %zu parked state bytes", need * sizeof(float));
+    if (need > h->d_save.capacity()) return fail(OWW_ESTATE, "park_state: nothing parked");
     float* q = h->d_save;
     auto cp = [&](void* live, size_t nfl) -> int {
         HIPCHK(copy_async(save ? (void*)q : live, save ? live : (void*)q, nfl * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
@@ -1129,14 +1086,10 @@ constexpr int CAL_NP = 32, CAL_T = 16, CAL_MAX_BATCHES = 8;
 struct HxCalib {
     int nb = 1;                      // batches
     std::vector<int16_t> pcm;        // [nb][CAL_T][CAL_NP][1280]
-    int16_t* d_pcm = nullptr;        // the same on the device: uploaded once, read by the calibration run and by the self-test replay
+    DevBuf<int16_t> d_pcm;           // the same on the device: uploaded once, read by the calibration run and by the self-test replay
     std::vector<float> ref_emb;      // [nb][CAL_T][CAL_NP][96]   exact-fp32 embeddings of the probe run
     std::vector<float> ref_raw;      // [nb][CAL_T][CAL_NP][NL]   exact-fp32 raw head outputs
     int NL = 0;
-    HxCalib() = default;
-    HxCalib(const HxCalib&) = delete;
-    HxCalib& operator=(const HxCalib&) = delete;
-    ~HxCalib() { if (d_pcm) (void)dev_free(d_pcm); }
 };
 
 void make_probe_pcm(std::vector<int16_t>& pcm, const std::vector<int16_t>& user /*[n_seg][CAL_T * 1280]*/) {
@@ -1180,6 +1133,68 @@ int probe_step(oww_ctx* t, const StepArgs& a, const int16_t* d_chunk, bool heads
     return 0;
 }
 
+// a failure behind queued work: the stream is drained before the caller's local buffers are released at its return
+int drained(oww_ctx* h, int rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+
+// the probe run on the scratch exact-fp32 handle t: per-layer maxima into h, reference embeddings and raw scores into cal
+int calibrate_run(oww_ctx* h, oww_ctx* t, HxCalib& cal, CommitClock& clk) {
+    if (int rc = oww_load_mel(t, h->mel_blob.data(), h->mel_blob.size() * sizeof(float))) return rc;
+    if (int rc = oww_load_embedding(t, h->emb_blob.data(), h->emb_blob.size() * sizeof(float))) return rc;
+    for (const HeadHost& hh : h->heads) {
+        std::vector<float> blob(8 + hh.blob.size());
+        const int32_t hdr[8] = {hh.kind, hh.T, hh.hidden, hh.n_out, hh.has_ln, hh.n_blocks - 1, 0, 0};
+        memcpy(blob.data(), hdr, sizeof hdr);
+        memcpy(blob.data() + 8, hh.blob.data(), hh.blob.size() * sizeof(float));
+        if (int rc = oww_add_head(t, blob.data(), blob.size() * sizeof(float)); rc < 0) return rc;
+    }
+    if (int rc = oww_commit(t)) return rc;
+    clk.lap("scratch fp32 handle");
+    cal.NL = t->NL;
+    int off[21]; off[0] = 0;
+    for (int l = 0; l < 20; ++l) off[l + 1] = off[l] + kLayerOut[l][0] * kLayerOut[l][1] * kLayerOut[l][2];
+    // probe audio up once, results down once: the run in between is stream-ordered, without a host round trip per probe step
+    const size_t n_steps = (size_t)cal.nb * CAL_T, n_emb = n_steps * CAL_NP * 96, n_raw = n_steps * CAL_NP * std::max(t->NL, 1);
+    DevBuf<unsigned> d_max; DevBuf<int> d_off; DevBuf<float> d_ref;
+    if (d_max.alloc(20) || d_off.alloc(21) || cal.d_pcm.alloc(cal.pcm.size()) || d_ref.alloc(n_emb + n_raw))
+        return fail(OWW_ENOMEM, "oww_commit: out of device memory (calibration)");
+    if (hipMemsetAsync(d_max, 0, 20 * sizeof(unsigned), t->stream) != hipSuccess ||
+        copy_async(d_off, off, sizeof off, hipMemcpyHostToDevice, t->stream) != hipSuccess ||
+        copy_async(cal.d_pcm, cal.pcm.data(), cal.pcm.size() * sizeof(int16_t), hipMemcpyHostToDevice, t->stream) != hipSuccess)
+        return drained(t, fail(OWW_EHIP, "oww_commit: calibration setup failed"));
+    auto absmax = [&]() { hipLaunchKernelGGL(layer_absmax_kernel, dim3(20, CAL_NP), dim3(256), 0, t->stream, t->d_dbg, (size_t)DBG_FLOATS, d_off, d_max); };
+    // (a) the all-ones mel history every stream starts from (utils.py:165): the handle sits in that steady state after its commit
+    hipLaunchKernelGGL(fill_kernel, dim3(CAL_NP), dim3(256), 0, t->stream, t->d_mel, (size_t)CAL_NP * 256, 1.0f);
+    const StepArgs a = step_args(t);             // (every layer dumped: the maxima are read from t's debug buffer)
+    if (int rc = run_cnn(t, a, CAL_NP, 256, 0)) return drained(t, rc);
+    absmax();
+    // (b) the probe audio, batch by batch from the reset state
+    cal.ref_emb.assign((size_t)cal.nb * CAL_T * CAL_NP * 96, 0.f);
+    cal.ref_raw.assign((size_t)cal.nb * CAL_T * CAL_NP * std::max(t->NL, 1), 0.f);
+    for (int bt = 0; bt < cal.nb * CAL_T; ++bt) {
+        const int it = bt % CAL_T;
+        if (it == 0 && bt > 0) if (int rc = do_reset(t, nullptr, CAL_NP, nullptr)) return drained(t, rc);
+        if (getenv("OWW_DEBUG_CALIB")) { const hipError_t e = hipStreamSynchronize(t->stream); fprintf(stderr, "calibrate: probe step %d of %d (%s)\n", bt, cal.nb * CAL_T, hipGetErrorString(e)); }
+        if (int rc = probe_step(t, a, cal.d_pcm + (size_t)bt * CAL_NP * OWW_CHUNK, true)) return drained(t, rc);
+        absmax();
+        if (hipMemcpyAsync(d_ref + (size_t)bt * CAL_NP * 96, t->d_emb, (size_t)CAL_NP * 96 * sizeof(float), hipMemcpyDeviceToDevice, t->stream) != hipSuccess ||
+            (t->NL > 0 && hipMemcpyAsync(d_ref + n_emb + (size_t)bt * CAL_NP * t->NL, t->d_raw, (size_t)CAL_NP * t->NL * sizeof(float), hipMemcpyDeviceToDevice, t->stream) != hipSuccess))
+            return drained(t, fail(OWW_EHIP, "oww_commit: probe gather failed"));
+    }
+    unsigned mx[20];
+    if (copy_async(cal.ref_emb.data(), d_ref, n_emb * sizeof(float), hipMemcpyDeviceToHost, t->stream) != hipSuccess ||
+        (t->NL > 0 && copy_async(cal.ref_raw.data(), d_ref + n_emb, n_raw * sizeof(float), hipMemcpyDeviceToHost, t->stream) != hipSuccess) ||
+        copy_async(mx, d_max, sizeof mx, hipMemcpyDeviceToHost, t->stream) != hipSuccess || hipStreamSynchronize(t->stream) != hipSuccess)
+        return drained(t, fail(OWW_EHIP, "oww_commit: calibration run failed: %s", hipGetErrorString(hipGetLastError())));
+    clk.lap("probe run (exact fp32)");
+    for (int l = 0; l < 20; ++l) {
+        float m; memcpy(&m, &mx[l], 4);
+        if (!std::isfinite(m)) return fail(OWW_EINVAL, "oww_commit: layer %d of the embedding network produces non-finite activations in exact fp32 -- the weights are broken", l);
+        h->hx_absmax[l] = m;
+    }
+    hx_ladder(h->hx_absmax, h->emb_blob, *h);
+    return 0;
+}
+
 int calibrate_hx(oww_ctx* h, HxCalib& cal) {
     (void)hipGetLastError();                 // (a stale error of the caller's thread is not this function's to report)
     make_probe_pcm(cal.pcm, h->cal_user);
@@ -1189,69 +1204,8 @@ int calibrate_hx(oww_ctx* h, HxCalib& cal) {
     c2.feature_ring = h->TR;
     oww_ctx* t = nullptr;
     if (int rc = oww_create(&c2, &t)) return rc;
-    int rc = 0;
-    unsigned* d_max = nullptr; int* d_off = nullptr; float* d_ref = nullptr;
     CommitClock clk("calibrate");
-    do {
-        if ((rc = oww_load_mel(t, h->mel_blob.data(), h->mel_blob.size() * sizeof(float)))) break;
-        if ((rc = oww_load_embedding(t, h->emb_blob.data(), h->emb_blob.size() * sizeof(float)))) break;
-        for (const HeadHost& hh : h->heads) {
-            std::vector<float> blob(8 + hh.blob.size());
-            const int32_t hdr[8] = {hh.kind, hh.T, hh.hidden, hh.n_out, hh.has_ln, hh.n_blocks - 1, 0, 0};
-            memcpy(blob.data(), hdr, sizeof hdr);
-            memcpy(blob.data() + 8, hh.blob.data(), hh.blob.size() * sizeof(float));
-            if ((rc = oww_add_head(t, blob.data(), blob.size() * sizeof(float))) < 0) break;
-            rc = 0;
-        }
-        if (rc) break;
-        if ((rc = oww_commit(t))) break;
-        clk.lap("scratch fp32 handle");
-        cal.NL = t->NL;
-        int off[21]; off[0] = 0;
-        for (int l = 0; l < 20; ++l) off[l + 1] = off[l] + kLayerOut[l][0] * kLayerOut[l][1] * kLayerOut[l][2];
-        // probe audio up once, results down once: the run in between is stream-ordered, without a host round trip per probe step
-        const size_t n_steps = (size_t)cal.nb * CAL_T, n_emb = n_steps * CAL_NP * 96, n_raw = n_steps * CAL_NP * std::max(t->NL, 1);
-        if (dev_alloc(&d_max, 20 * sizeof(unsigned)) != hipSuccess || dev_alloc(&d_off, sizeof off) != hipSuccess ||
-            dev_alloc(&cal.d_pcm, cal.pcm.size() * sizeof(int16_t)) != hipSuccess ||
-            dev_alloc(&d_ref, (n_emb + n_raw) * sizeof(float)) != hipSuccess) { rc = fail(OWW_ENOMEM, "oww_commit: out of device memory (calibration)"); break; }
-        if (hipMemsetAsync(d_max, 0, 20 * sizeof(unsigned), t->stream) != hipSuccess ||
-            copy_async(d_off, off, sizeof off, hipMemcpyHostToDevice, t->stream) != hipSuccess ||
-            copy_async(cal.d_pcm, cal.pcm.data(), cal.pcm.size() * sizeof(int16_t), hipMemcpyHostToDevice, t->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_commit: calibration setup failed"); break; }
-        auto absmax = [&]() { hipLaunchKernelGGL(layer_absmax_kernel, dim3(20, CAL_NP), dim3(256), 0, t->stream, t->d_dbg, (size_t)DBG_FLOATS, d_off, d_max); };
-        // (a) the all-ones mel history every stream starts from (utils.py:165): the handle sits in that steady state after its commit
-        hipLaunchKernelGGL(fill_kernel, dim3(CAL_NP), dim3(256), 0, t->stream, t->d_mel, (size_t)CAL_NP * 256, 1.0f);
-        const StepArgs a = step_args(t);             // (every layer dumped: the maxima are read from t's debug buffer)
-        if ((rc = run_cnn(t, a, CAL_NP, 256, 0))) break;
-        absmax();
-        // (b) the probe audio, batch by batch from the reset state
-        cal.ref_emb.assign((size_t)cal.nb * CAL_T * CAL_NP * 96, 0.f);
-        cal.ref_raw.assign((size_t)cal.nb * CAL_T * CAL_NP * std::max(t->NL, 1), 0.f);
-        for (int bt = 0; bt < cal.nb * CAL_T && !rc; ++bt) {
-            const int it = bt % CAL_T;
-            if (it == 0 && bt > 0 && (rc = do_reset(t, nullptr, CAL_NP, nullptr))) break;
-            if (getenv("OWW_DEBUG_CALIB")) { const hipError_t e = hipStreamSynchronize(t->stream); fprintf(stderr, "calibrate: probe step %d of %d (%s)\n", bt, cal.nb * CAL_T, hipGetErrorString(e)); }
-            if ((rc = probe_step(t, a, cal.d_pcm + (size_t)bt * CAL_NP * OWW_CHUNK, true))) break;
-            absmax();
-            if (hipMemcpyAsync(d_ref + (size_t)bt * CAL_NP * 96, t->d_emb, (size_t)CAL_NP * 96 * sizeof(float), hipMemcpyDeviceToDevice, t->stream) != hipSuccess ||
-                (t->NL > 0 && hipMemcpyAsync(d_ref + n_emb + (size_t)bt * CAL_NP * t->NL, t->d_raw, (size_t)CAL_NP * t->NL * sizeof(float), hipMemcpyDeviceToDevice, t->stream) != hipSuccess)) { rc = fail(OWW_EHIP, "oww_commit: probe gather failed"); break; }
-        }
-        if (rc) break;
-        unsigned mx[20];
-        if (copy_async(cal.ref_emb.data(), d_ref, n_emb * sizeof(float), hipMemcpyDeviceToHost, t->stream) != hipSuccess ||
-            (t->NL > 0 && copy_async(cal.ref_raw.data(), d_ref + n_emb, n_raw * sizeof(float), hipMemcpyDeviceToHost, t->stream) != hipSuccess) ||
-            copy_async(mx, d_max, sizeof mx, hipMemcpyDeviceToHost, t->stream) != hipSuccess || hipStreamSynchronize(t->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_commit: calibration run failed: %s", hipGetErrorString(hipGetLastError())); break; }
-        clk.lap("probe run (exact fp32)");
-        for (int l = 0; l < 20; ++l) {
-            float m; memcpy(&m, &mx[l], 4);
-            if (!std::isfinite(m)) { rc = fail(OWW_EINVAL, "oww_commit: layer %d of the embedding network produces non-finite activations in exact fp32 -- the weights are broken", l); break; }
-            h->hx_absmax[l] = m;
-        }
-        if (rc) break;
-        hx_ladder(h->hx_absmax, h->emb_blob, *h);
-    } while (0);
-    if (d_max) (void)dev_free(d_max);
-    if (d_off) (void)dev_free(d_off);
-    if (d_ref) (void)dev_free(d_ref);
+    int rc = calibrate_run(h, t, cal, clk);      // (its scratch buffers are gone when it returns)
     const std::string keep = g_err;
     // the scratch handle's whole life -- launches whose status nobody looked at, its frees -- must have left no HIP error behind
     const hipError_t e_run = hipStreamSynchronize(t->stream);
@@ -1268,24 +1222,22 @@ int calibrate_hx(oww_ctx* h, HxCalib& cal) {
 // replay of the probes on the handle's own (f16-split) kernels; leaves the first CAL_NP streams dirty -- the caller resets all state
 int selftest_hx(oww_ctx* h, const HxCalib& cal) {
     const size_t n_steps = (size_t)cal.nb * CAL_T, n_emb = n_steps * CAL_NP * 96, n_raw = n_steps * CAL_NP * std::max(h->NL, 1);
-    float* d_out = nullptr;
+    DevBuf<float> d_out;
     if (!cal.d_pcm) return fail(OWW_ESTATE, "oww_commit: self-test without calibration probes");
-    if (dev_alloc(&d_out, (n_emb + n_raw) * sizeof(float)) != hipSuccess) return fail(OWW_ENOMEM, "oww_commit: out of device memory (self-test)");
+    if (d_out.alloc(n_emb + n_raw)) return fail(OWW_ENOMEM, "oww_commit: out of device memory (self-test)");
     std::vector<float> emb(n_emb), raw(n_raw);
-    int rc = 0;
     const StepArgs a{};                                  // (no per-layer dumps: the replay runs the kernels the steps run)
-    for (int bt = 0; bt < cal.nb * CAL_T && !rc; ++bt) {
-        if (bt % CAL_T == 0 && bt > 0 && (rc = do_reset(h, nullptr, CAL_NP, nullptr))) break;
+    for (int bt = 0; bt < cal.nb * CAL_T; ++bt) {
+        if (bt % CAL_T == 0 && bt > 0) if (int rc = do_reset(h, nullptr, CAL_NP, nullptr)) return drained(h, rc);
         if (getenv("OWW_DEBUG_CALIB")) { const hipError_t e = hipStreamSynchronize(h->stream); fprintf(stderr, "self-test: probe step %d of %d (%s)\n", bt, cal.nb * CAL_T, hipGetErrorString(e)); }
-        if ((rc = probe_step(h, a, cal.d_pcm + (size_t)bt * CAL_NP * OWW_CHUNK, true))) break;
+        if (int rc = probe_step(h, a, cal.d_pcm + (size_t)bt * CAL_NP * OWW_CHUNK, true)) return drained(h, rc);
         if (hipMemcpyAsync(d_out + (size_t)bt * CAL_NP * 96, h->d_emb, (size_t)CAL_NP * 96 * sizeof(float), hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-            (h->NL > 0 && hipMemcpyAsync(d_out + n_emb + (size_t)bt * CAL_NP * h->NL, h->d_raw, (size_t)CAL_NP * h->NL * sizeof(float), hipMemcpyDeviceToDevice, h->stream) != hipSuccess)) { rc = fail(OWW_EHIP, "oww_commit: probe gather failed"); break; }
+            (h->NL > 0 && hipMemcpyAsync(d_out + n_emb + (size_t)bt * CAL_NP * h->NL, h->d_raw, (size_t)CAL_NP * h->NL * sizeof(float), hipMemcpyDeviceToDevice, h->stream) != hipSuccess))
+            return drained(h, fail(OWW_EHIP, "oww_commit: probe gather failed"));
     }
-    if (!rc && (copy_async(emb.data(), d_out, n_emb * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                (h->NL > 0 && copy_async(raw.data(), d_out + n_emb, n_raw * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) ||
-                hipStreamSynchronize(h->stream) != hipSuccess)) rc = fail(OWW_EHIP, "oww_commit: self-test run failed: %s", hipGetErrorString(hipGetLastError()));
-    (void)dev_free(d_out);
-    if (rc) return rc;
+    if (copy_async(emb.data(), d_out, n_emb * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        (h->NL > 0 && copy_async(raw.data(), d_out + n_emb, n_raw * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) ||
+        hipStreamSynchronize(h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "oww_commit: self-test run failed: %s", hipGetErrorString(hipGetLastError())));
     float err = 0.f, ref = 0.f, serr = 0.f;
     bool finite = true;
     for (size_t i = 0; i < emb.size(); ++i) {
@@ -1361,12 +1313,7 @@ int bank_route(oww_ctx* h) {
         tiles.insert(tiles.end(), ct.begin(), ct.end());
         h->bank_ntiles[c] = (int)ct.size();
     }
-    if (tiles.size() > h->bank_tiles_cap) {
-        if (h->d_bank_tiles) (void)dev_free(h->d_bank_tiles);
-        h->d_bank_tiles = nullptr; h->bank_tiles_cap = 0;
-        HIPCHK(dev_alloc(&h->d_bank_tiles, tiles.size() * sizeof(owh::BankTile)));
-        h->bank_tiles_cap = tiles.size();
-    }
+    HIPCHK(grow(h, h->d_bank_tiles, tiles.size()));
     if (!tiles.empty()) HIPCHK(copy_sync(h->d_bank_tiles, tiles.data(), tiles.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice));
     if (!entries.empty()) HIPCHK(copy_sync(h->d_bank_entries, entries.data(), entries.size() * sizeof(int), hipMemcpyHostToDevice));
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }     // the launch list changed
@@ -1420,10 +1367,25 @@ void comm_release(oww_ctx* h) {
     h->comm = nullptr; h->comm_rank = 0; h->comm_world = 1;
 }
 
+}  // namespace
+
+// Nothing of this handle may still be queued when its buffers go: every stream the handle ever launched on is drained before any member
+// is released (hipFree would wait for the whole device as well, but the page-locked words -- h_range, which the f16-split kernels write
+// at exit, h_lists, the ingest slots -- and the streams and events themselves are released by calls that promise no such wait).
+oww_ctx::~oww_ctx() {
+    for (hipStream_t st : {stream.get(), up_stream.get(), down_stream.get()})
+        if (st) (void)hipStreamSynchronize(st);
+    comm_release(this);
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    if (graph) (void)hipGraphDestroy(graph);
+}
+
+namespace {
+
 // ---- oww_commit, phase by phase (the host image phases -- build_nets, pack_* -- are owwhip_pack.h's) ----------------------------------
 // upload the image; offsets -> device pointers, the NetDesc tables and the fast groups' HeadHxNets
 int bind_weights(oww_ctx* h, const HostBuf& hb, const WeightOff& off) {
-    HIPCHK(dev_alloc(&h->d_w, hb.data.size() * sizeof(float)));
+    HIPCHK(herr(h->d_w.alloc(hb.data.size())));
     HIPCHK(copy_sync(h->d_w, hb.data.data(), hb.data.size() * sizeof(float), hipMemcpyHostToDevice));
     const float* w = h->d_w;
     h->d_hann = w + off.hann; h->d_mstart = reinterpret_cast<const int*>(w + off.start); h->d_taps = w + off.taps;
@@ -1457,7 +1419,7 @@ int bind_weights(oww_ctx* h, const HostBuf& hb, const WeightOff& off) {
     if (!h->nets.empty()) {
         std::vector<NetDesc> all;
         for (size_t ni = 0; ni < h->nets.size(); ++ni) all.push_back(make_desc((int)ni, 0));
-        HIPCHK(dev_alloc(&h->d_allnets, all.size() * sizeof(NetDesc)));
+        HIPCHK(herr(h->d_allnets.alloc(all.size())));
         HIPCHK(copy_sync(h->d_allnets, all.data(), all.size() * sizeof(NetDesc), hipMemcpyHostToDevice));
     }
     for (size_t gi = 0; gi < h->groups.size(); ++gi) {
@@ -1465,7 +1427,7 @@ int bind_weights(oww_ctx* h, const HostBuf& hb, const WeightOff& off) {
         const WeightOff::Group& go = off.group[gi];
         std::vector<NetDesc> ds;
         for (int i = 0; i < g.n_nets; ++i) ds.push_back(make_desc(g.nets[i], 64 * i));
-        HIPCHK(dev_alloc(&g.d_nets, ds.size() * sizeof(NetDesc)));
+        HIPCHK(herr(g.d_nets.alloc(ds.size())));
         HIPCHK(copy_sync(g.d_nets, ds.data(), ds.size() * sizeof(NetDesc), hipMemcpyHostToDevice));
         g.d_w1pk = w + go.w1pk; g.d_b1cat = w + go.b1cat;
         if (!h->hx) continue;
@@ -1479,7 +1441,7 @@ int bind_weights(oww_ctx* h, const HostBuf& hb, const WeightOff& off) {
 // sticky range flag of the f16-split kernels: page-locked + device-mapped, so the host reads it without a copy
 int alloc_range_flag(oww_ctx* h) {
     void* dp = nullptr;
-    HIPCHK(hipHostMalloc((void**)&h->h_range, 64, hipHostMallocMapped));
+    HIPCHK(herr(h->h_range.alloc(16, hipHostMallocMapped)));
     h->h_range[0] = 0; h->h_range[1] = -1;
     HIPCHK(hipHostGetDevicePointer(&dp, h->h_range, 0));
     h->d_range = (int*)dp;
@@ -1490,40 +1452,40 @@ int alloc_range_flag(oww_ctx* h) {
 int alloc_state(oww_ctx* h) {
     const size_t SP = h->Spad;
     for (int a = 0; a < N_STATE; ++a) {
-        if (int rc = dalloc(h->stream, &h->d_state[a], SP * h->state_len[a])) return rc;
-        if (int rc = dalloc(h->stream, &h->d_tmpl[a], (size_t)h->state_len[a] * (h->rr ? kStateSpgRr[a] : 1))) return rc;
+        if (int rc = dalloc(h->stream, h->d_state[a], SP * h->state_len[a])) return rc;
+        if (int rc = dalloc(h->stream, h->d_tmpl[a], (size_t)h->state_len[a] * (h->rr ? kStateSpgRr[a] : 1))) return rc;
     }
     const int* xlen = h->rr ? kXLenRr : kXLenLds;
-    float** x[4] = {&h->d_xA, &h->d_xB, &h->d_xC, &h->d_xD};
-    for (int i = 0; i < 4; ++i) if (int rc = dalloc(h->stream, x[i], SP * xlen[i])) return rc;
-    if (int rc = dalloc(h->stream, &h->d_mel, SP * 8 * h->kmax * 32)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_feat, SP * h->TR * 96)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_emb, SP * 96)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_raw, SP * std::max(h->NL, 1))) return rc;
-    if (int rc = dalloc(h->stream, &h->d_scores, SP * std::max(h->NL, 1))) return rc;
-    if (int rc = dalloc(h->stream, &h->d_ring, SP * std::max(h->NL, 1) * OWW_SCORE_RING)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_featinit, (size_t)h->TR * 96)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_nfeat, SP)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_npred, SP)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_vadring, SP * 8)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_nvad, SP)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_vadin, SP)) return rc;
+    DevBuf<float>* x[4] = {&h->d_xA, &h->d_xB, &h->d_xC, &h->d_xD};
+    for (int i = 0; i < 4; ++i) if (int rc = dalloc(h->stream, *x[i], SP * xlen[i])) return rc;
+    if (int rc = dalloc(h->stream, h->d_mel, SP * 8 * h->kmax * 32)) return rc;
+    if (int rc = dalloc(h->stream, h->d_feat, SP * h->TR * 96)) return rc;
+    if (int rc = dalloc(h->stream, h->d_emb, SP * 96)) return rc;
+    if (int rc = dalloc(h->stream, h->d_raw, SP * std::max(h->NL, 1))) return rc;
+    if (int rc = dalloc(h->stream, h->d_scores, SP * std::max(h->NL, 1))) return rc;
+    if (int rc = dalloc(h->stream, h->d_ring, SP * std::max(h->NL, 1) * OWW_SCORE_RING)) return rc;
+    if (int rc = dalloc(h->stream, h->d_featinit, (size_t)h->TR * 96)) return rc;
+    if (int rc = dalloc(h->stream, h->d_nfeat, SP)) return rc;
+    if (int rc = dalloc(h->stream, h->d_npred, SP)) return rc;
+    if (int rc = dalloc(h->stream, h->d_vadring, SP * 8)) return rc;
+    if (int rc = dalloc(h->stream, h->d_nvad, SP)) return rc;
+    if (int rc = dalloc(h->stream, h->d_vadin, SP)) return rc;
     if (h->vad) {
         const size_t G = (SP + 15) / 16;
-        if (int rc = dalloc(h->stream, &h->d_vadx, G * 4 * 1024)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_vadhc, G * 4096)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_vadlast, SP)) return rc;
+        if (int rc = dalloc(h->stream, h->d_vadx, G * 4 * 1024)) return rc;
+        if (int rc = dalloc(h->stream, h->d_vadhc, G * 4096)) return rc;
+        if (int rc = dalloc(h->stream, h->d_vadlast, SP)) return rc;
     }
-    if (int rc = dalloc(h->stream, &h->d_tail, SP * 480)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_pcm, (size_t)h->S * OWW_CHUNK * h->kmax)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_patience, (size_t)std::max(h->NL, 1))) return rc;
-    if (int rc = dalloc(h->stream, &h->d_threshold, (size_t)std::max(h->NL, 1))) return rc;
+    if (int rc = dalloc(h->stream, h->d_tail, SP * 480)) return rc;
+    if (int rc = dalloc(h->stream, h->d_pcm, (size_t)h->S * OWW_CHUNK * h->kmax)) return rc;
+    if (int rc = dalloc(h->stream, h->d_patience, (size_t)std::max(h->NL, 1))) return rc;
+    if (int rc = dalloc(h->stream, h->d_threshold, (size_t)std::max(h->NL, 1))) return rc;
     {
         std::vector<float> nanv(std::max(h->NL, 1), NAN);
         HIPCHK(copy_async(h->d_threshold, nanv.data(), nanv.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));   // (behind the buffer's zero fill, same stream)
     }
-    if (h->cfg.debug_layers) if (int rc = dalloc(h->stream, &h->d_dbg, SP * DBG_FLOATS)) return rc;
-    if (const char* e = getenv("OWW_PROF_BLOCK")) { h->prof_block = atoi(e); if (int rc = dalloc(h->stream, &h->d_prof, (size_t)4 * 256)) return rc; }
+    if (h->cfg.debug_layers) if (int rc = dalloc(h->stream, h->d_dbg, SP * DBG_FLOATS)) return rc;
+    if (const char* e = getenv("OWW_PROF_BLOCK")) { h->prof_block = atoi(e); if (int rc = dalloc(h->stream, h->d_prof, (size_t)4 * 256)) return rc; }
     return 0;
 }
 
@@ -1578,17 +1540,17 @@ int derive_reset_state(oww_ctx* h, const HxCalib& cal, CommitClock& clk) {
 // head bank (oww_bank_configure): subscription table, per-slot outputs, the head table; no head yet
 int alloc_bank(oww_ctx* h) {
     const size_t SK = (size_t)h->S * h->bank_K;
-    if (int rc = dalloc(h->stream, &h->d_bank_sub, SK, false)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_bank_idx, SK)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_bank_raw, SK)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_bank_scores, SK)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_bank_ring, SK * OWW_SCORE_RING)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_bank_npred, SK)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_bank_entries, SK)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_bank_heads, (size_t)h->bank_cap)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_bank_pat, (size_t)h->bank_cap)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_bank_thr, (size_t)h->bank_cap, false)) return rc;
-    h->bank.assign(h->bank_cap, oww_ctx::BankHead{});
+    if (int rc = dalloc(h->stream, h->d_bank_sub, SK, false)) return rc;
+    if (int rc = dalloc(h->stream, h->d_bank_idx, SK)) return rc;
+    if (int rc = dalloc(h->stream, h->d_bank_raw, SK)) return rc;
+    if (int rc = dalloc(h->stream, h->d_bank_scores, SK)) return rc;
+    if (int rc = dalloc(h->stream, h->d_bank_ring, SK * OWW_SCORE_RING)) return rc;
+    if (int rc = dalloc(h->stream, h->d_bank_npred, SK)) return rc;
+    if (int rc = dalloc(h->stream, h->d_bank_entries, SK)) return rc;
+    if (int rc = dalloc(h->stream, h->d_bank_heads, (size_t)h->bank_cap)) return rc;
+    if (int rc = dalloc(h->stream, h->d_bank_pat, (size_t)h->bank_cap)) return rc;
+    if (int rc = dalloc(h->stream, h->d_bank_thr, (size_t)h->bank_cap, false)) return rc;
+    h->bank.clear(); h->bank.resize(h->bank_cap);
     h->bank_sub.assign(SK, -1);
     std::vector<float> nanv(h->bank_cap, NAN);
     HIPCHK(copy_async(h->d_bank_sub, h->bank_sub.data(), SK * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1600,10 +1562,10 @@ int alloc_bank(oww_ctx* h) {
 // per-stream verifiers (oww_verifier_configure): the pool, the assignment tables (every pair at the default) and the pair list
 int alloc_verifiers(oww_ctx* h) {
     h->vpool_stride = h->TR * OWW_EMB_DIM;
-    if (int rc = dalloc(h->stream, &h->d_vpool_w, (size_t)h->vpool_cap * h->vpool_stride)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_vpool_b, (size_t)h->vpool_cap)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_svlist, (size_t)h->S * (h->NL + h->bank_K), false)) return rc;
-    if (int rc = dalloc(h->stream, &h->d_sv_eval, 1)) return rc;
+    if (int rc = dalloc(h->stream, h->d_vpool_w, (size_t)h->vpool_cap * h->vpool_stride)) return rc;
+    if (int rc = dalloc(h->stream, h->d_vpool_b, (size_t)h->vpool_cap)) return rc;
+    if (int rc = dalloc(h->stream, h->d_svlist, (size_t)h->S * (h->NL + h->bank_K), false)) return rc;
+    if (int rc = dalloc(h->stream, h->d_sv_eval, 1)) return rc;
     h->vpool_T.assign(h->vpool_cap, 0);
     h->vasg_fix.assign((size_t)h->S * h->NL, OWW_VERIFIER_DEFAULT);
     h->vthr_fix.assign((size_t)h->S * h->NL, 0.f);
@@ -1676,7 +1638,7 @@ int state_layout(oww_ctx* h) {
         fp = fp_mix(fp, h->ing_taps.data(), h->ing_taps.size() * sizeof(float));
     }
     h->st_fp = fp;
-    if (!h->d_st_flat) HIPCHK(dev_alloc(&h->d_st_flat, h->st_flat.size() * sizeof(ows::FlatSection)));
+    if (!h->d_st_flat) HIPCHK(herr(h->d_st_flat.alloc(h->st_flat.size())));
     HIPCHK(copy_sync(h->d_st_flat, h->st_flat.data(), h->st_flat.size() * sizeof(ows::FlatSection), hipMemcpyHostToDevice));
     h->st_ready = true;
     return 0;
@@ -1715,23 +1677,14 @@ void state_list_build(const oww_ctx* h, const int32_t* ids, int n, std::vector<i
 }
 
 int state_lists_upload(oww_ctx* h, const std::vector<int>& buf) {
-    if (buf.size() > h->st_items_cap) {
-        if (h->d_st_items) { HIPCHK(hipStreamSynchronize(h->stream)); (void)dev_free(h->d_st_items); }
-        h->d_st_items = nullptr; h->st_items_cap = 0;
-        if (dev_alloc(&h->d_st_items, buf.size() * sizeof(int)) != hipSuccess) return fail(OWW_ENOMEM, "out of device memory for %zu stream list bytes", buf.size() * sizeof(int));
-        h->st_items_cap = buf.size();
-    }
+    if (grow(h, h->d_st_items, buf.size()) != hipSuccess) return fail(OWW_ENOMEM, "out of device memory for %zu stream list bytes", buf.size() * sizeof(int));
     HIPCHK(copy_async(h->d_st_items, buf.data(), buf.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 
 int state_stage(oww_ctx* h, size_t n) {
     const size_t need = n * (size_t)h->st_record_words;
-    if (need <= h->st_stage_words) return 0;
-    if (h->d_st_stage) { HIPCHK(hipStreamSynchronize(h->stream)); (void)dev_free(h->d_st_stage); }
-    h->d_st_stage = nullptr; h->st_stage_words = 0;
-    if (dev_alloc(&h->d_st_stage, need * 4) != hipSuccess) return fail(OWW_ENOMEM, "out of device memory for %zu bytes of stream state records", need * 4);
-    h->st_stage_words = need;
+    if (grow(h, h->d_st_stage, need) != hipSuccess) return fail(OWW_ENOMEM, "out of device memory for %zu bytes of stream state records", need * 4);
     return 0;
 }
 
@@ -1765,6 +1718,31 @@ int state_xfer(oww_ctx* h, const StateList& L, uint32_t* rec) {
 #undef OWS_GO
         HIPCHK(hipGetLastError());
     }
+    return 0;
+}
+
+// the stream ids of a reset, into d_ids on the handle's stream
+int upload_ids(oww_ctx* h, const int32_t* ids, int n) {
+    HIPCHK(grow(h, h->d_ids, (size_t)n));
+    HIPCHK(copy_async(h->d_ids, ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+// The end of every step entry point: the scores out and, with sync -- somebody's host buffer must be free / filled on return -- the
+// wait and the range check behind it.
+int deliver_scores(oww_ctx* h, float* scores, int scores_on_device, bool sync, const char* fn) {
+    const size_t nb = (size_t)h->S * h->NL * sizeof(float);
+    if (scores && nb) HIPCHK(copy_async(scores, h->d_scores, nb, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    if (!sync) return OWW_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return range_check(h, fn);
+}
+
+// oww_step_masked / oww_submit_masked: the handle's own mask buffer (the kernels index it up to the padded stream count: pad streams 0)
+int ensure_mask(oww_ctx* h) {
+    if (h->d_on) return 0;
+    HIPCHK(herr(h->d_on.alloc(h->Spad)));
+    HIPCHK(hipMemsetAsync(h->d_on, 0, h->Spad, h->stream));
     return 0;
 }
 
@@ -1828,12 +1806,8 @@ int oww_create(const oww_config* cfg, oww_ctx** out) {
     h->rr = cfg->use_mfma == 1 || cfg->use_mfma == 3;
     h->hx = cfg->use_mfma == 3;
     h->state_len = h->rr ? kStateLenRr : kStateLenLds;
-    if (cfg->stream) h->stream = reinterpret_cast<hipStream_t>(cfg->stream);
-    else {
-        hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete h; return fail(OWW_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-        h->own_stream = true;
-    }
+    if (cfg->stream) h->stream.borrow(reinterpret_cast<hipStream_t>(cfg->stream));      // (the caller's: never destroyed)
+    else if (const int e = h->stream.create(hipStreamNonBlocking)) { delete h; return fail(OWW_EHIP, "hipStreamCreate: %s", hipGetErrorString(herr(e))); }
     *out = h;
     return OWW_OK;
     OWW_GUARD_END
@@ -1843,12 +1817,7 @@ int oww_destroy(oww_ctx* h) {
     OWW_GUARD_BEGIN
     if (!h) return OWW_OK;
     (void)hipSetDevice(h->cfg.device);
-    (void)hipStreamSynchronize(h->stream);
-    if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
-    if (h->down_stream) (void)hipStreamSynchronize(h->down_stream);
-    free_all(h);
-    if (h->own_stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                    // (~oww_ctx drains the handle's streams before anything is released)
     return OWW_OK;
     OWW_GUARD_END
 }
@@ -1994,13 +1963,7 @@ int oww_reset(oww_ctx* h, const int32_t* stream_ids, int32_t n, const float* ini
         if (n < 1) return OWW_OK;
         for (int i = 0; i < n; ++i)
             if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return fail(OWW_EINVAL, "oww_reset: stream id %d out of range", stream_ids[i]);
-        if (n > h->ids_cap) {
-            if (h->d_ids) (void)dev_free(h->d_ids);
-            h->d_ids = nullptr; h->ids_cap = 0;
-            HIPCHK(dev_alloc(&h->d_ids, (size_t)n * sizeof(int)));
-            h->ids_cap = n;
-        }
-        HIPCHK(copy_async(h->d_ids, stream_ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (int rc = upload_ids(h, stream_ids, n)) return rc;
         if (int rc = do_reset(h, h->d_ids, n, d_init)) return rc;
     }
     if (h->ing_ready && h->ing_Hpad) {           // stateful ingest: a new caller starts from silence
@@ -2049,25 +2012,14 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
     if (n_chunks > h->kmax) {                                    // longer than the mel buffer: slices that share the call's clamp floor
         const int16_t* d_call = pcm;
         if (!pcm_on_device) {
-            if (n_pcm > h->long_cap) {
-                if (h->d_long) { HIPCHK(hipStreamSynchronize(h->stream)); (void)dev_free(h->d_long); h->d_long = nullptr; h->long_cap = 0; }
-                if (dev_alloc(&h->d_long, n_pcm * sizeof(int16_t)) != hipSuccess) return fail(OWW_ENOMEM, "oww_step: out of device memory for a call of %d chunks", n_chunks);
-                h->long_cap = n_pcm;
-            }
+            if (grow(h, h->d_long, n_pcm) != hipSuccess) return fail(OWW_ENOMEM, "oww_step: out of device memory for a call of %d chunks", n_chunks);
             HIPCHK(copy_async(h->d_long, pcm, n_pcm * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
             d_call = h->d_long;
         }
         if (int rc = launch_step_long(h, a, d_call, n_chunks)) return rc;
         if (events_on(h)) { if (int rc = launch_events(h, a, h->evt_sync)) return rc; h->evt_cur = &h->evt_sync; }
-        if (scores) {
-            const size_t nb = (size_t)h->S * h->NL * sizeof(float);
-            if (nb) HIPCHK(copy_async(scores, h->d_scores, nb, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-        }
-        if (!scores_on_device || !pcm_on_device) {               // (the caller's host buffer is free to change when this returns)
-            HIPCHK(hipStreamSynchronize(h->stream));
-            if (int rc = range_check(h, "oww_step")) return rc;
-        }
-        return OWW_OK;
+        // (host PCM: the caller's buffer is free to change when this returns)
+        return deliver_scores(h, scores, scores_on_device, !scores_on_device || !pcm_on_device, "oww_step");
     }
     const bool graphable = h->want_graph && n_chunks == 1 && !h->timing;
     const int16_t* d_pcm = pcm;
@@ -2092,15 +2044,7 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
         if (int rc = launch_step(h, a, d_pcm, n_chunks)) return rc;
     }
     if (events_on(h)) { if (int rc = launch_events(h, a, h->evt_sync)) return rc; h->evt_cur = &h->evt_sync; }
-    if (scores) {
-        const size_t nb = (size_t)h->S * h->NL * sizeof(float);
-        if (nb) HIPCHK(copy_async(scores, h->d_scores, nb, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-        if (!scores_on_device) {
-            HIPCHK(hipStreamSynchronize(h->stream));
-            if (int rc = range_check(h, "oww_step")) return rc;
-        }
-    }
-    return OWW_OK;
+    return deliver_scores(h, scores, scores_on_device, scores && !scores_on_device, "oww_step");
     OWW_GUARD_END
 }
 
@@ -2113,11 +2057,7 @@ int oww_step_masked(oww_ctx* h, const int16_t* pcm, int pcm_on_device, const uin
     if (int rc = range_check(h, "oww_step_masked")) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     h->k_last = 1;
-    if (!h->d_on) {
-        HIPCHK(dev_alloc(&h->d_on, h->Spad));
-        HIPCHK(hipMemsetAsync(h->d_on, 0, h->Spad, h->stream));
-    }
-    // (always through the handle's own buffer: the kernels index it up to the padded stream count)
+    if (int rc = ensure_mask(h)) return rc;
     HIPCHK(copy_async(h->d_on, stream_on, h->S, stream_on_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     const int16_t* d_pcm = pcm;
     if (!pcm_on_device || (reinterpret_cast<uintptr_t>(pcm) & 15)) {
@@ -2135,31 +2075,21 @@ int oww_step_masked(oww_ctx* h, const int16_t* pcm, int pcm_on_device, const uin
     if (n_act != 0)                                             // (nobody takes part: nothing moves)
         if (int rc = launch_step(h, a, d_pcm, 1)) return rc;
     if (events_on(h)) { if (int rc = launch_events(h, a, h->evt_sync, n_act != 0)) return rc; h->evt_cur = &h->evt_sync; }
-    if (scores) {
-        const size_t nb = (size_t)h->S * h->NL * sizeof(float);
-        if (nb) HIPCHK(copy_async(scores, h->d_scores, nb, scores_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-        if (!scores_on_device) {
-            HIPCHK(hipStreamSynchronize(h->stream));
-            if (int rc2 = range_check(h, "oww_step_masked")) return rc2;
-        }
-    }
-    return OWW_OK;
+    return deliver_scores(h, scores, scores_on_device, scores && !scores_on_device, "oww_step_masked");
     OWW_GUARD_END
 }
 
 static int ensure_ingest(oww_ctx* h) {
     if (h->up_stream) return 0;
-    HIPCHK(hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&h->down_stream, hipStreamNonBlocking));
-    const size_t nb = (size_t)h->S * std::max(h->NL, 1) * sizeof(float);
+    HIPCHK(herr(h->up_stream.create(hipStreamNonBlocking)));
+    HIPCHK(herr(h->down_stream.create(hipStreamNonBlocking)));
+    const size_t n_sc = (size_t)h->S * std::max(h->NL, 1);
     for (auto& sl : h->slot) {
-        HIPCHK(dev_alloc(&sl.d_pcm, (size_t)h->S * OWW_CHUNK * h->kmax * sizeof(int16_t)));
-        HIPCHK(dev_alloc(&sl.d_scores, nb));
-        HIPCHK(hipHostMalloc((void**)&sl.h_scores, nb, hipHostMallocDefault));
-        HIPCHK(hipHostMalloc((void**)&sl.h_on, h->S, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&sl.up, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&sl.down, hipEventDisableTiming));
+        HIPCHK(herr(sl.d_pcm.alloc((size_t)h->S * OWW_CHUNK * h->kmax)));
+        HIPCHK(herr(sl.d_scores.alloc(n_sc)));
+        HIPCHK(herr(sl.h_scores.alloc(n_sc, hipHostMallocDefault)));
+        HIPCHK(herr(sl.h_on.alloc(h->S, hipHostMallocDefault)));
+        for (owm::Event* e : {&sl.up, &sl.done, &sl.down}) HIPCHK(herr(e->create(hipEventDisableTiming)));
     }
     if (events_on(h)) {
         for (auto& b : h->evt_slot) if (int rc = alloc_event_buf(h, b, true)) return rc;
@@ -2198,10 +2128,7 @@ static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const u
     StepArgs a = step_args(h);
     int n_act = -1;
     if (stream_on) {                                   // (the mask is small: copied on the compute stream, ordered before this step's kernels)
-        if (!h->d_on) {
-            HIPCHK(dev_alloc(&h->d_on, h->Spad));
-            HIPCHK(hipMemsetAsync(h->d_on, 0, h->Spad, h->stream));
-        }
+        if (int rc = ensure_mask(h)) return rc;
         memcpy(sl.h_on, stream_on, h->S);              // the caller's array is free again when this call returns
         HIPCHK(copy_async(h->d_on, sl.h_on, h->S, hipMemcpyHostToDevice, h->stream));
         a.on = h->d_on;
@@ -2246,14 +2173,14 @@ int oww_collect(oww_ctx* h, float* scores) {
 int oww_host_alloc(void** out, size_t nbytes) {
     OWW_GUARD_BEGIN
     if (!out || !nbytes) return fail(OWW_EINVAL, "oww_host_alloc: bad argument");
-    if (hipHostMalloc(out, nbytes, hipHostMallocDefault) != hipSuccess) { *out = nullptr; return fail(OWW_ENOMEM, "oww_host_alloc: %zu bytes of page-locked memory not available", nbytes); }
+    if (owm::pinned_alloc_raw(out, nbytes, hipHostMallocDefault)) { *out = nullptr; return fail(OWW_ENOMEM, "oww_host_alloc: %zu bytes of page-locked memory not available", nbytes); }
     return OWW_OK;
     OWW_GUARD_END
 }
 
 int oww_host_free(void* p) {
     OWW_GUARD_BEGIN
-    if (p) HIPCHK(hipHostFree(p));
+    if (p) HIPCHK(herr(owm::pinned_free_raw(p)));
     return OWW_OK;
     OWW_GUARD_END
 }
@@ -2274,10 +2201,10 @@ int oww_set_verifier(oww_ctx* h, int32_t label, const float* w, int32_t n_w, flo
         int maxT = 1;
         for (const auto& hh : h->heads) maxT = std::max(maxT, hh.T);
         h->ver_stride = maxT * OWW_EMB_DIM;
-        if (int rc = dalloc(h->stream, &h->d_verw, (size_t)h->NL * h->ver_stride)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_verb, (size_t)h->NL)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_verthr, (size_t)h->NL)) return rc;
-        if (int rc = dalloc(h->stream, &h->d_verT, (size_t)h->NL)) return rc;
+        if (int rc = dalloc(h->stream, h->d_verw, (size_t)h->NL * h->ver_stride)) return rc;
+        if (int rc = dalloc(h->stream, h->d_verb, (size_t)h->NL)) return rc;
+        if (int rc = dalloc(h->stream, h->d_verthr, (size_t)h->NL)) return rc;
+        if (int rc = dalloc(h->stream, h->d_verT, (size_t)h->NL)) return rc;
         h->ver_T.assign(h->NL, 0);
         h->ver_thr.assign(h->NL, 0.f);
     }
@@ -2348,13 +2275,7 @@ int oww_reset_vad(oww_ctx* h, const int32_t* stream_ids, int32_t n) {
         if (n < 1) return OWW_OK;
         for (int i = 0; i < n; ++i)
             if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return fail(OWW_EINVAL, "oww_reset_vad: stream id %d out of range", stream_ids[i]);
-        if (n > h->ids_cap) {
-            if (h->d_ids) (void)dev_free(h->d_ids);
-            h->d_ids = nullptr; h->ids_cap = 0;
-            HIPCHK(dev_alloc(&h->d_ids, (size_t)n * sizeof(int)));
-            h->ids_cap = n;
-        }
-        HIPCHK(copy_async(h->d_ids, stream_ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (int rc = upload_ids(h, stream_ids, n)) return rc;
         d_ids = h->d_ids; count = n;
     }
     if (h->vad) {
@@ -2435,14 +2356,8 @@ int oww_resample(oww_ctx* h, const int16_t* in, int in_on_device, int32_t n_in, 
     const size_t b_taps = ((size_t)q * ntp * sizeof(float) + 255) / 256 * 256;
     const size_t b_in = in_on_device ? 0 : ((size_t)h->S * n_in * sizeof(int16_t) + 255) / 256 * 256;
     const size_t b_out = out_on_device ? 0 : (size_t)h->S * n_out * sizeof(int16_t);
-    if (b_taps + b_in + b_out > h->rs_bytes) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->d_rs) (void)dev_free(h->d_rs);
-        h->d_rs = nullptr; h->rs_bytes = 0;
-        if (dev_alloc(&h->d_rs, b_taps + b_in + b_out) != hipSuccess) return fail(OWW_ENOMEM, "oww_resample: out of device memory");
-        h->rs_bytes = b_taps + b_in + b_out;
-    }
-    char* base = (char*)h->d_rs;
+    if (grow(h, h->d_rs, b_taps + b_in + b_out) != hipSuccess) return fail(OWW_ENOMEM, "oww_resample: out of device memory");
+    char* base = h->d_rs;
     // (stream-ordered upload from a buffer that lives in the handle: an earlier oww_resample may still be reading the old bank)
     HIPCHK(hipStreamSynchronize(h->stream));
     h->rs_taps.assign((size_t)q * ntp, 0.f);
@@ -2482,17 +2397,15 @@ int oww_ingest_configure(oww_ctx* h, int32_t encoding, int32_t p, int32_t q, con
     }
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipStreamSynchronize(h->stream));               // an earlier oww_ingest may still read the old bank and history
-    auto drop = [](auto*& ptr) { if (ptr) { (void)dev_free((void*)ptr); ptr = nullptr; } };
-    drop(h->d_ing_taps); drop(h->d_ing_hist);
+    h->d_ing_taps.reset(); h->d_ing_hist.reset();
     h->ing_ready = false;
-    drop(h->d_st_flat); h->st_ready = false;               // the record layout gains, loses or resizes its history section: rebuilt on demand
+    h->d_st_flat.reset(); h->st_ready = false;               // the record layout gains, loses or resizes its history section: rebuilt on demand
     const int ntp = (n_taps + 3) / 4 * 4, Hpad = n_taps ? (n_taps - 1 + 7) / 8 * 8 : 0;
     h->ing_taps.assign((size_t)q * ntp, 0.f);
     for (int r = 0; r < q && n_taps; ++r) memcpy(&h->ing_taps[(size_t)r * ntp], taps + (size_t)r * n_taps, n_taps * sizeof(float));
     if (n_taps) {
-        if (dev_alloc(&h->d_ing_taps, h->ing_taps.size() * sizeof(float)) != hipSuccess ||
-            dev_alloc(&h->d_ing_hist, (size_t)h->S * Hpad * sizeof(int16_t)) != hipSuccess) {
-            drop(h->d_ing_taps);
+        if (h->d_ing_taps.alloc(h->ing_taps.size()) || h->d_ing_hist.alloc((size_t)h->S * Hpad)) {
+            h->d_ing_taps.reset();
             return fail(OWW_ENOMEM, "oww_ingest_configure: out of device memory for %d streams x %d history samples", h->S, Hpad);
         }
         HIPCHK(copy_sync(h->d_ing_taps, h->ing_taps.data(), h->ing_taps.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -2500,9 +2413,8 @@ int oww_ingest_configure(oww_ctx* h, int32_t encoding, int32_t p, int32_t q, con
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     if (!h->d_ing_out) {
-        h->ing_out_cap = (size_t)h->S * OWW_CHUNK;
-        if (dev_alloc(&h->d_ing_out, h->ing_out_cap * sizeof(int16_t)) != hipSuccess) { h->ing_out_cap = 0; return fail(OWW_ENOMEM, "oww_ingest_configure: out of device memory"); }
-        HIPCHK(hipMemset(h->d_ing_out, 0, h->ing_out_cap * sizeof(int16_t)));
+        if (h->d_ing_out.alloc((size_t)h->S * OWW_CHUNK)) return fail(OWW_ENOMEM, "oww_ingest_configure: out of device memory");
+        HIPCHK(hipMemset(h->d_ing_out, 0, h->d_ing_out.capacity() * sizeof(int16_t)));
     }
     h->ing_enc = encoding; h->ing_p = p; h->ing_q = q; h->ing_n_taps = n_taps; h->ing_ntp = ntp; h->ing_Hpad = Hpad;
     h->ing_ready = true;
@@ -2540,34 +2452,26 @@ int oww_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const
     const size_t lds = lds_x + lds_y + (taps_in_lds ? lds_t : 0);
     HIPCHK(hipSetDevice(h->cfg.device));
     const size_t bps = h->ing_enc == OWW_ENC_PCM16 ? 2 : 1, in_bytes = (size_t)h->S * n_in * bps;
-    auto grow = [&](auto*& ptr, size_t& cap, size_t need, bool zero) -> int {
-        if (need <= cap) return 0;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (ptr) (void)dev_free((void*)ptr);
-        ptr = nullptr; cap = 0;
-        if (dev_alloc(&ptr, need) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest: out of device memory for %zu bytes", need);
-        if (zero) HIPCHK(hipMemset(ptr, 0, need));
-        cap = need;
-        return 0;
-    };
     IngestParams a{};
     a.in = in;
     if (!in_on_device) {
-        if (int rc = grow(h->d_ing_in, h->ing_in_cap, in_bytes, false)) return rc;
+        if (grow(h, h->d_ing_in, in_bytes) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest: out of device memory for %zu bytes", in_bytes);
         HIPCHK(copy_async(h->d_ing_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
         a.in = h->d_ing_in;
     }
     a.on = stream_on;
     if (stream_on && !stream_on_on_device) {
-        if (!h->d_ing_on) HIPCHK(dev_alloc(&h->d_ing_on, h->S));
+        if (!h->d_ing_on) HIPCHK(herr(h->d_ing_on.alloc(h->S)));
         HIPCHK(copy_async(h->d_ing_on, stream_on, h->S, hipMemcpyHostToDevice, h->stream));
         a.on = h->d_ing_on;
     }
     const bool to_staging = !out || !out_on_device;
     if (to_staging) {
-        size_t cap_bytes = h->ing_out_cap * sizeof(int16_t);
-        if (int rc = grow(h->d_ing_out, cap_bytes, (size_t)h->S * n_out * sizeof(int16_t), true)) { h->ing_out_cap = cap_bytes / sizeof(int16_t); return rc; }
-        h->ing_out_cap = cap_bytes / sizeof(int16_t);
+        const size_t need = (size_t)h->S * n_out;
+        if (need > h->d_ing_out.capacity()) {                // (a grown staging buffer starts zeroed, like the first)
+            if (grow(h, h->d_ing_out, need) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest: out of device memory for %zu bytes", need * sizeof(int16_t));
+            HIPCHK(hipMemset(h->d_ing_out, 0, need * sizeof(int16_t)));
+        }
     }
     a.out = to_staging ? h->d_ing_out : out;
     a.hist = h->d_ing_hist; a.taps = h->d_ing_taps;
@@ -2641,29 +2545,24 @@ static int mel_impl(oww_ctx* h, const int16_t* pcm, int32_t B, int32_t n, float*
     if (!pcm || !out_db || B < 1 || n < 512) return fail(OWW_EINVAL, "oww_mel: bad argument (B=%d n=%d)", B, n);
     HIPCHK(hipSetDevice(h->cfg.device));
     const int F = (n - 512) / 160 + 1;
-    int16_t* d_in = nullptr; float* d_out = nullptr; float* d_max = nullptr;
-    int rc = 0;
-    do {
-        if (dev_alloc(&d_in, (size_t)B * n * sizeof(int16_t)) != hipSuccess || dev_alloc(&d_out, (size_t)B * F * 32 * sizeof(float)) != hipSuccess ||
-            dev_alloc(&d_max, (size_t)B * sizeof(float)) != hipSuccess) { rc = fail(OWW_ENOMEM, "oww_mel: out of device memory"); break; }
-        if (copy_async(d_in, pcm, (size_t)B * n * sizeof(int16_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_mel: H2D failed"); break; }
-        if ((rc = launch_mel(h, StepArgs{}, d_in, B, n, F, 0, d_out, d_max))) break;
-        const size_t tot = (size_t)B * F * 32;
-        if (per_clip) {
-            hipLaunchKernelGGL(clamp_db_rows_kernel, dim3((F * 32 + 255) / 256, B), dim3(256), 0, h->stream, d_out, F * 32, d_max);
-        } else {
-            std::vector<float> mx(B);
-            if (copy_async(mx.data(), d_max, B * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_mel: D2H failed"); break; }
-            float gmax = -INFINITY;                       // one clamp floor for the whole call (ipynb cell 15: log_spec.max())
-            for (float v : mx) gmax = std::max(gmax, v);
-            hipLaunchKernelGGL(clamp_db_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_out, tot, gmax - 80.0f);
-        }
-        if (copy_async(out_db, d_out, tot * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_mel: D2H failed"); break; }
-    } while (0);
-    (void)dev_free(d_in); (void)dev_free(d_out); (void)dev_free(d_max);
-    return rc;
+    DevBuf<int16_t> d_in; DevBuf<float> d_out, d_max;
+    if (d_in.alloc((size_t)B * n) || d_out.alloc((size_t)B * F * 32) || d_max.alloc(B)) return fail(OWW_ENOMEM, "oww_mel: out of device memory");
+    if (copy_async(d_in, pcm, (size_t)B * n * sizeof(int16_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "oww_mel: H2D failed"));
+    if (int rc = launch_mel(h, StepArgs{}, d_in, B, n, F, 0, d_out, d_max)) return drained(h, rc);
+    const size_t tot = (size_t)B * F * 32;
+    if (per_clip) {
+        hipLaunchKernelGGL(clamp_db_rows_kernel, dim3((F * 32 + 255) / 256, B), dim3(256), 0, h->stream, d_out, F * 32, d_max);
+    } else {
+        std::vector<float> mx(B);
+        if (copy_async(mx.data(), d_max, B * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "oww_mel: D2H failed"));
+        float gmax = -INFINITY;                       // one clamp floor for the whole call (ipynb cell 15: log_spec.max())
+        for (float v : mx) gmax = std::max(gmax, v);
+        hipLaunchKernelGGL(clamp_db_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_out, tot, gmax - 80.0f);
+    }
+    if (copy_async(out_db, d_out, tot * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "oww_mel: D2H failed"));
+    return 0;                                         // (synchronised: the buffers are idle when they go)
 }
 
 int oww_mel(oww_ctx* h, const int16_t* pcm, int32_t B, int32_t n, float* out_db) { OWW_GUARD_BEGIN return mel_impl(h, pcm, B, n, out_db, false); OWW_GUARD_END }
@@ -2717,42 +2616,40 @@ int oww_embed_clips(oww_ctx* h, const int16_t* pcm, int32_t pcm_on_device, int32
     const int Bp = std::min(h->Spad, (B + 7) / 8 * 8);   // run_cnn covers whole groups of 8 streams: their (zero) mel rows must exist
     const size_t lead = 4 * 32;                         // four lead-in rows in front of clip 0 (other clips: the previous clip's tail;
                                                         // their content never reaches a returned embedding)
-    int16_t* d_in = nullptr; float* d_mel = nullptr; float* d_max = nullptr; float* d_out = nullptr;
-    int rc = park_state(h, B, true);
-    if (rc) return rc;
-    do {
+    if (int rc = park_state(h, B, true)) return rc;
+    DevBuf<int16_t> d_in; DevBuf<float> d_mel, d_max, d_out;
+    // the clips' embeddings; whatever it returns, the parked state goes back and the stream is drained before the buffers above go
+    auto run = [&]() -> int {
         if (!pcm_on_device) {
-            if (dev_alloc(&d_in, (size_t)B * n * sizeof(int16_t)) != hipSuccess) { rc = fail(OWW_ENOMEM, "oww_embed_clips: out of device memory"); break; }
-            if (copy_async(d_in, pcm, (size_t)B * n * sizeof(int16_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_embed_clips: H2D failed"); break; }
+            if (d_in.alloc((size_t)B * n)) return fail(OWW_ENOMEM, "oww_embed_clips: out of device memory");
+            if (copy_async(d_in, pcm, (size_t)B * n * sizeof(int16_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(OWW_EHIP, "oww_embed_clips: H2D failed");
         }
-        if (dev_alloc(&d_mel, (lead + (size_t)Bp * F * 32) * sizeof(float)) != hipSuccess ||
-            dev_alloc(&d_max, (size_t)B * sizeof(float)) != hipSuccess ||
-            (!out_on_device && dev_alloc(&d_out, (size_t)B * n_out * 96 * sizeof(float)) != hipSuccess)) { rc = fail(OWW_ENOMEM, "oww_embed_clips: out of device memory"); break; }
-        float* o = out_on_device ? out : d_out;
+        if (d_mel.alloc(lead + (size_t)Bp * F * 32) || d_max.alloc(B) || (!out_on_device && d_out.alloc((size_t)B * n_out * 96)))
+            return fail(OWW_ENOMEM, "oww_embed_clips: out of device memory");
+        float* o = out_on_device ? out : d_out.get();
         if (hipMemsetAsync(d_mel, 0, lead * sizeof(float), h->stream) != hipSuccess ||
-            (Bp > B && hipMemsetAsync(d_mel + lead + (size_t)B * F * 32, 0, (size_t)(Bp - B) * F * 32 * sizeof(float), h->stream) != hipSuccess)) { rc = fail(OWW_EHIP, "oww_embed_clips: memset failed"); break; }
+            (Bp > B && hipMemsetAsync(d_mel + lead + (size_t)B * F * 32, 0, (size_t)(Bp - B) * F * 32 * sizeof(float), h->stream) != hipSuccess)) return fail(OWW_EHIP, "oww_embed_clips: memset failed");
         StepArgs a = step_args(h);
         a.mel = d_mel + lead;
-        if ((rc = launch_mel(h, a, pcm_on_device ? pcm : d_in, B, n, F, 0, d_mel + lead, d_max))) break;
+        if (int rc = launch_mel(h, a, pcm_on_device ? pcm : d_in.get(), B, n, F, 0, d_mel + lead, d_max)) return rc;
         hipLaunchKernelGGL(clamp_transform_rows_kernel, dim3((F * 32 + 255) / 256, B), dim3(256), 0, h->stream, d_mel + lead, F * 32, d_max);
-        for (int it = 0; it < n_steps && !rc; ++it) {
-            rc = run_cnn(h, a, B, F * 32, (it * 8 - 4) * 32);
-            if (rc) break;
+        for (int it = 0; it < n_steps; ++it) {
+            if (int rc = run_cnn(h, a, B, F * 32, (it * 8 - 4) * 32)) return rc;
             hipLaunchKernelGGL(advance_kernel, dim3((h->Spad + 255) / 256), dim3(256), 0, h->stream, h->d_nfeat, h->Spad, (const uint8_t*)nullptr);
             if (it >= 9 && hipMemcpy2DAsync(o + (size_t)(it - 9) * 96, (size_t)n_out * 96 * sizeof(float), h->d_emb, 96 * sizeof(float),
                                             96 * sizeof(float), B, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-                rc = fail(OWW_EHIP, "oww_embed_clips: gather failed");
+                return fail(OWW_EHIP, "oww_embed_clips: gather failed");
         }
-        if (rc) break;
-        if (!out_on_device && copy_async(out, d_out, (size_t)B * n_out * 96 * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_embed_clips: D2H failed"); break; }
-        if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_embed_clips: device error: %s", hipGetErrorString(hipGetLastError())); break; }
-    } while (0);
+        if (!out_on_device && copy_async(out, d_out, (size_t)B * n_out * 96 * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess) return fail(OWW_EHIP, "oww_embed_clips: D2H failed");
+        if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "oww_embed_clips: device error: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    };
+    const int rc = run();
     const int rc_restore = park_state(h, B, false);
     (void)hipStreamSynchronize(h->stream);
-    (void)dev_free(d_in); (void)dev_free(d_mel); (void)dev_free(d_max); (void)dev_free(d_out);
-    if (!rc) rc = rc_restore;
-    if (!rc) rc = range_check(h, "oww_embed_clips");
-    return rc;
+    if (rc) return rc;
+    if (rc_restore) return rc_restore;
+    return range_check(h, "oww_embed_clips");
     OWW_GUARD_END
 }
 
@@ -2763,24 +2660,17 @@ int oww_head(oww_ctx* h, int32_t head, const float* features, int32_t B, float* 
     HIPCHK(hipSetDevice(h->cfg.device));
     const HeadHost& hh = h->heads[head];
     const size_t nf = (size_t)B * hh.T * 96;
-    float* d_f = nullptr; float* d_raw = nullptr;
-    int rc = 0;
-    do {
-        if (dev_alloc(&d_f, nf * sizeof(float)) != hipSuccess || dev_alloc(&d_raw, (size_t)B * h->NL * sizeof(float)) != hipSuccess) {
-            rc = fail(OWW_ENOMEM, "oww_head: out of device memory"); break;
-        }
-        if (copy_async(d_f, features, nf * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_head: H2D failed"); break; }
-        if (hipMemsetAsync(d_raw, 0, (size_t)B * h->NL * sizeof(float), h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_head: memset failed"); break; }
-        if ((rc = run_heads(h, step_args(h), B, false, d_f, head, d_raw, 0))) break;
-        std::vector<float> raw((size_t)B * h->NL);
-        if (copy_async(raw.data(), d_raw, raw.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(OWW_EHIP, "oww_head: D2H failed"); break; }
-        for (int b = 0; b < B; ++b)
-            for (int o = 0; o < hh.n_out; ++o) out[(size_t)b * hh.n_out + o] = raw[(size_t)b * h->NL + hh.out_col + o];
-        rc = range_check(h, "oww_head");
-    } while (0);
-    (void)dev_free(d_f); (void)dev_free(d_raw);
-    return rc;
+    DevBuf<float> d_f, d_raw;
+    if (d_f.alloc(nf) || d_raw.alloc((size_t)B * h->NL)) return fail(OWW_ENOMEM, "oww_head: out of device memory");
+    if (copy_async(d_f, features, nf * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "oww_head: H2D failed"));
+    if (hipMemsetAsync(d_raw, 0, (size_t)B * h->NL * sizeof(float), h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "oww_head: memset failed"));
+    if (int rc = run_heads(h, step_args(h), B, false, d_f, head, d_raw, 0)) return drained(h, rc);
+    std::vector<float> raw((size_t)B * h->NL);
+    if (copy_async(raw.data(), d_raw, raw.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "oww_head: D2H failed"));
+    for (int b = 0; b < B; ++b)
+        for (int o = 0; o < hh.n_out; ++o) out[(size_t)b * hh.n_out + o] = raw[(size_t)b * h->NL + hh.out_col + o];
+    return range_check(h, "oww_head");
     OWW_GUARD_END
 }
 
@@ -3013,12 +2903,10 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
     const size_t o_w1 = hb.add(pk);
     const size_t w1_floats = pk.size();
     pack_hx_net(net, ht, true, hb, pack);
-    float* d_img = nullptr;
-    HIPCHK(dev_alloc(&d_img, hb.data.size() * sizeof(float)));
-    if (copy_sync(d_img, hb.data.data(), hb.data.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)dev_free(d_img);
+    DevBuf<float> d_img;                             // (the head's when the self-test passes, released on every other way out)
+    HIPCHK(herr(d_img.alloc(hb.data.size())));
+    if (copy_sync(d_img, hb.data.data(), hb.data.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return fail(OWW_EHIP, "oww_bank_add: weight upload failed");
-    }
     owh::BankHeadDev dv{};
     dv.w1hx = d_img + o_w1; dv.T = T; dv.ht = ht;
     dv.net = make_hx_net(net, ht, pack, d_img, nullptr, h->hx_efeat);
@@ -3026,34 +2914,28 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
     //      fixed heads to (1e-3)
     std::vector<float> win;
     const int B = probe_windows(h->probe_emb, h->probe_nb, T, win);
-    float *d_win = nullptr, *d_out = nullptr; int* d_ent = nullptr; owh::BankTile* d_til = nullptr; owh::BankHeadDev* d_hd = nullptr;
+    DevBuf<float> d_win, d_out; DevBuf<int> d_ent; DevBuf<owh::BankTile> d_til; DevBuf<owh::BankHeadDev> d_hd;
     std::vector<int> ent(B);
     for (int i = 0; i < B; ++i) ent[i] = i;
     std::vector<owh::BankTile> til;
     for (int o0 = 0; o0 < B; o0 += 128) til.push_back(owh::BankTile{0, o0, std::min(128, B - o0), 0});
     std::vector<float> got(B, 0.f);
-    int rc = 0;
-    if (dev_alloc(&d_win, win.size() * sizeof(float)) != hipSuccess || dev_alloc(&d_out, (size_t)B * sizeof(float)) != hipSuccess ||
-        dev_alloc(&d_ent, (size_t)B * sizeof(int)) != hipSuccess || dev_alloc(&d_til, til.size() * sizeof(owh::BankTile)) != hipSuccess ||
-        dev_alloc(&d_hd, sizeof(owh::BankHeadDev)) != hipSuccess) rc = fail(OWW_ENOMEM, "oww_bank_add: out of device memory (self-test)");
-    if (!rc && (copy_sync(d_win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-                copy_sync(d_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-                copy_sync(d_til, til.data(), til.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice) != hipSuccess ||
-                copy_sync(d_hd, &dv, sizeof dv, hipMemcpyHostToDevice) != hipSuccess)) rc = fail(OWW_EHIP, "oww_bank_add: self-test upload failed");
+    if (d_win.alloc(win.size()) || d_out.alloc(B) || d_ent.alloc(B) || d_til.alloc(til.size()) || d_hd.alloc(1))
+        return fail(OWW_ENOMEM, "oww_bank_add: out of device memory (self-test)");
+    if (copy_sync(d_win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        copy_sync(d_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+        copy_sync(d_til, til.data(), til.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice) != hipSuccess ||
+        copy_sync(d_hd, &dv, sizeof dv, hipMemcpyHostToDevice) != hipSuccess) return fail(OWW_EHIP, "oww_bank_add: self-test upload failed");
     const int flag_before = h->h_range ? *(volatile int*)h->h_range : 0;
-    if (!rc) {
-        if (int r2 = bank_quiesce(h)) rc = r2;
-    }
-    if (!rc) {
-        owh::BankParams bp{};
-        bp.feat = d_win; bp.ext = 1; bp.TR = T; bp.tiles = d_til; bp.entries = d_ent; bp.heads = d_hd; bp.K = 1;
-        bp.raw = d_out; bp.range_flag = h->d_range; bp.fscale = std::ldexp(1.0f, h->hx_efeat);
-        if (ht == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 4>), dim3((unsigned)til.size()), dim3(256), 0, h->stream, bp);
-        else hipLaunchKernelGGL((owh::heads_bank_kernel<4, 8>), dim3((unsigned)til.size()), dim3(256), 0, h->stream, bp);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-            copy_sync(got.data(), d_out, (size_t)B * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(OWW_EHIP, "oww_bank_add: self-test run failed");
-    }
-    for (void* ptr : {(void*)d_win, (void*)d_out, (void*)d_ent, (void*)d_til, (void*)d_hd}) if (ptr) (void)dev_free(ptr);
+    if (int rc = bank_quiesce(h)) return rc;
+    owh::BankParams bp{};
+    bp.feat = d_win; bp.ext = 1; bp.TR = T; bp.tiles = d_til; bp.entries = d_ent; bp.heads = d_hd; bp.K = 1;
+    bp.raw = d_out; bp.range_flag = h->d_range; bp.fscale = std::ldexp(1.0f, h->hx_efeat);
+    if (ht == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 4>), dim3((unsigned)til.size()), dim3(256), 0, h->stream, bp);
+    else hipLaunchKernelGGL((owh::heads_bank_kernel<4, 8>), dim3((unsigned)til.size()), dim3(256), 0, h->stream, bp);
+    int rc = 0;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+        copy_sync(got.data(), d_out, (size_t)B * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = drained(h, fail(OWW_EHIP, "oww_bank_add: self-test run failed"));
     double err = 0.0;
     bool finite = true;
     for (int w = 0; w < B && !rc; ++w) {
@@ -3066,11 +2948,11 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
         rc = fail(OWW_ERANGE, "oww_bank_add: with these weights the fp16-split heads kernel differs from a float64 evaluation by %.3g on the "
                   "commit's probe embeddings (tolerance 1e-3)%s: load the head as a fixed head of a use_mfma = 1 handle", err,
                   raised ? ", an activation left the f16 range" : "");
-    if (rc) { (void)dev_free(d_img); return rc; }
+    if (rc) return rc;
     HIPCHK(copy_sync(h->d_bank_heads + id, &dv, sizeof dv, hipMemcpyHostToDevice));
     oww_ctx::BankHead& bh = h->bank[id];
     bh = oww_ctx::BankHead{};
-    bh.live = true; bh.T = T; bh.hidden = H; bh.has_ln = has_ln; bh.ht = ht; bh.d_img = d_img; bh.dev = dv;
+    bh.live = true; bh.T = T; bh.hidden = H; bh.has_ln = has_ln; bh.ht = ht; bh.d_img = std::move(d_img); bh.dev = dv;
     bh.w1_bytes = w1_floats * sizeof(float);
     const int pat0 = 0; const float thr0 = NAN;
     HIPCHK(copy_sync(h->d_bank_pat + id, &pat0, sizeof pat0, hipMemcpyHostToDevice));
@@ -3090,8 +2972,7 @@ int oww_bank_remove(oww_ctx* h, int32_t id) {
     if (!changed.empty()) HIPCHK(copy_sync(h->d_bank_sub, h->bank_sub.data(), h->bank_sub.size() * sizeof(int), hipMemcpyHostToDevice));
     if (int rc = bank_clear(h, changed)) return rc;
     if (int rc = sv_drop_bank(h, changed)) return rc;
-    (void)dev_free(h->bank[id].d_img);
-    h->bank[id] = oww_ctx::BankHead{};
+    h->bank[id] = oww_ctx::BankHead{};               // (releases the head's image)
     return bank_route(h);
     OWW_GUARD_END
 }
