@@ -768,7 +768,8 @@ class StreamEngine:
 
     def embed_clips(self, pcm: np.ndarray) -> np.ndarray:
         """AudioFeatures.embed_clips on the device (utils.py:354-385): int16 [B, n] -> [B, n_windows, 96], mel, window
-        walk and CNN without leaving HBM.  Clobbers the streaming state of streams [0, B)."""
+        walk and CNN without leaving HBM.  Borrows the streaming machinery of streams [0, B) (B rounded up to 8): their state is
+        parked for the call and put back, so live streams continue bit for bit (ABI 2)."""
         pcm = np.ascontiguousarray(pcm)
         if pcm.dtype != np.int16 or pcm.ndim != 2:
             raise ValueError("embed_clips expects a 2-D int16 array [B, samples]")
@@ -788,11 +789,18 @@ class StreamEngine:
 
     def embed(self, mel_rows: np.ndarray) -> np.ndarray:
         """embedding_model_predict over sliding windows (utils.py:229-236): [B, 76+8j, 32] -> [B, j+1, 96].
-        Clobbers the streaming state of streams [0, B)."""
+        Borrows the streaming machinery of streams [0, B) (B rounded up to 8): their state is parked for the call and put back, so
+        live streams continue bit for bit (ABI 2)."""
         m = np.ascontiguousarray(mel_rows, dtype=np.float32)
         if m.ndim == 2:
             m = m[None]
+        if m.ndim != 3 or m.shape[2] != 32:
+            raise ValueError(f"embed expects mel rows [B, 76 + 8 j, 32], got {m.shape}")
         B, rows, _ = m.shape
+        if rows < 76 or (rows - 76) % 8:
+            raise ValueError(f"embed expects 76 + 8 j mel rows per clip (whole windows), got {rows}")
+        if B < 1 or B > self.n_streams_padded:
+            raise ValueError(f"between 1 and {self.n_streams_padded} clips per call (the handle's stream count)")
         out = np.empty((B, (rows - 76) // 8 + 1, EMB_DIM), dtype=np.float32)
         _lib.check(self._lib.oww_embed(self._h, _ptr(m), B, rows, _ptr(out)))
         return out
