@@ -284,6 +284,56 @@ const int16_t* oww_ingest_dev(const oww_ctx* h);
 int  oww_step_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const uint8_t* stream_on, int stream_on_on_device,
                      float* scores, int scores_on_device);
 
+/* ---- ingest classes: every stream its own rate and encoding in one launch ---------------------------------------------------------------
+ * The serving example lets every connection announce its own sample rate and converts each message on the host
+ * (examples/web/streaming_server.py:50-59); the entries above serve that only when all streams of a handle speak one format.  A
+ * CLASS is what oww_ingest_configure takes -- (encoding, p, q, taps [q][n_taps], n_taps; n_taps = 0 with p = q = 1: decode only) -- a
+ * handle holds a table of up to OWW_INGEST_MAX_CLASSES of them, and every stream belongs to one.  Per stream the arithmetic is that of
+ * oww_ingest on a handle configured with the stream's class, bit for bit (same decode, same k-ordered fmaf chain over the padded row,
+ * same rounding, same history).
+ *   oww_ingest_configure_classes   after oww_commit; replaces any earlier ingest configuration (single or classes; per-class checks as
+ *                       oww_ingest_configure, OWW_EINVAL naming the class).  Allocates one history int16 [S][Hpad], Hpad = the largest
+ *                       class's n_taps - 1 rounded up to 8 (a stream uses the first n_taps - 1 of its own class; the rest stays zero),
+ *                       the device table of class parameters, the padded banks back to back and the per-stream class id.  Every
+ *                       stream starts in class 0 with a zero history; the state-record layout is rebuilt on demand.
+ *   oww_ingest_assign   (examples/web/streaming_server.py:50-52: the connection's rate message) sets the class of the listed streams
+ *                       and zeroes their histories: a caller arriving in a new format starts from silence.  Ordered on the handle's
+ *                       stream like oww_reset, so it may follow submitted steps.  Unknown class, stream id out of range: OWW_EINVAL;
+ *                       a handle without classes: OWW_ESTATE; nothing has moved then.
+ *   oww_ingest_mixed    (examples/web/streaming_server.py:53-59: the per-message conversion) row s of `in` starts at s * row_bytes and
+ *                       holds n_in(c) = n_out * p_c / q_c samples in the encoding of stream s's class c.  row_bytes: a multiple of 16
+ *                       and at least the largest configured class's n_in * bytes per sample.  OWW_EINVAL, before any history moves,
+ *                       when n_out * p_c is no multiple of q_c for a configured class or when a class's history + message exceed
+ *                       the kernel's 96 KB of LDS staging.  out, stream_on: as oww_ingest (out == NULL: the staging buffer of
+ *                       oww_ingest_dev).
+ *   oww_step_ingest_mixed   oww_ingest_mixed into the staging buffer, then oww_step (n_out / 1280 chunks) or oww_step_masked (one
+ *                       chunk), with every check of oww_step_ingest made before anything moves.
+ *   oww_submit_ingest_mixed (examples/web/streaming_server.py:53-59 in the pipelined form of oww_submit_masked) one masked chunk,
+ *                       n_out = 1280, stream_on == NULL: every stream.  in_host [S][row_bytes] goes up on the upload stream into the
+ *                       slot's own device buffer; the compute stream waits for it, runs the mixed ingest into the staging buffer and
+ *                       then the step; scores (and events) come down as after oww_submit; pair it with oww_collect.  in_host must
+ *                       stay unmodified until that oww_collect; two steps in flight at most (OWW_ESTATE).
+ * State: oww_reset zeroes the history of the streams it resets and KEEPS their class; oww_move_streams, oww_state_export and
+ * oww_state_import carry history and class: the record's ingest part is Hpad / 2 words plus one 16-byte piece with the class id.
+ * The fingerprint covers the whole table and every bank, so a record is refused by a handle with another table.  oww_ingest and
+ * oww_step_ingest on a handle configured with classes, and the entries here on a handle configured with oww_ingest_configure, are
+ * refused with OWW_ESTATE.  One launch serves all classes: its dynamic LDS is the largest class's need, which sets the occupancy for
+ * every workgroup, and workgroups differ in work with their class.  Not counted by oww_kernel_times. */
+#define OWW_INGEST_MAX_CLASSES 16
+typedef struct oww_ingest_class {
+    int32_t encoding;        /* OWW_ENC_* */
+    int32_t p, q;            /* input rate / 16000 in lowest terms */
+    int32_t n_taps;          /* even, <= 4096; 0 with p = q = 1: decode only */
+    const float* taps;       /* [q][n_taps]; ignored when n_taps = 0 */
+} oww_ingest_class;
+int  oww_ingest_configure_classes(oww_ctx* h, int32_t n_classes, const oww_ingest_class* classes);
+int  oww_ingest_assign(oww_ctx* h, const int32_t* stream_ids, int32_t n, const uint8_t* class_ids);
+int  oww_ingest_mixed(oww_ctx* h, const void* in, int in_on_device, int64_t row_bytes, int32_t n_out, const uint8_t* stream_on,
+                      int stream_on_on_device, int16_t* out, int out_on_device);
+int  oww_step_ingest_mixed(oww_ctx* h, const void* in, int in_on_device, int64_t row_bytes, int32_t n_out, const uint8_t* stream_on,
+                           int stream_on_on_device, float* scores, int scores_on_device);
+int  oww_submit_ingest_mixed(oww_ctx* h, const void* in_host, int64_t row_bytes, const uint8_t* stream_on);
+
 /* ---- head bank: each stream scored only by the wake-word models it subscribed to -----------------------------------------------------
  * openWakeWord's training pipeline (train.py, examples/custom_model.yml) yields one small binary head per phrase; a server that carries
  * many users' own phrases scores each connection with ITS heads, not with every head of the handle.  The embedding CNN (~94 % of a step)

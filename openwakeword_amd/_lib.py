@@ -22,6 +22,13 @@ class Config(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class IngestClass(C.Structure):
+    """oww_ingest_class (include/owwhip.h)"""
+    _fields_ = [("encoding", C.c_int32), ("p", C.c_int32), ("q", C.c_int32), ("n_taps", C.c_int32), ("taps", C.c_void_p)]
+
+
+INGEST_MAX_CLASSES = 16  # OWW_INGEST_MAX_CLASSES
+
 # every symbol include/owwhip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -62,6 +69,11 @@ SYMBOLS = {
     "oww_ingest": (C.c_int, [_P, _P, C.c_int, C.c_int32, _P, C.c_int, _P, C.c_int]),
     "oww_ingest_dev": (_P, [_P]),
     "oww_step_ingest": (C.c_int, [_P, _P, C.c_int, C.c_int32, _P, C.c_int, _P, C.c_int]),
+    "oww_ingest_configure_classes": (C.c_int, [_P, C.c_int32, C.POINTER(IngestClass)]),
+    "oww_ingest_assign": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "oww_ingest_mixed": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int32, _P, C.c_int, _P, C.c_int]),
+    "oww_step_ingest_mixed": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int32, _P, C.c_int, _P, C.c_int]),
+    "oww_submit_ingest_mixed": (C.c_int, [_P, _P, C.c_int64, _P]),
     "oww_mel": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "oww_mel_clips": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "oww_embed": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),

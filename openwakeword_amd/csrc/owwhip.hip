@@ -19,6 +19,7 @@
 
 #include "owwhip.h"
 #include "owwhip_pack.h"
+#include "owwhip_ingest.h"
 #include "owwhip_mem.h"
 #include "owwhip_kernels.h"
 #include "owwhip_rr.h"
@@ -217,6 +218,7 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     // host-fed pipeline (oww_submit / oww_collect): two steps in flight, uploads and score downloads on their own streams
     struct IngestSlot {
         DevBuf<int16_t> d_pcm; DevBuf<float> d_scores; PinnedBuf<float> h_scores;
+        DevBuf<char> d_mix;          // oww_submit_ingest_mixed: [S][row_bytes] in the streams' own formats, allocated at first use
         PinnedBuf<uint8_t> h_on;     // page-locked staging of a masked submit's participation mask
         owm::Event up, done, down;
         bool busy = false;
@@ -260,6 +262,13 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     DevBuf<int16_t> d_ing_out;                     // 16 kHz staging [S][n_out] (oww_ingest_dev), grown on demand
     DevBuf<char> d_ing_in;                         // a host message on its way in, in bytes
     DevBuf<uint8_t> d_ing_on;                      // [S] a host mask on its way in
+    // ingest classes (oww_ingest_configure_classes / oww_ingest_mixed; owk::ingest_mixed_kernel).  ing_ready is set as well, ing_Hpad is
+    // the table's largest and d_ing_hist / d_ing_taps hold [S][Hpad_max] and every bank: reset and the state records read those alone.
+    bool ing_mixed = false;
+    owi::Table ing_tab;                            // host copy of the table and banks (upload source, fingerprint, checks)
+    DevBuf<IngestClass> d_ing_table;
+    DevBuf<uint32_t> d_ing_cls;                    // [S] each stream's class: a word per stream, so that the state records carry it
+    DevBuf<int> d_ing_newcls;                      // the class list of oww_ingest_assign on its way in
     DevBuf<uint8_t> d_on;            // oww_step_masked: [Spad] participation mask of the step being launched (pad streams 0)
     // masked step with few participants: the device copy of the group lists (StepArgs::gl) and its two page-locked staging buffers,
     // used in turn (build_active_lists)
@@ -1602,6 +1611,7 @@ int state_layout(oww_ctx* h) {
     if (h->vad) flat(h->d_vadlast, 1, 1);
     if (K) { flat(h->d_bank_raw, K, K); flat(h->d_bank_scores, K, K); flat(h->d_bank_npred, K, K); flat(h->d_bank_ring, K * OWW_SCORE_RING, K * OWW_SCORE_RING); }
     if (h->ing_ready && h->ing_Hpad) flat(h->d_ing_hist, (size_t)h->ing_Hpad / 2, (size_t)h->ing_Hpad / 2);   // oww_ingest history (int16 pairs)
+    if (h->ing_ready && h->ing_mixed) flat(h->d_ing_cls, 1, 1);            // ... and the stream's class: one word in a 16-byte piece of its own
     h->st_flat_quads = off / 4;
     auto group = [&](float* live, int spg, int ppr, bool inter, uint32_t block_words) -> int {
         const int R = ppr >= 4 ? 1 : 4 / ppr;
@@ -1632,7 +1642,12 @@ int state_layout(oww_ctx* h) {
         fp = fp_mix(fp, hh.blob.data(), hh.blob.size() * sizeof(float));
     }
     fp = fp_mix(fp, h->vad_blob.data(), h->vad_blob.size() * sizeof(float));
-    if (h->ing_ready) {                          // a handle that never configured ingest hashes what it always hashed
+    if (h->ing_ready && h->ing_mixed) {          // ingest classes: the whole table and every bank
+        const int32_t tag[2] = {-1, (int32_t)h->ing_tab.dev.size()};       // (no single configuration has encoding -1)
+        fp = fp_mix(fp, tag, sizeof tag);
+        fp = fp_mix(fp, h->ing_tab.dev.data(), h->ing_tab.dev.size() * sizeof(owi::ClassDev));
+        fp = fp_mix(fp, h->ing_tab.banks.data(), h->ing_tab.banks.size() * sizeof(float));
+    } else if (h->ing_ready) {                   // a handle that never configured ingest hashes what it always hashed
         const int32_t ig[4] = {h->ing_enc, h->ing_p, h->ing_q, h->ing_n_taps};
         fp = fp_mix(fp, ig, sizeof ig);
         fp = fp_mix(fp, h->ing_taps.data(), h->ing_taps.size() * sizeof(float));
@@ -2098,7 +2113,10 @@ static int ensure_ingest(oww_ctx* h) {
     return 0;
 }
 
-static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const uint8_t* stream_on);
+static int launch_ingest_mixed(oww_ctx* h, const void* d_in, long long row_bytes, int n_out, const uint8_t* d_on, int16_t* out, const owi::Geometry& g);
+// mix != nullptr (oww_submit_ingest_mixed): one chunk per stream in the streams' own formats, [S][row_bytes], checked by the caller
+static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const uint8_t* stream_on, const void* mix = nullptr,
+                       long long row_bytes = 0, const owi::Geometry* geo = nullptr);
 
 int oww_submit(oww_ctx* h, const int16_t* pcm, int32_t n_chunks) { OWW_GUARD_BEGIN return submit_impl(h, pcm, n_chunks, nullptr); OWW_GUARD_END }
 
@@ -2111,9 +2129,10 @@ int oww_submit_masked(oww_ctx* h, const int16_t* pcm, const uint8_t* stream_on) 
     OWW_GUARD_END
 }
 
-static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const uint8_t* stream_on) {
+static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const uint8_t* stream_on, const void* mix, long long row_bytes,
+                       const owi::Geometry* geo) {
     if (!h || !h->committed) return fail(OWW_ESTATE, "oww_submit: handle not committed");
-    if (!pcm) return fail(OWW_EINVAL, "oww_submit: pcm is null");
+    if (!pcm && !mix) return fail(OWW_EINVAL, "oww_submit: pcm is null");
     if (n_chunks < 1 || n_chunks > h->kmax) return fail(OWW_EINVAL, "oww_submit: n_chunks=%d outside [1,%d]", n_chunks, h->kmax);
     if (int rc = range_check(h, "oww_submit")) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -2122,7 +2141,15 @@ static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const u
     auto& sl = h->slot[h->n_submit & 1];
     if (sl.busy) return fail(OWW_ESTATE, "oww_submit: two steps already in flight, call oww_collect first");
     const size_t n_pcm = (size_t)h->S * OWW_CHUNK * n_chunks;
-    HIPCHK(copy_async(sl.d_pcm, pcm, n_pcm * sizeof(int16_t), hipMemcpyHostToDevice, h->up_stream));
+    if (mix) {
+        const size_t nb = (size_t)h->S * (size_t)row_bytes;
+        if (nb > sl.d_mix.capacity()) {                // first use, or wider rows than before (the slot was collected: nothing reads the old block)
+            if (sl.d_mix.reserve(nb)) return fail(OWW_ENOMEM, "oww_submit_ingest_mixed: out of device memory for %zu bytes", nb);
+        }
+        HIPCHK(copy_async(sl.d_mix, mix, nb, hipMemcpyHostToDevice, h->up_stream));
+    } else {
+        HIPCHK(copy_async(sl.d_pcm, pcm, n_pcm * sizeof(int16_t), hipMemcpyHostToDevice, h->up_stream));
+    }
     HIPCHK(hipEventRecord(sl.up, h->up_stream));
     HIPCHK(hipStreamWaitEvent(h->stream, sl.up, 0));
     StepArgs a = step_args(h);
@@ -2135,8 +2162,10 @@ static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const u
         n_act = build_active_lists(h, stream_on, a);
         if (n_act < -1) return n_act + 100;
     }
+    if (mix && n_act != 0)                             // (both slots' ingest launches and steps are ordered on the compute stream: one staging buffer)
+        if (int rc = launch_ingest_mixed(h, sl.d_mix, row_bytes, OWW_CHUNK, stream_on ? (const uint8_t*)h->d_on : nullptr, h->d_ing_out, *geo)) return rc;
     if (n_act != 0)
-        if (int rc = launch_step(h, a, sl.d_pcm, n_chunks)) return rc;
+        if (int rc = launch_step(h, a, mix ? (const int16_t*)h->d_ing_out : (const int16_t*)sl.d_pcm, n_chunks)) return rc;
     const oww_ctx::EventBuf& eb = h->evt_slot[h->n_submit & 1];
     if (events_on(h)) { if (int rc = launch_events(h, a, eb, n_act != 0)) return rc; h->evt_cur = nullptr; }
     const size_t nb = (size_t)h->S * h->NL * sizeof(float);
@@ -2398,6 +2427,7 @@ int oww_ingest_configure(oww_ctx* h, int32_t encoding, int32_t p, int32_t q, con
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipStreamSynchronize(h->stream));               // an earlier oww_ingest may still read the old bank and history
     h->d_ing_taps.reset(); h->d_ing_hist.reset();
+    h->d_ing_table.reset(); h->d_ing_cls.reset(); h->ing_mixed = false; h->ing_tab = owi::Table();   // (replaces a class table as well)
     h->ing_ready = false;
     h->d_st_flat.reset(); h->st_ready = false;               // the record layout gains, loses or resizes its history section: rebuilt on demand
     const int ntp = (n_taps + 3) / 4 * 4, Hpad = n_taps ? (n_taps - 1 + 7) / 8 * 8 : 0;
@@ -2428,6 +2458,7 @@ const int16_t* oww_ingest_dev(const oww_ctx* h) { return h ? h->d_ing_out : null
 static int ingest_check(const oww_ctx* h, const char* fn, const void* in, int32_t n_in, long long* n_out) {
     if (!h || !h->committed) return fail(OWW_ESTATE, "%s: handle not committed", fn);
     if (!h->ing_ready) return fail(OWW_ESTATE, "%s: ingest is not configured (oww_ingest_configure)", fn);
+    if (h->ing_mixed) return fail(OWW_ESTATE, "%s: the handle is configured with ingest classes: use the _mixed entry", fn);
     if (!in) return fail(OWW_EINVAL, "%s: null argument: in", fn);
     if (n_in < 1) return fail(OWW_EINVAL, "%s: bad argument (n_in=%d)", fn, n_in);
     if (((long long)n_in * h->ing_q) % h->ing_p)
@@ -2525,6 +2556,160 @@ int oww_step_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, 
     if (int rc = oww_ingest(h, in, in_on_device, n_in, stream_on, stream_on_on_device, nullptr, 1)) return rc;
     if (stream_on) return oww_step_masked(h, h->d_ing_out, 1, stream_on, stream_on_on_device, scores, scores_on_device);
     return oww_step(h, h->d_ing_out, 1, n_chunks, scores, scores_on_device);
+    OWW_GUARD_END
+}
+
+// ---- ingest classes (header: oww_ingest_configure_classes / oww_ingest_assign / oww_ingest_mixed / oww_step_ingest_mixed /
+//      oww_submit_ingest_mixed; host checks and table: owwhip_ingest.h; kernel: ingest_mixed_kernel in owwhip_kernels.h) ----
+static_assert(owi::kTile == IG_TILE && sizeof(owi::ClassDev) == sizeof(IngestClass), "owwhip_ingest.h restates the kernel's tile and table row");
+
+int oww_ingest_configure_classes(oww_ctx* h, int32_t n_classes, const oww_ingest_class* classes) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed) return fail(OWW_ESTATE, "oww_ingest_configure_classes: handle not committed");
+    owi::Table tab;
+    if (int rc = owi::table_build("oww_ingest_configure_classes", n_classes, classes, tab)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));               // an earlier ingest may still read the old banks and histories
+    h->d_ing_taps.reset(); h->d_ing_hist.reset(); h->d_ing_table.reset(); h->d_ing_cls.reset();
+    h->ing_ready = false; h->ing_mixed = false;
+    h->d_st_flat.reset(); h->st_ready = false;               // the record layout changes: rebuilt on demand
+    const int Hpad = tab.Hpad_max;
+    if (h->d_ing_taps.alloc(tab.banks.size()) || h->d_ing_table.alloc(tab.dev.size()) || h->d_ing_cls.alloc(h->S) ||
+        (Hpad && h->d_ing_hist.alloc((size_t)h->S * Hpad))) {
+        h->d_ing_taps.reset(); h->d_ing_hist.reset(); h->d_ing_table.reset(); h->d_ing_cls.reset();
+        return fail(OWW_ENOMEM, "oww_ingest_configure_classes: out of device memory for %d streams x %d history samples and %zu bank floats", h->S, Hpad, tab.banks.size());
+    }
+    HIPCHK(copy_sync(h->d_ing_taps, tab.banks.data(), tab.banks.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(copy_sync(h->d_ing_table, tab.dev.data(), tab.dev.size() * sizeof(owi::ClassDev), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(h->d_ing_cls, 0, (size_t)h->S * sizeof(uint32_t), h->stream));
+    if (Hpad) HIPCHK(hipMemsetAsync(h->d_ing_hist, 0, (size_t)h->S * Hpad * sizeof(int16_t), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (!h->d_ing_out) {
+        if (h->d_ing_out.alloc((size_t)h->S * OWW_CHUNK)) return fail(OWW_ENOMEM, "oww_ingest_configure_classes: out of device memory");
+        HIPCHK(hipMemset(h->d_ing_out, 0, h->d_ing_out.capacity() * sizeof(int16_t)));
+    }
+    h->ing_tab = std::move(tab);
+    h->ing_enc = 0; h->ing_p = 1; h->ing_q = 1; h->ing_n_taps = 0; h->ing_ntp = 0; h->ing_Hpad = Hpad;
+    h->ing_mixed = true; h->ing_ready = true;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+static int mixed_ready(const oww_ctx* h, const char* fn) {
+    if (!h || !h->committed) return fail(OWW_ESTATE, "%s: handle not committed", fn);
+    if (!h->ing_ready) return fail(OWW_ESTATE, "%s: ingest is not configured (oww_ingest_configure_classes)", fn);
+    if (!h->ing_mixed) return fail(OWW_ESTATE, "%s: the handle is configured with oww_ingest_configure, not with ingest classes", fn);
+    return 0;
+}
+
+int oww_ingest_assign(oww_ctx* h, const int32_t* stream_ids, int32_t n, const uint8_t* class_ids) {
+    OWW_GUARD_BEGIN
+    if (int rc = mixed_ready(h, "oww_ingest_assign")) return rc;
+    if (int rc = owi::assign_check("oww_ingest_assign", h->ing_tab, h->S, stream_ids, n, class_ids)) return rc;
+    if (n < 1) return OWW_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    std::vector<int> cls(class_ids, class_ids + n);
+    if (int rc = upload_ids(h, stream_ids, n)) return rc;
+    HIPCHK(grow(h, h->d_ing_newcls, (size_t)n));
+    HIPCHK(copy_async(h->d_ing_newcls, cls.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(ingest_assign_kernel, dim3(n), dim3(64), 0, h->stream, h->d_ing_hist, h->ing_Hpad, h->d_ing_cls, h->d_ids, h->d_ing_newcls, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));     // host lists may be reused by the caller
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+// the launch, on the handle's stream: d_in [S][row_bytes] and d_on (or null) are device pointers, `out` is a device pointer
+static int launch_ingest_mixed(oww_ctx* h, const void* d_in, long long row_bytes, int n_out, const uint8_t* d_on, int16_t* out, const owi::Geometry& g) {
+    IngestMixedParams m{};
+    m.in = static_cast<const char*>(d_in); m.out = out; m.hist = h->d_ing_hist; m.taps = h->d_ing_taps; m.on = d_on;
+    m.cls = h->d_ing_cls; m.table = h->d_ing_table;
+    m.row_bytes = row_bytes; m.n_out = n_out; m.Hpad_max = h->ing_Hpad; m.lds_floats = (int)(g.lds / sizeof(float));
+    m.in_aligned = !(reinterpret_cast<uintptr_t>(d_in) & 15);
+    m.vec_out = !(reinterpret_cast<uintptr_t>(out) & 15) && n_out % 8 == 0;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ingest_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(ingest_mixed_kernel, dim3(h->S), dim3(RS_NT), g.lds, h->stream, m);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int oww_ingest_mixed(oww_ctx* h, const void* in, int in_on_device, int64_t row_bytes, int32_t n_out, const uint8_t* stream_on,
+                     int stream_on_on_device, int16_t* out, int out_on_device) {
+    OWW_GUARD_BEGIN
+    if (int rc = mixed_ready(h, "oww_ingest_mixed")) return rc;
+    owi::Geometry g;
+    if (int rc = owi::mixed_check("oww_ingest_mixed", h->ing_tab, in, row_bytes, n_out, g)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t in_bytes = (size_t)h->S * (size_t)row_bytes;
+    const void* d_in = in;
+    if (!in_on_device) {
+        if (grow(h, h->d_ing_in, in_bytes) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest_mixed: out of device memory for %zu bytes", in_bytes);
+        HIPCHK(copy_async(h->d_ing_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
+        d_in = h->d_ing_in;
+    }
+    const uint8_t* d_on = stream_on;
+    if (stream_on && !stream_on_on_device) {
+        if (!h->d_ing_on) HIPCHK(herr(h->d_ing_on.alloc(h->S)));
+        HIPCHK(copy_async(h->d_ing_on, stream_on, h->S, hipMemcpyHostToDevice, h->stream));
+        d_on = h->d_ing_on;
+    }
+    const bool to_staging = !out || !out_on_device;
+    if (to_staging) {
+        const size_t need = (size_t)h->S * n_out;
+        if (need > h->d_ing_out.capacity()) {                // (a grown staging buffer starts zeroed, like the first)
+            if (grow(h, h->d_ing_out, need) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest_mixed: out of device memory for %zu bytes", need * sizeof(int16_t));
+            HIPCHK(hipMemset(h->d_ing_out, 0, need * sizeof(int16_t)));
+        }
+    }
+    if (int rc = launch_ingest_mixed(h, d_in, row_bytes, n_out, d_on, to_staging ? (int16_t*)h->d_ing_out : out, g)) return rc;
+    if (out && !out_on_device) {
+        const size_t row = (size_t)n_out * sizeof(int16_t);
+        if (!stream_on) {
+            HIPCHK(copy_async(out, h->d_ing_out, (size_t)h->S * row, hipMemcpyDeviceToHost, h->stream));
+        } else {                                             // only the rows of the streams that took part reach the caller's buffer, run by run
+            std::vector<uint8_t> on(h->S);
+            if (stream_on_on_device) HIPCHK(hipMemcpy(on.data(), stream_on, h->S, hipMemcpyDeviceToHost)); else memcpy(on.data(), stream_on, h->S);
+            for (int s = 0; s < h->S;) {
+                if (!on[s]) { ++s; continue; }
+                int e = s;
+                while (e < h->S && on[e]) ++e;
+                HIPCHK(copy_async(out + (size_t)s * n_out, h->d_ing_out + (size_t)s * n_out, (size_t)(e - s) * row, hipMemcpyDeviceToHost, h->stream));
+                s = e;
+            }
+        }
+    }
+    if (!in_on_device || (stream_on && !stream_on_on_device) || (out && !out_on_device)) HIPCHK(hipStreamSynchronize(h->stream));   // host buffers are the caller's again
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_step_ingest_mixed(oww_ctx* h, const void* in, int in_on_device, int64_t row_bytes, int32_t n_out, const uint8_t* stream_on,
+                          int stream_on_on_device, float* scores, int scores_on_device) {
+    OWW_GUARD_BEGIN
+    if (int rc = mixed_ready(h, "oww_step_ingest_mixed")) return rc;
+    owi::Geometry g;
+    if (int rc = owi::mixed_check("oww_step_ingest_mixed", h->ing_tab, in, row_bytes, n_out, g)) return rc;
+    if (n_out < OWW_CHUNK || n_out % OWW_CHUNK)
+        return fail(OWW_EINVAL, "oww_step_ingest_mixed: n_out = %d must be a positive multiple of %d", n_out, OWW_CHUNK);
+    const int n_chunks = n_out / OWW_CHUNK;
+    if (stream_on && n_chunks != 1) return fail(OWW_EINVAL, "oww_step_ingest_mixed: a masked step takes one chunk, n_out = %d", n_out);
+    if (stream_on && !h->rr) return fail(OWW_EINVAL, "oww_step_ingest_mixed: a masked step needs the register-resident kernel families (use_mfma = 3 or 1)");
+    if (n_chunks > OWW_MAX_CALL_CHUNKS) return fail(OWW_EINVAL, "oww_step_ingest_mixed: n_chunks=%d outside [1,%d]", n_chunks, OWW_MAX_CALL_CHUNKS);
+    if (int rc = range_check(h, "oww_step_ingest_mixed")) return rc;       // (before any history moves)
+    if (int rc = oww_ingest_mixed(h, in, in_on_device, row_bytes, n_out, stream_on, stream_on_on_device, nullptr, 1)) return rc;
+    if (stream_on) return oww_step_masked(h, h->d_ing_out, 1, stream_on, stream_on_on_device, scores, scores_on_device);
+    return oww_step(h, h->d_ing_out, 1, n_chunks, scores, scores_on_device);
+    OWW_GUARD_END
+}
+
+int oww_submit_ingest_mixed(oww_ctx* h, const void* in_host, int64_t row_bytes, const uint8_t* stream_on) {
+    OWW_GUARD_BEGIN
+    if (int rc = mixed_ready(h, "oww_submit_ingest_mixed")) return rc;
+    owi::Geometry g;
+    if (int rc = owi::mixed_check("oww_submit_ingest_mixed", h->ing_tab, in_host, row_bytes, OWW_CHUNK, g)) return rc;
+    if (stream_on && !h->rr)
+        return fail(OWW_EINVAL, "oww_submit_ingest_mixed: a masked step needs the register-resident kernel families (use_mfma = 3 or 1; see oww_step_masked)");
+    return submit_impl(h, nullptr, 1, stream_on, in_host, row_bytes, &g);
     OWW_GUARD_END
 }
 

@@ -1701,11 +1701,12 @@ __device__ __forceinline__ float pcm_lo(uint32_t w) { return (float)(int16_t)(w 
 __device__ __forceinline__ float pcm_hi(uint32_t w) { return (float)(int16_t)(w >> 16); }
 __device__ __forceinline__ uint32_t pcm_pack(float lo, float hi) { return ((uint32_t)(int)lo & 0xffffu) | ((uint32_t)(int)hi << 16); }
 
+// One stream's message: `in` is the stream's row, `hist` its history row (a.Hpad samples of it are used), `y` its output row.  Shared
+// by ingest_kernel (one class per launch) and ingest_mixed_kernel (the stream's own class): same statements, same order.
 template <int ENC>
-__global__ __launch_bounds__(RS_NT) void ingest_kernel(IngestParams a) {
+__device__ __forceinline__ void ingest_stream(const IngestParams& a, const void* in, int16_t* hist, int16_t* y) {
     extern __shared__ __attribute__((aligned(16))) float ig_lds[];
-    const int s = blockIdx.x, t = threadIdx.x;
-    if (a.on && !a.on[s]) return;
+    const int t = threadIdx.x;
     const int H = a.n_taps > 0 ? a.n_taps - 1 : 0, Hoff = (H + 3) / 4 * 4, x0 = Hoff - H;
     float* xs = ig_lds;                                               // [xs_len]: x0 spare words | history | message | >= 8 zeros
     int16_t* ys = reinterpret_cast<int16_t*>(ig_lds + a.xs_len);      // [IG_TILE]
@@ -1714,7 +1715,7 @@ __global__ __launch_bounds__(RS_NT) void ingest_kernel(IngestParams a) {
     // ---- 1. history | decoded message, as float
     if (t < x0) xs[t] = 0.f;
     if (a.Hpad) {
-        const uint4* hq = reinterpret_cast<const uint4*>(a.hist + (size_t)s * a.Hpad);
+        const uint4* hq = reinterpret_cast<const uint4*>(hist);
         for (int c = t; c < a.Hpad / 8; c += RS_NT) {
             const uint4 v = hq[c];
             const float f[8] = {pcm_lo(v.x), pcm_hi(v.x), pcm_lo(v.y), pcm_hi(v.y), pcm_lo(v.z), pcm_hi(v.z), pcm_lo(v.w), pcm_hi(v.w)};
@@ -1723,7 +1724,7 @@ __global__ __launch_bounds__(RS_NT) void ingest_kernel(IngestParams a) {
         }
     }
     if (ENC == IG_PCM16) {
-        const int16_t* x = static_cast<const int16_t*>(a.in) + (size_t)s * a.n_in;
+        const int16_t* x = static_cast<const int16_t*>(in);
         if (a.vec_in) {
             for (int c = t; c < a.n_in / 8; c += RS_NT) {
                 const uint4 v = reinterpret_cast<const uint4*>(x)[c];
@@ -1734,7 +1735,7 @@ __global__ __launch_bounds__(RS_NT) void ingest_kernel(IngestParams a) {
             for (int i = t; i < a.n_in; i += RS_NT) xm[i] = (float)x[i];
         }
     } else {
-        const uint8_t* x = static_cast<const uint8_t*>(a.in) + (size_t)s * a.n_in;
+        const uint8_t* x = static_cast<const uint8_t*>(in);
         if (a.vec_in) {
             for (int c = t; c < a.n_in / 16; c += RS_NT) {
                 const uint4 v = reinterpret_cast<const uint4*>(x)[c];
@@ -1751,7 +1752,6 @@ __global__ __launch_bounds__(RS_NT) void ingest_kernel(IngestParams a) {
         for (int i = t; i < a.q * a.ntp; i += RS_NT) ts[i] = a.taps[i];
     __syncthreads();
     // ---- 3. tiles of outputs: every output is resample_kernel's chain; they leave LDS eight at a time
-    int16_t* y = a.out + (size_t)s * a.n_out;
     for (int j0 = 0; j0 < a.n_out; j0 += IG_TILE) {
         const int nt = min(IG_TILE, a.n_out - j0);
         if (a.slide) {
@@ -1812,7 +1812,7 @@ __global__ __launch_bounds__(RS_NT) void ingest_kernel(IngestParams a) {
     }
     // ---- 4. the new history, from LDS (every read of the old one happened in 1.)
     if (a.Hpad) {
-        uint4* hq = reinterpret_cast<uint4*>(a.hist + (size_t)s * a.Hpad);
+        uint4* hq = reinterpret_cast<uint4*>(hist);
         const float* nx = xs + x0 + a.n_in;
         for (int c = t; c < a.Hpad / 8; c += RS_NT) {
             float f[8];
@@ -1821,6 +1821,60 @@ __global__ __launch_bounds__(RS_NT) void ingest_kernel(IngestParams a) {
             hq[c] = make_uint4(pcm_pack(f[0], f[1]), pcm_pack(f[2], f[3]), pcm_pack(f[4], f[5]), pcm_pack(f[6], f[7]));
         }
     }
+}
+
+template <int ENC>
+__global__ __launch_bounds__(RS_NT) void ingest_kernel(IngestParams a) {
+    const int s = blockIdx.x;
+    if (a.on && !a.on[s]) return;
+    const size_t bps = ENC == IG_PCM16 ? 2 : 1;
+    ingest_stream<ENC>(a, static_cast<const char*>(a.in) + (size_t)s * a.n_in * bps, a.hist + (size_t)s * a.Hpad, a.out + (size_t)s * a.n_out);
+}
+
+// oww_ingest_mixed: every stream in its own class (oww_ingest_configure_classes).  Same geometry -- one workgroup owns one stream's
+// message -- and, per stream, ingest_kernel's statements on the class's parameters: the workgroup reads its stream's class id and the
+// class's row of the device table (uniform addresses: the parameters live in scalar registers; nothing is written through them),
+// derives the message geometry ingest_kernel's host side derives, and branches workgroup-uniformly on the encoding.  Rows of `in` are
+// row_bytes apart (a multiple of 16); a class whose message is no multiple of 16 bytes takes the element-wise loads.  History rows
+// are Hpad_max apart and a stream uses the first Hpad of its class: the rest of the row stays zero (configure, assign and reset zero
+// whole rows).  The launch's dynamic LDS is the largest class's need; a class keeps its bank in LDS when it fits that allocation.
+struct IngestClass { int enc, p, q, n_taps, ntp, Hpad, taps_off, slide; };      // taps_off: in floats from IngestMixedParams::taps
+struct IngestMixedParams {
+    const char* in; int16_t* out; int16_t* hist; const float* taps; const uint8_t* on;
+    const uint32_t* cls; const IngestClass* table;
+    long long row_bytes;
+    int n_out, Hpad_max, lds_floats, in_aligned, vec_out;
+};
+__global__ __launch_bounds__(RS_NT, 8) void ingest_mixed_kernel(IngestMixedParams m) {
+    const int s = blockIdx.x;
+    if (m.on && !m.on[s]) return;
+    const IngestClass c = m.table[m.cls[s]];
+    IngestParams a;
+    a.in = nullptr; a.out = nullptr; a.hist = nullptr; a.on = nullptr;
+    a.taps = m.taps + c.taps_off;
+    a.enc = c.enc; a.n_out = m.n_out; a.p = c.p; a.q = c.q; a.n_taps = c.n_taps; a.ntp = c.ntp; a.Hpad = c.Hpad; a.slide = c.slide;
+    a.n_in = (int)((long long)m.n_out * c.p / c.q);
+    const int H = c.n_taps > 0 ? c.n_taps - 1 : 0, Hoff = (H + 3) / 4 * 4;
+    a.xs_len = (Hoff + a.n_in + 8 + 3) / 4 * 4;
+    a.taps_in_lds = c.n_taps && a.xs_len + IG_TILE / 2 + c.q * c.ntp <= m.lds_floats;
+    a.vec_in = m.in_aligned && (a.n_in * (c.enc == IG_PCM16 ? 2 : 1)) % 16 == 0;
+    a.vec_out = m.vec_out;
+    const void* in = m.in + (size_t)s * m.row_bytes;
+    int16_t* hist = m.hist + (size_t)s * m.Hpad_max;
+    int16_t* y = m.out + (size_t)s * m.n_out;
+    if (c.enc == IG_PCM16) ingest_stream<IG_PCM16>(a, in, hist, y);
+    else if (c.enc == IG_ULAW) ingest_stream<IG_ULAW>(a, in, hist, y);
+    else ingest_stream<IG_ALAW>(a, in, hist, y);
+}
+
+// oww_ingest_assign: the listed streams take their new class and start from silence
+__global__ void ingest_assign_kernel(int16_t* hist, int Hpad, uint32_t* cls, const int* ids, const int* new_cls, int n) {
+    const int k = blockIdx.x;
+    if (k >= n) return;
+    const int s = ids[k];
+    if (threadIdx.x == 0) cls[s] = (uint32_t)new_cls[k];
+    uint4* hq = reinterpret_cast<uint4*>(hist + (size_t)s * Hpad);
+    for (int c = threadIdx.x; c < Hpad / 8; c += blockDim.x) hq[c] = make_uint4(0u, 0u, 0u, 0u);
 }
 
 // oww_reset: the listed streams (ids == nullptr: streams [0, n)) start from silence again

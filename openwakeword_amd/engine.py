@@ -383,6 +383,7 @@ class StreamEngine:
             n_taps = taps.shape[1]
         _lib.check(self._lib.oww_ingest_configure(self._h, R.ENCODINGS[encoding], p, q, _ptr(taps), n_taps))
         self._ingest = (encoding, p, q, n_taps)
+        self._ingest_classes = None
 
     def _ingest_args(self, data: np.ndarray, stream_on):
         if getattr(self, "_ingest", None) is None:
@@ -425,6 +426,89 @@ class StreamEngine:
     def ingest_dev_ptr(self) -> int:
         """Device address of the 16 kHz staging buffer the last ingest without `out` wrote (16-byte aligned; 0 before configure_ingest)."""
         return int(self._lib.oww_ingest_dev(self._h) or 0)
+
+    # ---- ingest classes: every stream its own rate and encoding (include/owwhip.h: oww_ingest_configure_classes ... ) ----
+    def configure_ingest_classes(self, formats) -> None:
+        """`formats`: a list of (sample_rate, encoding), at most 16.  Every stream starts in class 0 with a zero history; replaces any
+        earlier ingest configuration.  Banks come from resample.design; 16000 Hz means decode only."""
+        from . import resample as R
+        formats = [(int(r), str(e)) for r, e in formats]
+        arr = (_lib.IngestClass * max(len(formats), 1))()
+        keep = []
+        for i, (rate, enc) in enumerate(formats):
+            p, q, taps, n_taps = R.class_params(rate, enc)
+            keep.append(taps)
+            arr[i] = _lib.IngestClass(R.ENCODINGS[enc], p, q, n_taps, None if taps is None else taps.ctypes.data)
+        _lib.check(self._lib.oww_ingest_configure_classes(self._h, len(formats), arr))
+        self._ingest = None
+        self._ingest_classes = formats
+
+    def _classes(self):
+        if getattr(self, "_ingest_classes", None) is None:
+            raise _lib.OwwError("ingest classes are not configured: call configure_ingest_classes(formats) first")
+        return self._ingest_classes
+
+    def assign_ingest(self, stream_ids, class_ids) -> None:
+        """Streams `stream_ids` take the classes `class_ids` and start from silence (oww_ingest_assign)."""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32).reshape(-1)
+        cls = np.asarray(class_ids).reshape(-1)
+        if cls.size != ids.size or (cls.size and (cls.min() < 0 or cls.max() > 255)):
+            raise ValueError(f"class_ids must be {ids.size} values in [0, 255]")
+        cls = np.ascontiguousarray(cls, dtype=np.uint8)
+        _lib.check(self._lib.oww_ingest_assign(self._h, _ptr(ids), ids.size, _ptr(cls)))
+
+    def ingest_row_bytes(self, n_out: int = CHUNK) -> int:
+        """Row pitch of `rows` for messages of n_out outputs: the widest configured class's message, rounded up to 16 bytes."""
+        from . import resample as R
+        return R.class_row_bytes(self._classes(), n_out)
+
+    def pack_ingest_rows(self, per_stream_arrays, class_ids, n_out: int = CHUNK, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """uint8 [S, row_bytes] from one int16 / uint8 array per stream (None: the stream sits out); lengths and dtypes are checked
+        against each stream's class (resample.pack_ingest_rows with this engine's classes)."""
+        from . import resample as R
+        if len(per_stream_arrays) != self.n_streams:
+            raise ValueError(f"{len(per_stream_arrays)} arrays for n_streams={self.n_streams}")
+        return R.pack_ingest_rows(per_stream_arrays, class_ids, self._classes(), n_out, out)
+
+    def _mixed_args(self, rows, n_out, stream_on):
+        self._classes()
+        if not isinstance(rows, np.ndarray) or rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[0] != self.n_streams \
+                or not rows.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"rows must be a C-contiguous uint8 [n_streams={self.n_streams}, row_bytes] array")
+        on = None
+        if stream_on is not None:
+            on = np.ascontiguousarray(np.asarray(stream_on) != 0, dtype=np.uint8)
+            if on.shape != (self.n_streams,):
+                raise ValueError(f"stream_on must be [n_streams={self.n_streams}], got {on.shape}")
+        return rows, on, int(n_out)
+
+    def ingest_mixed(self, rows: np.ndarray, n_out: int = CHUNK, stream_on: Optional[np.ndarray] = None,
+                     out: Optional[np.ndarray] = None) -> np.ndarray:
+        """One message per stream in the stream's own class, rows uint8 [S, row_bytes] (resample.pack_ingest_rows) -> 16 kHz int16
+        [S, n_out], continuous with each stream's earlier messages.  Masked streams as in ingest()."""
+        rows, on, n_out = self._mixed_args(rows, n_out, stream_on)
+        if out is None:
+            out = np.zeros((self.n_streams, n_out), dtype=np.int16)
+        elif out.dtype != np.int16 or out.shape != (self.n_streams, n_out) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous int16 [{self.n_streams}, {n_out}] array")
+        _lib.check(self._lib.oww_ingest_mixed(self._h, _ptr(rows), 0, rows.shape[1], n_out, _ptr(on), 0, _ptr(out), 0))
+        return out
+
+    def step_ingest_mixed(self, rows: np.ndarray, n_out: int = CHUNK, stream_on: Optional[np.ndarray] = None,
+                          out: Optional[np.ndarray] = None) -> np.ndarray:
+        """ingest_mixed + step without the 16 kHz audio leaving the device (oww_step_ingest_mixed): scores fp32 [S, n_labels]."""
+        rows, on, n_out = self._mixed_args(rows, n_out, stream_on)
+        if out is None:
+            out = np.empty((self.n_streams, self.n_labels), dtype=np.float32)
+        _lib.check(self._lib.oww_step_ingest_mixed(self._h, _ptr(rows), 0, rows.shape[1], n_out, _ptr(on), 0, _ptr(out), 0))
+        return out
+
+    def submit_ingest_mixed(self, rows: np.ndarray, stream_on: Optional[np.ndarray] = None) -> None:
+        """Pipelined step_ingest_mixed of one chunk (oww_submit_ingest_mixed): returns at once, collect() brings the scores.  `rows`
+        must stay alive and unmodified until then (use `pinned_empty(shape, np.uint8)` for an asynchronous upload)."""
+        rows, on, _ = self._mixed_args(rows, CHUNK, stream_on)
+        _lib.check(self._lib.oww_submit_ingest_mixed(self._h, _ptr(rows), rows.shape[1], _ptr(on)))
+        self._inflight.append(rows)
 
     def step_raw(self, pcm: np.ndarray) -> np.ndarray:
         """Like step(), but returns the head outputs before post-processing (model.py:313-317)."""

@@ -867,6 +867,28 @@ class BatchedModel:
             raise ValueError(f"The input audio data (x) must by a Numpy array, instead received an object of type {type(data)}.")
         return self.engine.step_ingest(data, active)[:, self._keep]
 
+    def configure_ingest_classes(self, formats) -> None:
+        """Streams in different formats on one model: `formats` is a list of (sample_rate, encoding), at most 16 (engine.
+        configure_ingest_classes).  Every stream starts in class 0; assign_ingest moves it, predict_ingest_mixed feeds all of them."""
+        self.engine.configure_ingest_classes(formats)
+
+    def assign_ingest(self, stream_ids, class_ids) -> None:
+        """The listed streams take the listed classes and start from silence."""
+        self.engine.assign_ingest(stream_ids, class_ids)
+
+    def predict_ingest_mixed(self, rows: np.ndarray, active=None) -> np.ndarray:
+        """predict_ingest with every stream in its own class: rows uint8 [n_streams, row_bytes] (engine.pack_ingest_rows), one 80 ms
+        message per stream in the stream's own format; `active` as in predict_ingest."""
+        if not isinstance(rows, np.ndarray):
+            raise ValueError(f"The input audio data (x) must by a Numpy array, instead received an object of type {type(rows)}.")
+        return self.engine.step_ingest_mixed(rows, stream_on=active)[:, self._keep]
+
+    def submit_ingest_mixed(self, rows: np.ndarray, active=None) -> None:
+        """Pipelined predict_ingest_mixed, beside submit_batch: the scores come back from collect_batch() in submission order."""
+        if not isinstance(rows, np.ndarray):
+            raise ValueError(f"The input audio data (x) must by a Numpy array, instead received an object of type {type(rows)}.")
+        self.engine.submit_ingest_mixed(rows, active)
+
     def predict_active(self, pcm: np.ndarray, active) -> np.ndarray:
         """predict_batch for the streams flagged in `active` ([n_streams] bool) only; the others do not advance at all and
         repeat their previous scores (the reference's per-client behaviour: no audio, no predict() call)."""

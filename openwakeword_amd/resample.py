@@ -114,3 +114,81 @@ def ingest_numpy(x_decoded: np.ndarray, rate: int, history: np.ndarray = None) -
     idx = (jp // q)[:, None] + np.arange(n_taps)[None, :]                  # [n_out, n_taps] into ext
     y = (ext[..., idx] * taps[jp % q].astype(np.float64)).sum(-1)
     return y, ext[..., ext.shape[-1] - (n_taps - 1):]
+
+
+# ---- ingest classes (include/owwhip.h: oww_ingest_configure_classes / oww_ingest_mixed): every stream its own rate and encoding ------
+def class_params(rate: int, encoding: str):
+    """(p, q, taps or None, n_taps) of the class (rate, encoding): 16000 Hz means decode only (p = q = 1, no filter, no history)."""
+    if encoding not in ENCODINGS:
+        raise ValueError(f"unknown encoding {encoding!r} (one of {sorted(ENCODINGS)})")
+    if int(rate) == 16000:
+        return 1, 1, None, 0
+    p, q, taps = design(int(rate))
+    return p, q, taps, taps.shape[1]
+
+
+def class_n_in(rate: int, n_out: int = 1280) -> int:
+    """Input samples of one message of `n_out` 16 kHz samples at `rate` Hz; ValueError when that is no whole number."""
+    r = Fraction(int(rate), 16000)
+    if (int(n_out) * r.numerator) % r.denominator:
+        raise ValueError(f"{n_out} output samples are no whole number of input samples at {rate} Hz")
+    return int(n_out) * r.numerator // r.denominator
+
+
+def class_row_bytes(classes, n_out: int = 1280) -> int:
+    """Bytes of the widest class's message of n_out outputs, rounded up to 16: the row pitch oww_ingest_mixed wants."""
+    widest = max(class_n_in(rate, n_out) * (2 if enc == "pcm16" else 1) for rate, enc in classes)
+    return (widest + 15) // 16 * 16
+
+
+def pack_ingest_rows(per_stream_arrays, class_ids, classes, n_out: int = 1280, out: np.ndarray = None) -> np.ndarray:
+    """uint8 [S, row_bytes] for oww_ingest_mixed from one array per stream: int16 for a "pcm16" class, uint8 for "ulaw" / "alaw", each
+    exactly class_n_in(rate, n_out) long (ValueError otherwise).  None leaves a stream's row as it is (zeros in a fresh array): for
+    streams that sit out.  `classes` is the list given to configure_ingest_classes, class_ids[s] the class of stream s."""
+    S = len(per_stream_arrays)
+    if len(class_ids) != S:
+        raise ValueError(f"{S} arrays but {len(class_ids)} class ids")
+    rb = class_row_bytes(classes, n_out)
+    if out is None:
+        out = np.zeros((S, rb), np.uint8)
+    elif out.dtype != np.uint8 or out.shape != (S, rb) or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous uint8 [{S}, {rb}] array")
+    for s, (x, c) in enumerate(zip(per_stream_arrays, class_ids)):
+        if not 0 <= int(c) < len(classes):
+            raise ValueError(f"stream {s}: unknown class {c}")
+        if x is None:
+            continue
+        rate, enc = classes[int(c)]
+        want = np.int16 if enc == "pcm16" else np.uint8
+        x = np.asarray(x)
+        n = class_n_in(rate, n_out)
+        if x.dtype != want:
+            raise ValueError(f"stream {s}: class {c} ({rate} Hz {enc}) takes {np.dtype(want).name}, got {x.dtype}")
+        if x.shape != (n,):
+            raise ValueError(f"stream {s}: class {c} ({rate} Hz {enc}) takes {n} samples for {n_out} outputs, got shape {x.shape}")
+        out[s, :x.nbytes] = np.ascontiguousarray(x).view(np.uint8)
+    return out
+
+
+def ingest_mixed_numpy(rows: np.ndarray, class_ids, classes, histories, n_out: int = 1280, stream_on=None) -> np.ndarray:
+    """Host definition of one oww_ingest_mixed message: rows uint8 [S, row_bytes], class_ids[s] the class of stream s, `classes` the
+    list of (rate, encoding), `histories` a list of S arrays (None = silence) that is updated in place.  Per stream this is decode +
+    ingest_numpy + the device's rounding; a 16 kHz class is decode only.  -> int16 [S, n_out]; a stream with stream_on[s] == 0 is not
+    read, keeps its history and has a zero row."""
+    rows = np.asarray(rows)
+    if rows.dtype != np.uint8 or rows.ndim != 2:
+        raise ValueError(f"rows must be uint8 [S, row_bytes], got {rows.dtype} {rows.shape}")
+    out = np.zeros((rows.shape[0], int(n_out)), np.int16)
+    for s in range(rows.shape[0]):
+        if stream_on is not None and not stream_on[s]:
+            continue
+        rate, enc = classes[int(class_ids[s])]
+        n = class_n_in(rate, n_out)
+        raw = rows[s, :n * (2 if enc == "pcm16" else 1)]
+        x = decode(raw.view(np.int16) if enc == "pcm16" else raw, enc)
+        if int(rate) == 16000:
+            out[s] = x
+            continue
+        y, histories[s] = ingest_numpy(x, int(rate), histories[s])
+        out[s] = np.clip(np.rint(y), -32768, 32767).astype(np.int16)
+    return out

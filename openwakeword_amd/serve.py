@@ -26,6 +26,17 @@ share groups: participation per group becomes all-or-nothing instead of "every g
 Sample-rate conversion follows the example (per message, stateless: `resampy.resample(data, sample_rate, 16000)`,
 streaming_server.py:57-58) with scipy's polyphase resampler; resampy is not a dependency here.
 
+`ingest="device"` (`--ingest device`) takes the conversion off the host altogether: the server configures one ingest class per
+accepted format on the model's handle (`BatchedModel.configure_ingest_classes`: every rate of RATES as PCM16, plus G.711 mu-law and
+A-law at 8 kHz, announced as "8000 ulaw" / "8000 alaw"), a connection's slot is assigned its class with its first audio, the handler
+queues the RAW bytes, and each complete 80 ms frame of the client's own format goes into the connection's row of a page-locked
+uint8 [S][row_bytes] buffer that `oww_submit_ingest_mixed` decodes, converts CONTINUOUSLY per stream and scores.  No message edge is
+audible any more (per-message conversion: 30-40 dB SNR against one-piece conversion), and no resampler runs in this
+process.  The price is the upload: a row is as wide as the widest class's frame -- 15,360 bytes with the full table (96 kHz PCM16),
+six times the 2,560 bytes of a 16 kHz chunk -- whatever the row's own format.  A deployment that only expects telephony should
+pass a smaller table (`rates=[(8000, "ulaw"), (8000, "alaw"), 8000]`: rows of 1,280 bytes); the largest class also sets the ingest
+launch's LDS allocation and so its occupancy.
+
     python -m openwakeword_amd.serve --streams 4096 --models alexa hey_jarvis --weights synthetic --port 9000
 """
 from __future__ import annotations
@@ -185,7 +196,7 @@ def cohort_distance(a, b) -> float:
 
 class _Client:
     __slots__ = ("cid", "slot", "ws", "rate", "pending", "n_pending", "n_steps", "closed", "in_flight", "outbox", "sender", "arrivals",
-                 "n_arrived", "reaped")
+                 "n_arrived", "reaped", "frame", "enc", "cls")
 
     def __init__(self, slot: Optional[int], ws, cid: int = -1):
         self.cid, self.slot, self.ws, self.rate = cid, slot, ws, 16000
@@ -199,19 +210,22 @@ class _Client:
         self.sender: Optional[asyncio.Task] = None                  # the one task that drains `outbox`
         self.arrivals: "collections.deque" = collections.deque()   # when each complete, not yet scored chunk became available (metrics)
         self.n_arrived = 0                                          # samples received so far
+        # what `pending` counts and one step takes: 1280 samples at 16 kHz; with ingest="device" the BYTES of one 80 ms frame of the
+        # connection's own format (set with its class at the first audio)
+        self.frame, self.enc, self.cls = CHUNK, "pcm16", 0
 
     def push(self, x: np.ndarray, now: float = 0.0) -> None:
         if x.size:
             self.pending.append(x)
             self.n_pending += x.size
-            done = (self.n_arrived + x.size) // CHUNK - self.n_arrived // CHUNK      # chunks this message completes
+            done = (self.n_arrived + x.size) // self.frame - self.n_arrived // self.frame      # chunks this message completes
             self.n_arrived += x.size
             for _ in range(done):
                 self.arrivals.append(now)
 
     def pop_chunk(self, out: np.ndarray) -> None:
-        """Move the oldest 1280 samples into `out`."""
-        need, o = CHUNK, 0
+        """Move the oldest 1280 samples (ingest="device": the oldest frame's bytes) into `out`."""
+        need, o = self.frame, 0
         while need:
             head = self.pending[0]
             take = min(need, head.size)
@@ -222,7 +236,7 @@ class _Client:
                 self.pending[0] = head[take:]
             o += take
             need -= take
-        self.n_pending -= CHUNK
+        self.n_pending -= self.frame
 
 
 class _GpuWorker(threading.Thread):
@@ -283,7 +297,13 @@ class FanInServer:
 
     N_BUF = 3
 
-    def __init__(self, model, threshold: float = 0.5, window_s: float = 0.01, on_scores=None):
+    def __init__(self, model, threshold: float = 0.5, window_s: float = 0.01, on_scores=None, ingest: str = "host", rates=None):
+        """`ingest`: "host" converts every message on the host (to_16k, per message, like the example); "device" configures ingest
+        classes on the model and uploads the clients' own formats (module docstring).  `rates` (device mode): the class table, entries
+        a rate (PCM16) or (rate, "pcm16" | "ulaw" | "alaw"), at most 16; default every rate of RATES plus G.711 at 8 kHz."""
+        if ingest not in ("host", "device"):
+            raise ValueError(f'ingest must be "host" or "device", got {ingest!r}')
+        self.ingest = ingest
         self.model = model
         self.threshold = float(threshold)
         self.window_s = float(window_s)
@@ -297,7 +317,22 @@ class FanInServer:
         self._have_chunk: Optional[asyncio.Event] = None
         self._pump_task: Optional[asyncio.Task] = None
         self._gpu: Optional[_GpuWorker] = None
-        self._pcm = [model.engine.pinned_empty((S, CHUNK)) for _ in range(self.N_BUF)]
+        if ingest == "device":
+            from . import resample
+            table = list(RATES) + [(8000, "ulaw"), (8000, "alaw")] if rates is None else list(rates)
+            self.classes = [(int(r), "pcm16") if np.isscalar(r) else (int(r[0]), str(r[1])) for r in table]
+            for rate, enc in self.classes:
+                if rate not in RATES or enc not in resample.ENCODINGS:
+                    raise ValueError(f"unsupported ingest class {(rate, enc)}")
+            self._class_of = {fmt: i for i, fmt in enumerate(self.classes)}
+            self._frame_bytes = [resample.class_n_in(rate, CHUNK) * (2 if enc == "pcm16" else 1) for rate, enc in self.classes]
+            self.row_bytes = resample.class_row_bytes(self.classes, CHUNK)
+            model.configure_ingest_classes(self.classes)
+            self._pcm = [model.engine.pinned_empty((S, self.row_bytes), np.uint8) for _ in range(self.N_BUF)]
+            self._submit = model.engine.submit_ingest_mixed
+        else:
+            self._pcm = [model.engine.pinned_empty((S, CHUNK)) for _ in range(self.N_BUF)]
+            self._submit = model.engine.submit
         for b in self._pcm:
             b[:] = 0
         self._on = [np.zeros(S, dtype=np.uint8) for _ in range(self.N_BUF)]        # rows of the buffer that carry a chunk
@@ -350,7 +385,7 @@ class FanInServer:
     def _stage(self, c: "_Client") -> None:
         """Move the connection's oldest complete chunk into its row of the buffer being filled -- if that row is free; else the
         connection waits in `_more` for the next buffer (one chunk per stream and step, in order)."""
-        if c.n_pending < CHUNK or c.slot is None:
+        if c.n_pending < c.frame or c.slot is None:
             return
         f = self._fill
         if self._on[f][c.slot]:
@@ -360,7 +395,7 @@ class FanInServer:
         self._on[f][c.slot] = 1
         self._t_arr[f][c.slot] = c.arrivals.popleft() if c.arrivals else 0.0
         self._n_fill += 1
-        if c.n_pending >= CHUNK:
+        if c.n_pending >= c.frame:
             self._more.add(c)
         self._have_chunk.set()
 
@@ -381,22 +416,29 @@ class FanInServer:
             await ws.send_str(json.dumps({"loaded_models": list(self.model.labels)}))
             async for msg in ws:
                 if msg.type == WSMsgType.TEXT:
+                    text, enc = msg.data, "pcm16"
+                    if self.ingest == "device":             # "<rate>" as in the example, or "<rate> ulaw" / "<rate> alaw"
+                        word = text.split()
+                        if len(word) == 2 and word[1] in ("ulaw", "alaw"):
+                            text, enc = word[0], word[1]
                     try:
-                        rate = int(msg.data)
+                        rate = int(text)
                     except ValueError:
+                        rate = 0
+                    if self.ingest == "device" and (rate, enc) not in self._class_of:
                         rate = 0
                     if rate not in RATES:                   # (the example trusts the client here; see RATES)
                         # the accepted rates go out as a message: a close reason is limited to 123 bytes (RFC 6455, 5.5)
                         await ws.send_str(json.dumps({"error": "unsupported sample rate", "accepted_rates": list(RATES)}))
                         await ws.close(code=1003, message=b"unsupported sample rate")
                         break
-                    c.rate = rate
+                    c.rate, c.enc = rate, enc
                 elif msg.type == WSMsgType.BINARY:
                     if c.closed:
                         # dropped by the server (send timeout, unread activations): its slot is being -- or has been -- returned and may
                         # already belong to another connection; audio that still arrives is not staged, the handler ends
                         break
-                    n = len(msg.data) // 2
+                    n = len(msg.data) if c.enc != "pcm16" else len(msg.data) // 2      # samples
                     if c.slot is None and n:
                         # the first audio: place the connection next to the ones whose chunks fall due in the same rounds.  A slot
                         # handed to a new caller starts from Model()'s initial state, VAD history included; the job queue orders
@@ -405,6 +447,14 @@ class FanInServer:
                         self.clients[c.slot] = c
                         self._k[c.slot] = 0
                         await self._gpu.call(self.model.reset, [c.slot], reset_vad=bool(self.model.engine.has_vad))
+                        if self.ingest == "device":         # ... and the slot's class behind it: a zero history in the caller's own format
+                            c.cls = self._class_of[(c.rate, c.enc)]
+                            c.frame = self._frame_bytes[c.cls]
+                            await self._gpu.call(self.model.assign_ingest, [c.slot], [c.cls])
+                    if self.ingest == "device":             # the raw bytes (whole samples): nothing is converted on the host
+                        c.push(np.frombuffer(msg.data, dtype=np.uint8, count=n * (2 if c.enc == "pcm16" else 1)), loop.time())
+                        self._stage(c)
+                        continue
                     x = np.frombuffer(msg.data, dtype="<i2", count=n)
                     if c.rate != 16000:                     # filtering runs on the default executor, not on the event loop
                         x = await loop.run_in_executor(None, to_16k, x, c.rate)
@@ -427,7 +477,7 @@ class FanInServer:
             if c.reaped:                                    # one-shot: a second pass must not release a slot that has a new owner
                 self._closing.discard(c)
                 continue
-            if c.slot is not None and (c.n_pending >= CHUNK or self._inflight[c.slot] or self._on[self._fill][c.slot]):
+            if c.slot is not None and (c.n_pending >= c.frame or self._inflight[c.slot] or self._on[self._fill][c.slot]):
                 continue
             self._closing.discard(c)
             self._more.discard(c)
@@ -487,7 +537,7 @@ class FanInServer:
         whether steps are long enough to be worth pipelining."""
         import time
         t0 = time.perf_counter()
-        self.model.engine.submit(pcm, on)
+        self._submit(pcm, on)
         scores = self.model.engine.collect()
         return scores, time.perf_counter() - t0
 
@@ -600,7 +650,7 @@ class FanInServer:
                         else:
                             flying.append(g)
                             t_sub.append(t0)
-                            await self._gpu.call(self.model.engine.submit, self._pcm[g], self._on[g])
+                            await self._gpu.call(self._submit, self._pcm[g], self._on[g])
                             if self.keep_metrics:
                                 self.step_log[self.n_steps - 1][2] = loop.time()
                     # collect: otherwise keep two steps in flight, so that the next upload overlaps this step's kernels
@@ -697,6 +747,9 @@ def main(argv=None) -> None:
                          "event loop and its own handle on the GPU: one Python event loop carries about two thousand real-time clients "
                          "(tools/serve_load.py), the GPU a thousand times that -- the edge scales over host cores, not over GPUs")
     ap.add_argument("--reuse-port", action="store_true", help="(set for the worker processes of --workers)")
+    ap.add_argument("--ingest", choices=("host", "device"), default="host",
+                    help='"device": clients\' own rates and G.711 ("8000 ulaw" / "8000 alaw") are decoded and converted continuously on the GPU '
+                         "(ingest classes); no resampler runs on the host")
     a = ap.parse_args(argv)
     if a.workers > 1:
         import sys
@@ -704,10 +757,11 @@ def main(argv=None) -> None:
                "--host", a.host, "--port", str(a.port), "--device", str(a.device), "--workers", "1", "--reuse-port"]
         cmd += ["--weights", a.weights] if a.weights else []
         cmd += ["--use-mfma", str(a.use_mfma)] if a.use_mfma is not None else []
+        cmd += ["--ingest", a.ingest]
         raise SystemExit(_supervise(cmd, a.workers))
     from .model import BatchedModel
     model = BatchedModel(a.streams, a.models, weights=a.weights, device=a.device, use_mfma=a.use_mfma)
-    web.run_app(FanInServer(model, threshold=a.threshold).app(), host=a.host, port=a.port, reuse_port=True if a.reuse_port else None)
+    web.run_app(FanInServer(model, threshold=a.threshold, ingest=a.ingest).app(), host=a.host, port=a.port, reuse_port=True if a.reuse_port else None)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,13 @@ Reports, as one JSON line (and to --out):
   step_ingest_ms   oww_step_ingest on the resident codes, against
   step_pcm16k_ms   oww_step on resident 16 kHz PCM, same build, same process
   host_8k_ms       predict_batch(pcm_8k, sample_rate=8000) from host memory (host clock around a blocking call): the stateless host-fed path
-The three device variants alternate inside every round (warm-up first); every figure is the median over rounds with its min..max."""
+  mixed_one_class_ms   the ingest-classes launch (oww_ingest_mixed) on a second handle whose table holds the one class (8000, "ulaw"):
+                   the same codes, the same row pitch, to be read against ingest_ms -- what the class lookup costs
+  mixed_thirds_ms  oww_ingest_mixed on a third handle with the table [(8000, "ulaw"), (16000, "pcm16"), (48000, "pcm16")] and a third of
+                   the streams in each (stream s in class s % 3), rows 7,680 bytes apart: workgroups of 640, 1,280 and 3,840 input
+                   samples in one launch, and the 48 kHz class's LDS allocation for all of them -- what the imbalance costs
+All device variants alternate inside every round (warm-up first); every figure is the median over rounds with its min..max.
+--no-mixed leaves the two extra handles out."""
 import argparse
 import ctypes as C
 import json
@@ -36,6 +42,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--host-iters", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--no-mixed", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ingest_bench needs the GPU: there is nothing to time without one")
@@ -74,6 +81,26 @@ def main():
         return a.elapsed_time(b) / args.iters
 
     variants = {"ingest_ms": ingest, "step_ingest_ms": step_ingest, "step_pcm16k_ms": step_pcm}
+    thirds = [(8000, "ulaw"), (16000, "pcm16"), (48000, "pcm16")]
+    if not args.no_mixed:
+        bm_one = BatchedModel(S, list(names), weights=wts, hip_stream=st.cuda_stream)
+        bm_one.configure_ingest_classes([(rate, "ulaw")])
+        bm_mix = BatchedModel(S, list(names), weights=wts, hip_stream=st.cuda_stream)
+        bm_mix.configure_ingest_classes(thirds)
+        bm_mix.assign_ingest(np.arange(S), np.arange(S) % 3)
+        rb = bm_mix.engine.ingest_row_bytes()
+        rows = torch.randint(0, 256, (S, rb), device="cuda", dtype=torch.uint8, generator=gen)
+        torch.cuda.synchronize()
+        rp = C.c_void_p(rows.data_ptr())
+        assert bm_one.engine.ingest_row_bytes() == n_in
+
+        def mixed_one():
+            _lib.check(lib.oww_ingest_mixed(bm_one.engine._h, cp, 1, n_in, 1280, None, 0, None, 1))
+
+        def mixed_thirds():
+            _lib.check(lib.oww_ingest_mixed(bm_mix.engine._h, rp, 1, rb, 1280, None, 0, None, 1))
+        variants["mixed_one_class_ms"] = mixed_one
+        variants["mixed_thirds_ms"] = mixed_thirds
     for fn in variants.values():
         for _ in range(3):
             fn()
@@ -114,6 +141,26 @@ def main():
            "ingest_frac_of_hbm_peak": round(bytes_launch / t / 1e9 / PEAK_HBM_GBS, 4),
            "ingest_fma_per_launch": S * 1280 * ((int(taps.shape[1]) + 3) // 4 * 4),
            "max_abs_diff_vs_numpy_first_streams": max_diff}
+    if not args.no_mixed:
+        # the one-class mixed launch computes what the single-format launch computes: first streams, one more launch each from silence
+        bm_one.configure_ingest_classes([(rate, "ulaw")])
+        out2 = torch.empty(S, 1280, device="cuda", dtype=torch.int16)
+        torch.cuda.synchronize()
+        _lib.check(lib.oww_ingest_mixed(bm_one.engine._h, cp, 1, n_in, 1280, None, 0, C.c_void_p(out2.data_ptr()), 1))
+        bm_one.engine.sync()
+        hp = [(R.class_params(r, e)[3] - 1 + 7) // 8 * 8 if r != 16000 else 0 for r, e in thirds]
+        per_class = [R.class_n_in(r) * (2 if e == "pcm16" else 1) + 1280 * 2 + 2 * h * 2 for (r, e), h in zip(thirds, hp)]
+        n_cls = [len(range(c, S, 3)) for c in range(3)]
+        bytes_mix = sum(n * b for n, b in zip(n_cls, per_class))
+        t_mix = statistics.median(ms["mixed_thirds_ms"]) * 1e-3
+        res.update({"mixed_one_class_ms": stat(ms["mixed_one_class_ms"]), "mixed_thirds_ms": stat(ms["mixed_thirds_ms"]),
+                    "mixed_one_class_over_ingest": round(statistics.median(ms["mixed_one_class_ms"]) / statistics.median(ms["ingest_ms"]), 4),
+                    "mixed_one_class_equals_ingest_bit_for_bit": bool(torch.equal(out, out2)),
+                    "mixed_thirds_classes": [list(c) for c in thirds], "mixed_thirds_row_bytes": int(rb),
+                    "mixed_thirds_bytes_per_launch": bytes_mix, "mixed_thirds_GB_s": round(bytes_mix / t_mix / 1e9, 1),
+                    "mixed_thirds_fma_per_launch": sum(n * 1280 * ((R.class_params(r, e)[3] + 3) // 4 * 4) for n, (r, e) in zip(n_cls, thirds))})
+        bm_one.close()
+        bm_mix.close()
     line = json.dumps(res)
     print(line)
     if args.out:
