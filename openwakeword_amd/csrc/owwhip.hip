@@ -253,22 +253,21 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     int* d_range = nullptr;          // the same word as the kernels address it (a view: the device alias of h_range)
     DevBuf<char> d_rs;               // oww_resample scratch: [taps | in | out] as needed, in bytes
     std::vector<float> rs_taps;                    // the padded filter bank of the last oww_resample call (upload source)
-    // stateful stream ingest (oww_ingest_configure / oww_ingest / oww_step_ingest; owk::ingest_kernel): nothing before the first configure
-    bool ing_ready = false;
-    int ing_enc = 0, ing_p = 1, ing_q = 1, ing_n_taps = 0, ing_ntp = 0, ing_Hpad = 0;
-    std::vector<float> ing_taps;                   // the padded bank [q][ntp] (upload source, fingerprint)
-    DevBuf<float> d_ing_taps;
-    DevBuf<int16_t> d_ing_hist;                    // [S][Hpad]: each stream's last n_taps - 1 decoded samples, oldest first, zero padded
-    DevBuf<int16_t> d_ing_out;                     // 16 kHz staging [S][n_out] (oww_ingest_dev), grown on demand
-    DevBuf<char> d_ing_in;                         // a host message on its way in, in bytes
-    DevBuf<uint8_t> d_ing_on;                      // [S] a host mask on its way in
-    // ingest classes (oww_ingest_configure_classes / oww_ingest_mixed; owk::ingest_mixed_kernel).  ing_ready is set as well, ing_Hpad is
-    // the table's largest and d_ing_hist / d_ing_taps hold [S][Hpad_max] and every bank: reset and the state records read those alone.
-    bool ing_mixed = false;
-    owi::Table ing_tab;                            // host copy of the table and banks (upload source, fingerprint, checks)
-    DevBuf<IngestClass> d_ing_table;
-    DevBuf<uint32_t> d_ing_cls;                    // [S] each stream's class: a word per stream, so that the state records carry it
-    DevBuf<int> d_ing_newcls;                      // the class list of oww_ingest_assign on its way in
+    // stateful stream ingest: nothing before the first configure.  The single form (oww_ingest_configure; owk::ingest_kernel) is a table
+    // of one row served by its own kernel, the class form (oww_ingest_configure_classes; owk::ingest_mixed_kernel) sets `mixed` and
+    // has the table and the class ids on the device as well.
+    struct Ingest {
+        bool ready = false, mixed = false;
+        owi::Table tab;                            // host copy of the rows and padded banks (upload source, fingerprint, checks)
+        DevBuf<float> d_taps;                      // every bank (none: single form, decode only)
+        DevBuf<int16_t> d_hist;                    // [S][tab.Hpad_max]: each stream's last n_taps - 1 decoded samples, oldest first, zero padded
+        DevBuf<int16_t> d_out;                     // 16 kHz staging [S][n_out] (oww_ingest_dev), grown on demand; survives reconfiguration
+        DevBuf<char> d_in;                         // a host message on its way in, in bytes
+        DevBuf<uint8_t> d_on;                      // [S] a host mask on its way in
+        DevBuf<IngestClass> d_table;               // class form: the rows
+        DevBuf<uint32_t> d_cls;                    // class form: [S] each stream's class, a word per stream, so that the state records carry it
+        DevBuf<int> d_newcls;                      // the class list of oww_ingest_assign on its way in
+    } ing;
     DevBuf<uint8_t> d_on;            // oww_step_masked: [Spad] participation mask of the step being launched (pad streams 0)
     // masked step with few participants: the device copy of the group lists (StepArgs::gl) and its two page-locked staging buffers,
     // used in turn (build_active_lists)
@@ -1610,8 +1609,9 @@ int state_layout(oww_ctx* h) {
     flat(h->d_vadring, 8, 8); flat(h->d_nvad, 1, 1);
     if (h->vad) flat(h->d_vadlast, 1, 1);
     if (K) { flat(h->d_bank_raw, K, K); flat(h->d_bank_scores, K, K); flat(h->d_bank_npred, K, K); flat(h->d_bank_ring, K * OWW_SCORE_RING, K * OWW_SCORE_RING); }
-    if (h->ing_ready && h->ing_Hpad) flat(h->d_ing_hist, (size_t)h->ing_Hpad / 2, (size_t)h->ing_Hpad / 2);   // oww_ingest history (int16 pairs)
-    if (h->ing_ready && h->ing_mixed) flat(h->d_ing_cls, 1, 1);            // ... and the stream's class: one word in a 16-byte piece of its own
+    const oww_ctx::Ingest& ing = h->ing;
+    if (ing.ready && ing.tab.Hpad_max) flat(ing.d_hist, (size_t)ing.tab.Hpad_max / 2, (size_t)ing.tab.Hpad_max / 2);   // oww_ingest history (int16 pairs)
+    if (ing.ready && ing.mixed) flat(ing.d_cls, 1, 1);                     // ... and the stream's class: one word in a 16-byte piece of its own
     h->st_flat_quads = off / 4;
     auto group = [&](float* live, int spg, int ppr, bool inter, uint32_t block_words) -> int {
         const int R = ppr >= 4 ? 1 : 4 / ppr;
@@ -1642,17 +1642,7 @@ int state_layout(oww_ctx* h) {
         fp = fp_mix(fp, hh.blob.data(), hh.blob.size() * sizeof(float));
     }
     fp = fp_mix(fp, h->vad_blob.data(), h->vad_blob.size() * sizeof(float));
-    if (h->ing_ready && h->ing_mixed) {          // ingest classes: the whole table and every bank
-        const int32_t tag[2] = {-1, (int32_t)h->ing_tab.dev.size()};       // (no single configuration has encoding -1)
-        fp = fp_mix(fp, tag, sizeof tag);
-        fp = fp_mix(fp, h->ing_tab.dev.data(), h->ing_tab.dev.size() * sizeof(owi::ClassDev));
-        fp = fp_mix(fp, h->ing_tab.banks.data(), h->ing_tab.banks.size() * sizeof(float));
-    } else if (h->ing_ready) {                   // a handle that never configured ingest hashes what it always hashed
-        const int32_t ig[4] = {h->ing_enc, h->ing_p, h->ing_q, h->ing_n_taps};
-        fp = fp_mix(fp, ig, sizeof ig);
-        fp = fp_mix(fp, h->ing_taps.data(), h->ing_taps.size() * sizeof(float));
-    }
-    h->st_fp = fp;
+    h->st_fp = owi::fingerprint(fp, ing.ready, ing.mixed, ing.tab);
     if (!h->d_st_flat) HIPCHK(herr(h->d_st_flat.alloc(h->st_flat.size())));
     HIPCHK(copy_sync(h->d_st_flat, h->st_flat.data(), h->st_flat.size() * sizeof(ows::FlatSection), hipMemcpyHostToDevice));
     h->st_ready = true;
@@ -1981,8 +1971,8 @@ int oww_reset(oww_ctx* h, const int32_t* stream_ids, int32_t n, const float* ini
         if (int rc = upload_ids(h, stream_ids, n)) return rc;
         if (int rc = do_reset(h, h->d_ids, n, d_init)) return rc;
     }
-    if (h->ing_ready && h->ing_Hpad) {           // stateful ingest: a new caller starts from silence
-        hipLaunchKernelGGL(ingest_hist_reset_kernel, dim3(stream_ids ? n : h->S), dim3(64), 0, h->stream, h->d_ing_hist, h->ing_Hpad,
+    if (h->ing.ready && h->ing.tab.Hpad_max) {   // stateful ingest: a new caller starts from silence
+        hipLaunchKernelGGL(ingest_hist_reset_kernel, dim3(stream_ids ? n : h->S), dim3(64), 0, h->stream, h->ing.d_hist, h->ing.tab.Hpad_max,
                            stream_ids ? h->d_ids : nullptr, stream_ids ? n : h->S);
         HIPCHK(hipGetLastError());
     }
@@ -2113,26 +2103,51 @@ static int ensure_ingest(oww_ctx* h) {
     return 0;
 }
 
-static int launch_ingest_mixed(oww_ctx* h, const void* d_in, long long row_bytes, int n_out, const uint8_t* d_on, int16_t* out, const owi::Geometry& g);
-// mix != nullptr (oww_submit_ingest_mixed): one chunk per stream in the streams' own formats, [S][row_bytes], checked by the caller
-static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const uint8_t* stream_on, const void* mix = nullptr,
-                       long long row_bytes = 0, const owi::Geometry* geo = nullptr);
-
-int oww_submit(oww_ctx* h, const int16_t* pcm, int32_t n_chunks) { OWW_GUARD_BEGIN return submit_impl(h, pcm, n_chunks, nullptr); OWW_GUARD_END }
-
-int oww_submit_masked(oww_ctx* h, const int16_t* pcm, const uint8_t* stream_on) {
-    OWW_GUARD_BEGIN
-    if (!stream_on) return fail(OWW_EINVAL, "oww_submit_masked: stream_on is null");
-    if (h && h->committed && !h->rr)
-        return fail(OWW_EINVAL, "oww_submit_masked: needs the register-resident kernel families (use_mfma = 3 or 1; see oww_step_masked)");
-    return submit_impl(h, pcm, 1, stream_on);
-    OWW_GUARD_END
+// The ingest launch on the handle's stream, the one place where the two forms differ: d_in [S][row_bytes] and d_on (or null) are
+// device pointers, `out` is a device pointer, `g` is what single_check / mixed_check gave for this message.  A single-format handle
+// has a kernel of its own (the class kernel serves one class slower).
+static_assert(owi::kTile == IG_TILE && sizeof(owi::ClassDev) == sizeof(IngestClass), "owwhip_ingest.h restates the kernel's tile and table row");
+static int launch_ingest(oww_ctx* h, const void* d_in, long long row_bytes, int n_out, const uint8_t* d_on, int16_t* out, const owi::Geometry& g) {
+    const oww_ctx::Ingest& ing = h->ing;
+    const dim3 grid(h->S), block(RS_NT);
+    if (ing.mixed) {
+        IngestMixedParams m{};
+        m.in = static_cast<const char*>(d_in); m.out = out; m.hist = ing.d_hist; m.taps = ing.d_taps; m.on = d_on;
+        m.cls = ing.d_cls; m.table = ing.d_table;
+        m.row_bytes = row_bytes; m.n_out = n_out; m.Hpad_max = ing.tab.Hpad_max; m.lds_floats = (int)(g.lds / sizeof(float));
+        m.in_aligned = !(reinterpret_cast<uintptr_t>(d_in) & 15);
+        m.vec_out = !(reinterpret_cast<uintptr_t>(out) & 15) && n_out % 8 == 0;
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ingest_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL(ingest_mixed_kernel, grid, block, g.lds, h->stream, m);
+    } else {
+        const owi::ClassDev& k = ing.tab.dev[0];
+        IngestParams a{};
+        a.in = d_in; a.on = d_on; a.out = out; a.hist = ing.d_hist; a.taps = ing.d_taps;
+        a.enc = k.enc; a.n_in = (int)((long long)n_out * k.p / k.q); a.n_out = n_out; a.p = k.p; a.q = k.q; a.n_taps = k.n_taps; a.ntp = k.ntp;
+        a.Hpad = k.Hpad; a.xs_len = g.xs_len; a.taps_in_lds = g.taps_in_lds;
+        a.vec_in = !(reinterpret_cast<uintptr_t>(d_in) & 15) && row_bytes % 16 == 0;
+        a.vec_out = !(reinterpret_cast<uintptr_t>(out) & 15) && n_out % 8 == 0;
+        a.slide = k.slide;
+#define OWW_IG_GO(ENC)                                                                                                                        \
+    do {                                                                                                                                      \
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ingest_kernel<ENC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+        hipLaunchKernelGGL(ingest_kernel<ENC>, grid, block, g.lds, h->stream, a);                                                            \
+    } while (0)
+        if (k.enc == OWW_ENC_PCM16) OWW_IG_GO(IG_PCM16); else if (k.enc == OWW_ENC_ULAW) OWW_IG_GO(IG_ULAW); else OWW_IG_GO(IG_ALAW);
+#undef OWW_IG_GO
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
-static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const uint8_t* stream_on, const void* mix, long long row_bytes,
-                       const owi::Geometry* geo) {
+// what a submit uploads: 16 kHz PCM [S][n_chunks * 1280], or (mix != nullptr; oww_submit_ingest_mixed) one chunk per stream in the
+// streams' own formats, [S][row_bytes], checked by the caller, who passes mixed_check's geometry
+struct SubmitSource { const int16_t* pcm; int32_t n_chunks; const void* mix; long long row_bytes; owi::Geometry geo; };
+static int submit_impl(oww_ctx* h, const SubmitSource& src, const uint8_t* stream_on) {
+    const void* mix = src.mix;
+    const int32_t n_chunks = src.n_chunks;
     if (!h || !h->committed) return fail(OWW_ESTATE, "oww_submit: handle not committed");
-    if (!pcm && !mix) return fail(OWW_EINVAL, "oww_submit: pcm is null");
+    if (!src.pcm && !mix) return fail(OWW_EINVAL, "oww_submit: pcm is null");
     if (n_chunks < 1 || n_chunks > h->kmax) return fail(OWW_EINVAL, "oww_submit: n_chunks=%d outside [1,%d]", n_chunks, h->kmax);
     if (int rc = range_check(h, "oww_submit")) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -2142,13 +2157,13 @@ static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const u
     if (sl.busy) return fail(OWW_ESTATE, "oww_submit: two steps already in flight, call oww_collect first");
     const size_t n_pcm = (size_t)h->S * OWW_CHUNK * n_chunks;
     if (mix) {
-        const size_t nb = (size_t)h->S * (size_t)row_bytes;
+        const size_t nb = (size_t)h->S * (size_t)src.row_bytes;
         if (nb > sl.d_mix.capacity()) {                // first use, or wider rows than before (the slot was collected: nothing reads the old block)
             if (sl.d_mix.reserve(nb)) return fail(OWW_ENOMEM, "oww_submit_ingest_mixed: out of device memory for %zu bytes", nb);
         }
         HIPCHK(copy_async(sl.d_mix, mix, nb, hipMemcpyHostToDevice, h->up_stream));
     } else {
-        HIPCHK(copy_async(sl.d_pcm, pcm, n_pcm * sizeof(int16_t), hipMemcpyHostToDevice, h->up_stream));
+        HIPCHK(copy_async(sl.d_pcm, src.pcm, n_pcm * sizeof(int16_t), hipMemcpyHostToDevice, h->up_stream));
     }
     HIPCHK(hipEventRecord(sl.up, h->up_stream));
     HIPCHK(hipStreamWaitEvent(h->stream, sl.up, 0));
@@ -2163,9 +2178,9 @@ static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const u
         if (n_act < -1) return n_act + 100;
     }
     if (mix && n_act != 0)                             // (both slots' ingest launches and steps are ordered on the compute stream: one staging buffer)
-        if (int rc = launch_ingest_mixed(h, sl.d_mix, row_bytes, OWW_CHUNK, stream_on ? (const uint8_t*)h->d_on : nullptr, h->d_ing_out, *geo)) return rc;
+        if (int rc = launch_ingest(h, sl.d_mix, src.row_bytes, OWW_CHUNK, stream_on ? (const uint8_t*)h->d_on : nullptr, h->ing.d_out, src.geo)) return rc;
     if (n_act != 0)
-        if (int rc = launch_step(h, a, mix ? (const int16_t*)h->d_ing_out : (const int16_t*)sl.d_pcm, n_chunks)) return rc;
+        if (int rc = launch_step(h, a, mix ? (const int16_t*)h->ing.d_out : (const int16_t*)sl.d_pcm, n_chunks)) return rc;
     const oww_ctx::EventBuf& eb = h->evt_slot[h->n_submit & 1];
     if (events_on(h)) { if (int rc = launch_events(h, a, eb, n_act != 0)) return rc; h->evt_cur = nullptr; }
     const size_t nb = (size_t)h->S * h->NL * sizeof(float);
@@ -2181,6 +2196,17 @@ static int submit_impl(oww_ctx* h, const int16_t* pcm, int32_t n_chunks, const u
     sl.busy = true;
     ++h->n_submit;
     return OWW_OK;
+}
+
+int oww_submit(oww_ctx* h, const int16_t* pcm, int32_t n_chunks) { OWW_GUARD_BEGIN return submit_impl(h, SubmitSource{pcm, n_chunks, nullptr, 0, {}}, nullptr); OWW_GUARD_END }
+
+int oww_submit_masked(oww_ctx* h, const int16_t* pcm, const uint8_t* stream_on) {
+    OWW_GUARD_BEGIN
+    if (!stream_on) return fail(OWW_EINVAL, "oww_submit_masked: stream_on is null");
+    if (h && h->committed && !h->rr)
+        return fail(OWW_EINVAL, "oww_submit_masked: needs the register-resident kernel families (use_mfma = 3 or 1; see oww_step_masked)");
+    return submit_impl(h, SubmitSource{pcm, 1, nullptr, 0, {}}, stream_on);
+    OWW_GUARD_END
 }
 
 int oww_collect(oww_ctx* h, float* scores) {
@@ -2389,8 +2415,8 @@ int oww_resample(oww_ctx* h, const int16_t* in, int in_on_device, int32_t n_in, 
     char* base = h->d_rs;
     // (stream-ordered upload from a buffer that lives in the handle: an earlier oww_resample may still be reading the old bank)
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->rs_taps.assign((size_t)q * ntp, 0.f);
-    for (int r = 0; r < q; ++r) memcpy(&h->rs_taps[(size_t)r * ntp], taps + (size_t)r * n_taps, n_taps * sizeof(float));
+    h->rs_taps.clear();
+    owi::bank_pad(taps, q, n_taps, h->rs_taps);
     HIPCHK(copy_async(base, h->rs_taps.data(), h->rs_taps.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     ResampleParams a{};
     a.taps = (const float*)base; a.n_in = n_in; a.n_out = n_out; a.p = p; a.q = q; a.n_taps = n_taps; a.ntp = ntp; a.S = h->S;
@@ -2411,261 +2437,124 @@ int oww_resample(oww_ctx* h, const int16_t* in, int in_on_device, int32_t n_in, 
     OWW_GUARD_END
 }
 
-// ---- stateful stream ingest (header: oww_ingest_configure / oww_ingest / oww_step_ingest; kernel: ingest_kernel in owwhip_kernels.h) ----
+// ---- stateful stream ingest, both forms (header: oww_ingest_configure / oww_ingest / oww_step_ingest and oww_ingest_configure_classes /
+//      oww_ingest_assign / oww_ingest_mixed / oww_step_ingest_mixed / oww_submit_ingest_mixed).  Every check and all arithmetic is in
+//      owwhip_ingest.h; here are the buffers and one of each step: ingest_install behind the two configure entries, ingest_message
+//      behind the two ingest entries, step_behind_ingest behind the two step entries.  The launch (launch_ingest, above submit_impl)
+//      is where the forms part: ingest_kernel<ENC> for a single-format handle, ingest_mixed_kernel for classes (owwhip_kernels.h) ----
+
+// the handle takes `tab`: the single form's one row, or (mixed) the class table, which goes to the device with a class id per stream
+static int ingest_install(oww_ctx* h, const char* fn, owi::Table&& tab, bool mixed) {
+    oww_ctx::Ingest& ing = h->ing;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));               // an earlier ingest may still read the old banks and histories
+    auto drop = [&] { ing.d_taps.reset(); ing.d_hist.reset(); ing.d_table.reset(); ing.d_cls.reset(); };
+    drop();
+    ing.ready = false; ing.mixed = false; ing.tab = owi::Table();
+    h->d_st_flat.reset(); h->st_ready = false;               // the record layout gains, loses or resizes its ingest sections: rebuilt on demand
+    const int Hpad = tab.Hpad_max;
+    // (a single form that only decodes has no bank; the table's one placeholder float is there for the class kernel's pointer)
+    const size_t n_bank = mixed ? tab.banks.size() : (size_t)tab.dev[0].q * tab.dev[0].ntp, n_hist = (size_t)h->S * Hpad;
+    if ((n_bank && ing.d_taps.alloc(n_bank)) || (n_hist && ing.d_hist.alloc(n_hist)) ||
+        (mixed && (ing.d_table.alloc(tab.dev.size()) || ing.d_cls.alloc(h->S)))) {
+        drop();
+        return fail(OWW_ENOMEM, "%s: out of device memory for %d streams x %d history samples and %zu bank floats", fn, h->S, Hpad, n_bank);
+    }
+    if (n_bank) HIPCHK(copy_sync(ing.d_taps, tab.banks.data(), n_bank * sizeof(float), hipMemcpyHostToDevice));
+    if (mixed) {
+        HIPCHK(copy_sync(ing.d_table, tab.dev.data(), tab.dev.size() * sizeof(owi::ClassDev), hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(ing.d_cls, 0, (size_t)h->S * sizeof(uint32_t), h->stream));
+    }
+    if (n_hist) HIPCHK(hipMemsetAsync(ing.d_hist, 0, n_hist * sizeof(int16_t), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (!ing.d_out) {
+        if (ing.d_out.alloc((size_t)h->S * OWW_CHUNK)) return fail(OWW_ENOMEM, "%s: out of device memory", fn);
+        HIPCHK(hipMemset(ing.d_out, 0, ing.d_out.capacity() * sizeof(int16_t)));
+    }
+    ing.tab = std::move(tab);
+    ing.mixed = mixed; ing.ready = true;
+    return OWW_OK;
+}
+
 int oww_ingest_configure(oww_ctx* h, int32_t encoding, int32_t p, int32_t q, const float* taps, int32_t n_taps) {
     OWW_GUARD_BEGIN
     if (!h || !h->committed) return fail(OWW_ESTATE, "oww_ingest_configure: handle not committed");
-    if (encoding != OWW_ENC_PCM16 && encoding != OWW_ENC_ULAW && encoding != OWW_ENC_ALAW)
-        return fail(OWW_EINVAL, "oww_ingest_configure: unknown encoding %d (OWW_ENC_PCM16 = 0, OWW_ENC_ULAW = 1, OWW_ENC_ALAW = 2)", encoding);
-    if (n_taps == 0) {
-        if (p != 1 || q != 1) return fail(OWW_EINVAL, "oww_ingest_configure: n_taps = 0 (decode only) needs p = q = 1, got p=%d q=%d", p, q);
-    } else {
-        if (p < 1 || q < 1 || n_taps < 2 || (n_taps & 1) || n_taps > 4096 || q > 65536)
-            return fail(OWW_EINVAL, "oww_ingest_configure: bad argument (p=%d q=%d n_taps=%d)", p, q, n_taps);
-        if (!taps) return fail(OWW_EINVAL, "oww_ingest_configure: null argument: taps");
-    }
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipStreamSynchronize(h->stream));               // an earlier oww_ingest may still read the old bank and history
-    h->d_ing_taps.reset(); h->d_ing_hist.reset();
-    h->d_ing_table.reset(); h->d_ing_cls.reset(); h->ing_mixed = false; h->ing_tab = owi::Table();   // (replaces a class table as well)
-    h->ing_ready = false;
-    h->d_st_flat.reset(); h->st_ready = false;               // the record layout gains, loses or resizes its history section: rebuilt on demand
-    const int ntp = (n_taps + 3) / 4 * 4, Hpad = n_taps ? (n_taps - 1 + 7) / 8 * 8 : 0;
-    h->ing_taps.assign((size_t)q * ntp, 0.f);
-    for (int r = 0; r < q && n_taps; ++r) memcpy(&h->ing_taps[(size_t)r * ntp], taps + (size_t)r * n_taps, n_taps * sizeof(float));
-    if (n_taps) {
-        if (h->d_ing_taps.alloc(h->ing_taps.size()) || h->d_ing_hist.alloc((size_t)h->S * Hpad)) {
-            h->d_ing_taps.reset();
-            return fail(OWW_ENOMEM, "oww_ingest_configure: out of device memory for %d streams x %d history samples", h->S, Hpad);
-        }
-        HIPCHK(copy_sync(h->d_ing_taps, h->ing_taps.data(), h->ing_taps.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMemsetAsync(h->d_ing_hist, 0, (size_t)h->S * Hpad * sizeof(int16_t), h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    if (!h->d_ing_out) {
-        if (h->d_ing_out.alloc((size_t)h->S * OWW_CHUNK)) return fail(OWW_ENOMEM, "oww_ingest_configure: out of device memory");
-        HIPCHK(hipMemset(h->d_ing_out, 0, h->d_ing_out.capacity() * sizeof(int16_t)));
-    }
-    h->ing_enc = encoding; h->ing_p = p; h->ing_q = q; h->ing_n_taps = n_taps; h->ing_ntp = ntp; h->ing_Hpad = Hpad;
-    h->ing_ready = true;
-    return OWW_OK;
+    const oww_ingest_class one{encoding, p, q, n_taps, taps};
+    owi::Table tab;
+    if (int rc = owi::table_build("oww_ingest_configure", 1, &one, tab, false)) return rc;
+    return ingest_install(h, "oww_ingest_configure", std::move(tab), false);
     OWW_GUARD_END
 }
-
-const int16_t* oww_ingest_dev(const oww_ctx* h) { return h ? h->d_ing_out : nullptr; }
-
-// argument checks shared by oww_ingest and oww_step_ingest: nothing has moved when they refuse
-static int ingest_check(const oww_ctx* h, const char* fn, const void* in, int32_t n_in, long long* n_out) {
-    if (!h || !h->committed) return fail(OWW_ESTATE, "%s: handle not committed", fn);
-    if (!h->ing_ready) return fail(OWW_ESTATE, "%s: ingest is not configured (oww_ingest_configure)", fn);
-    if (h->ing_mixed) return fail(OWW_ESTATE, "%s: the handle is configured with ingest classes: use the _mixed entry", fn);
-    if (!in) return fail(OWW_EINVAL, "%s: null argument: in", fn);
-    if (n_in < 1) return fail(OWW_EINVAL, "%s: bad argument (n_in=%d)", fn, n_in);
-    if (((long long)n_in * h->ing_q) % h->ing_p)
-        return fail(OWW_EINVAL, "%s: a message must hold a whole number of output samples: n_in * q = %d * %d is no multiple of p = %d", fn, n_in, h->ing_q, h->ing_p);
-    *n_out = (long long)n_in * h->ing_q / h->ing_p;
-    if (*n_out > (1 << 24)) return fail(OWW_EINVAL, "%s: n_out = %lld is beyond 2^24 samples per message", fn, *n_out);
-    return 0;
-}
-
-int oww_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const uint8_t* stream_on, int stream_on_on_device,
-               int16_t* out, int out_on_device) {
-    OWW_GUARD_BEGIN
-    long long n_out_ll = 0;
-    if (int rc = ingest_check(h, "oww_ingest", in, n_in, &n_out_ll)) return rc;
-    const int n_out = (int)n_out_ll, H = h->ing_n_taps ? h->ing_n_taps - 1 : 0, Hoff = (H + 3) / 4 * 4;
-    const int xs_len = (Hoff + n_in + 8 + 3) / 4 * 4;        // (+ 8: what the zero-padded taps, and the sliding form's look-ahead quad, read on)
-    const size_t lds_x = (size_t)xs_len * sizeof(float), lds_y = (size_t)IG_TILE * sizeof(int16_t), lds_t = (size_t)h->ing_q * h->ing_ntp * sizeof(float);
-    if (lds_x > 96 * 1024)
-        return fail(OWW_EINVAL, "oww_ingest: a message of n_in = %d samples behind a history of %d needs %zu bytes of LDS, the one-workgroup-per-stream "
-                                "kernel stages at most %d: send shorter messages", n_in, H, lds_x, 96 * 1024);
-    const int taps_in_lds = h->ing_n_taps && lds_x + lds_y + lds_t <= 150 * 1024;
-    const size_t lds = lds_x + lds_y + (taps_in_lds ? lds_t : 0);
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const size_t bps = h->ing_enc == OWW_ENC_PCM16 ? 2 : 1, in_bytes = (size_t)h->S * n_in * bps;
-    IngestParams a{};
-    a.in = in;
-    if (!in_on_device) {
-        if (grow(h, h->d_ing_in, in_bytes) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest: out of device memory for %zu bytes", in_bytes);
-        HIPCHK(copy_async(h->d_ing_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
-        a.in = h->d_ing_in;
-    }
-    a.on = stream_on;
-    if (stream_on && !stream_on_on_device) {
-        if (!h->d_ing_on) HIPCHK(herr(h->d_ing_on.alloc(h->S)));
-        HIPCHK(copy_async(h->d_ing_on, stream_on, h->S, hipMemcpyHostToDevice, h->stream));
-        a.on = h->d_ing_on;
-    }
-    const bool to_staging = !out || !out_on_device;
-    if (to_staging) {
-        const size_t need = (size_t)h->S * n_out;
-        if (need > h->d_ing_out.capacity()) {                // (a grown staging buffer starts zeroed, like the first)
-            if (grow(h, h->d_ing_out, need) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest: out of device memory for %zu bytes", need * sizeof(int16_t));
-            HIPCHK(hipMemset(h->d_ing_out, 0, need * sizeof(int16_t)));
-        }
-    }
-    a.out = to_staging ? h->d_ing_out : out;
-    a.hist = h->d_ing_hist; a.taps = h->d_ing_taps;
-    a.enc = h->ing_enc; a.n_in = n_in; a.n_out = n_out; a.p = h->ing_p; a.q = h->ing_q; a.n_taps = h->ing_n_taps; a.ntp = h->ing_ntp;
-    a.Hpad = h->ing_Hpad; a.xs_len = xs_len; a.taps_in_lds = taps_in_lds;
-    a.vec_in = !(reinterpret_cast<uintptr_t>(a.in) & 15) && ((size_t)n_in * bps) % 16 == 0;
-    a.vec_out = !(reinterpret_cast<uintptr_t>(a.out) & 15) && n_out % 8 == 0;
-    a.slide = h->ing_n_taps && h->ing_p == 1 && (h->ing_q == 1 || h->ing_q == 2 || h->ing_q == 4 || h->ing_q == 8);
-    const dim3 grid(h->S), block(RS_NT);
-#define OWW_IG_GO(ENC)                                                                                                                        \
-    do {                                                                                                                                      \
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ingest_kernel<ENC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        hipLaunchKernelGGL(ingest_kernel<ENC>, grid, block, lds, h->stream, a);                                                              \
-    } while (0)
-    if (h->ing_enc == OWW_ENC_PCM16) OWW_IG_GO(IG_PCM16); else if (h->ing_enc == OWW_ENC_ULAW) OWW_IG_GO(IG_ULAW); else OWW_IG_GO(IG_ALAW);
-#undef OWW_IG_GO
-    HIPCHK(hipGetLastError());
-    if (out && !out_on_device) {
-        const size_t row = (size_t)n_out * sizeof(int16_t);
-        if (!stream_on) {
-            HIPCHK(copy_async(out, h->d_ing_out, (size_t)h->S * row, hipMemcpyDeviceToHost, h->stream));
-        } else {                                             // only the rows of the streams that took part reach the caller's buffer, run by run
-            std::vector<uint8_t> on(h->S);
-            if (stream_on_on_device) HIPCHK(hipMemcpy(on.data(), stream_on, h->S, hipMemcpyDeviceToHost)); else memcpy(on.data(), stream_on, h->S);
-            for (int s = 0; s < h->S;) {
-                if (!on[s]) { ++s; continue; }
-                int e = s;
-                while (e < h->S && on[e]) ++e;
-                HIPCHK(copy_async(out + (size_t)s * n_out, h->d_ing_out + (size_t)s * n_out, (size_t)(e - s) * row, hipMemcpyDeviceToHost, h->stream));
-                s = e;
-            }
-        }
-    }
-    if (!in_on_device || (stream_on && !stream_on_on_device) || (out && !out_on_device)) HIPCHK(hipStreamSynchronize(h->stream));   // host buffers are the caller's again
-    return OWW_OK;
-    OWW_GUARD_END
-}
-
-int oww_step_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const uint8_t* stream_on, int stream_on_on_device,
-                    float* scores, int scores_on_device) {
-    OWW_GUARD_BEGIN
-    long long n_out = 0;
-    if (int rc = ingest_check(h, "oww_step_ingest", in, n_in, &n_out)) return rc;
-    if (n_out < OWW_CHUNK || n_out % OWW_CHUNK)
-        return fail(OWW_EINVAL, "oww_step_ingest: n_out = n_in * q / p = %lld must be a positive multiple of %d", n_out, OWW_CHUNK);
-    const int n_chunks = (int)(n_out / OWW_CHUNK);
-    if (stream_on && n_chunks != 1) return fail(OWW_EINVAL, "oww_step_ingest: a masked step takes one chunk, n_out = %lld", n_out);
-    if (stream_on && !h->rr) return fail(OWW_EINVAL, "oww_step_ingest: a masked step needs the register-resident kernel families (use_mfma = 3 or 1)");
-    if (n_chunks > OWW_MAX_CALL_CHUNKS) return fail(OWW_EINVAL, "oww_step_ingest: n_chunks=%d outside [1,%d]", n_chunks, OWW_MAX_CALL_CHUNKS);
-    if (int rc = range_check(h, "oww_step_ingest")) return rc;             // (before any history moves)
-    if (int rc = oww_ingest(h, in, in_on_device, n_in, stream_on, stream_on_on_device, nullptr, 1)) return rc;
-    if (stream_on) return oww_step_masked(h, h->d_ing_out, 1, stream_on, stream_on_on_device, scores, scores_on_device);
-    return oww_step(h, h->d_ing_out, 1, n_chunks, scores, scores_on_device);
-    OWW_GUARD_END
-}
-
-// ---- ingest classes (header: oww_ingest_configure_classes / oww_ingest_assign / oww_ingest_mixed / oww_step_ingest_mixed /
-//      oww_submit_ingest_mixed; host checks and table: owwhip_ingest.h; kernel: ingest_mixed_kernel in owwhip_kernels.h) ----
-static_assert(owi::kTile == IG_TILE && sizeof(owi::ClassDev) == sizeof(IngestClass), "owwhip_ingest.h restates the kernel's tile and table row");
 
 int oww_ingest_configure_classes(oww_ctx* h, int32_t n_classes, const oww_ingest_class* classes) {
     OWW_GUARD_BEGIN
     if (!h || !h->committed) return fail(OWW_ESTATE, "oww_ingest_configure_classes: handle not committed");
     owi::Table tab;
     if (int rc = owi::table_build("oww_ingest_configure_classes", n_classes, classes, tab)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipStreamSynchronize(h->stream));               // an earlier ingest may still read the old banks and histories
-    h->d_ing_taps.reset(); h->d_ing_hist.reset(); h->d_ing_table.reset(); h->d_ing_cls.reset();
-    h->ing_ready = false; h->ing_mixed = false;
-    h->d_st_flat.reset(); h->st_ready = false;               // the record layout changes: rebuilt on demand
-    const int Hpad = tab.Hpad_max;
-    if (h->d_ing_taps.alloc(tab.banks.size()) || h->d_ing_table.alloc(tab.dev.size()) || h->d_ing_cls.alloc(h->S) ||
-        (Hpad && h->d_ing_hist.alloc((size_t)h->S * Hpad))) {
-        h->d_ing_taps.reset(); h->d_ing_hist.reset(); h->d_ing_table.reset(); h->d_ing_cls.reset();
-        return fail(OWW_ENOMEM, "oww_ingest_configure_classes: out of device memory for %d streams x %d history samples and %zu bank floats", h->S, Hpad, tab.banks.size());
-    }
-    HIPCHK(copy_sync(h->d_ing_taps, tab.banks.data(), tab.banks.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(copy_sync(h->d_ing_table, tab.dev.data(), tab.dev.size() * sizeof(owi::ClassDev), hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(h->d_ing_cls, 0, (size_t)h->S * sizeof(uint32_t), h->stream));
-    if (Hpad) HIPCHK(hipMemsetAsync(h->d_ing_hist, 0, (size_t)h->S * Hpad * sizeof(int16_t), h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (!h->d_ing_out) {
-        if (h->d_ing_out.alloc((size_t)h->S * OWW_CHUNK)) return fail(OWW_ENOMEM, "oww_ingest_configure_classes: out of device memory");
-        HIPCHK(hipMemset(h->d_ing_out, 0, h->d_ing_out.capacity() * sizeof(int16_t)));
-    }
-    h->ing_tab = std::move(tab);
-    h->ing_enc = 0; h->ing_p = 1; h->ing_q = 1; h->ing_n_taps = 0; h->ing_ntp = 0; h->ing_Hpad = Hpad;
-    h->ing_mixed = true; h->ing_ready = true;
-    return OWW_OK;
+    return ingest_install(h, "oww_ingest_configure_classes", std::move(tab), true);
     OWW_GUARD_END
 }
 
-static int mixed_ready(const oww_ctx* h, const char* fn) {
+const int16_t* oww_ingest_dev(const oww_ctx* h) { return h ? h->ing.d_out : nullptr; }
+
+// the handle is configured, and in the form the entry `fn` serves
+static int ingest_ready(const oww_ctx* h, const char* fn, bool mixed) {
     if (!h || !h->committed) return fail(OWW_ESTATE, "%s: handle not committed", fn);
-    if (!h->ing_ready) return fail(OWW_ESTATE, "%s: ingest is not configured (oww_ingest_configure_classes)", fn);
-    if (!h->ing_mixed) return fail(OWW_ESTATE, "%s: the handle is configured with oww_ingest_configure, not with ingest classes", fn);
+    if (!h->ing.ready) return fail(OWW_ESTATE, "%s: ingest is not configured (%s)", fn, mixed ? "oww_ingest_configure_classes" : "oww_ingest_configure");
+    if (mixed && !h->ing.mixed) return fail(OWW_ESTATE, "%s: the handle is configured with oww_ingest_configure, not with ingest classes", fn);
+    if (!mixed && h->ing.mixed) return fail(OWW_ESTATE, "%s: the handle is configured with ingest classes: use the _mixed entry", fn);
     return 0;
 }
 
 int oww_ingest_assign(oww_ctx* h, const int32_t* stream_ids, int32_t n, const uint8_t* class_ids) {
     OWW_GUARD_BEGIN
-    if (int rc = mixed_ready(h, "oww_ingest_assign")) return rc;
-    if (int rc = owi::assign_check("oww_ingest_assign", h->ing_tab, h->S, stream_ids, n, class_ids)) return rc;
+    if (int rc = ingest_ready(h, "oww_ingest_assign", true)) return rc;
+    if (int rc = owi::assign_check("oww_ingest_assign", h->ing.tab, h->S, stream_ids, n, class_ids)) return rc;
     if (n < 1) return OWW_OK;
     HIPCHK(hipSetDevice(h->cfg.device));
     std::vector<int> cls(class_ids, class_ids + n);
     if (int rc = upload_ids(h, stream_ids, n)) return rc;
-    HIPCHK(grow(h, h->d_ing_newcls, (size_t)n));
-    HIPCHK(copy_async(h->d_ing_newcls, cls.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(ingest_assign_kernel, dim3(n), dim3(64), 0, h->stream, h->d_ing_hist, h->ing_Hpad, h->d_ing_cls, h->d_ids, h->d_ing_newcls, n);
+    HIPCHK(grow(h, h->ing.d_newcls, (size_t)n));
+    HIPCHK(copy_async(h->ing.d_newcls, cls.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(ingest_assign_kernel, dim3(n), dim3(64), 0, h->stream, h->ing.d_hist, h->ing.tab.Hpad_max, h->ing.d_cls, h->d_ids, h->ing.d_newcls, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));     // host lists may be reused by the caller
     return OWW_OK;
     OWW_GUARD_END
 }
 
-// the launch, on the handle's stream: d_in [S][row_bytes] and d_on (or null) are device pointers, `out` is a device pointer
-static int launch_ingest_mixed(oww_ctx* h, const void* d_in, long long row_bytes, int n_out, const uint8_t* d_on, int16_t* out, const owi::Geometry& g) {
-    IngestMixedParams m{};
-    m.in = static_cast<const char*>(d_in); m.out = out; m.hist = h->d_ing_hist; m.taps = h->d_ing_taps; m.on = d_on;
-    m.cls = h->d_ing_cls; m.table = h->d_ing_table;
-    m.row_bytes = row_bytes; m.n_out = n_out; m.Hpad_max = h->ing_Hpad; m.lds_floats = (int)(g.lds / sizeof(float));
-    m.in_aligned = !(reinterpret_cast<uintptr_t>(d_in) & 15);
-    m.vec_out = !(reinterpret_cast<uintptr_t>(out) & 15) && n_out % 8 == 0;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ingest_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(ingest_mixed_kernel, dim3(h->S), dim3(RS_NT), g.lds, h->stream, m);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int oww_ingest_mixed(oww_ctx* h, const void* in, int in_on_device, int64_t row_bytes, int32_t n_out, const uint8_t* stream_on,
-                     int stream_on_on_device, int16_t* out, int out_on_device) {
-    OWW_GUARD_BEGIN
-    if (int rc = mixed_ready(h, "oww_ingest_mixed")) return rc;
-    owi::Geometry g;
-    if (int rc = owi::mixed_check("oww_ingest_mixed", h->ing_tab, in, row_bytes, n_out, g)) return rc;
+// A checked message goes through ingest: `in` is [S][row_bytes] (single form: a row is the message itself), `g` its geometry.  Host
+// input and a host mask are staged on the device, a host or absent `out` is served through the 16 kHz staging buffer.
+static int ingest_message(oww_ctx* h, const char* fn, const void* in, int in_on_device, long long row_bytes, int n_out, const uint8_t* stream_on,
+                          int stream_on_on_device, int16_t* out, int out_on_device, const owi::Geometry& g) {
+    oww_ctx::Ingest& ing = h->ing;
     HIPCHK(hipSetDevice(h->cfg.device));
     const size_t in_bytes = (size_t)h->S * (size_t)row_bytes;
     const void* d_in = in;
     if (!in_on_device) {
-        if (grow(h, h->d_ing_in, in_bytes) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest_mixed: out of device memory for %zu bytes", in_bytes);
-        HIPCHK(copy_async(h->d_ing_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
-        d_in = h->d_ing_in;
+        if (grow(h, ing.d_in, in_bytes) != hipSuccess) return fail(OWW_ENOMEM, "%s: out of device memory for %zu bytes", fn, in_bytes);
+        HIPCHK(copy_async(ing.d_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
+        d_in = ing.d_in;
     }
     const uint8_t* d_on = stream_on;
     if (stream_on && !stream_on_on_device) {
-        if (!h->d_ing_on) HIPCHK(herr(h->d_ing_on.alloc(h->S)));
-        HIPCHK(copy_async(h->d_ing_on, stream_on, h->S, hipMemcpyHostToDevice, h->stream));
-        d_on = h->d_ing_on;
+        if (!ing.d_on) HIPCHK(herr(ing.d_on.alloc(h->S)));
+        HIPCHK(copy_async(ing.d_on, stream_on, h->S, hipMemcpyHostToDevice, h->stream));
+        d_on = ing.d_on;
     }
     const bool to_staging = !out || !out_on_device;
     if (to_staging) {
         const size_t need = (size_t)h->S * n_out;
-        if (need > h->d_ing_out.capacity()) {                // (a grown staging buffer starts zeroed, like the first)
-            if (grow(h, h->d_ing_out, need) != hipSuccess) return fail(OWW_ENOMEM, "oww_ingest_mixed: out of device memory for %zu bytes", need * sizeof(int16_t));
-            HIPCHK(hipMemset(h->d_ing_out, 0, need * sizeof(int16_t)));
+        if (need > ing.d_out.capacity()) {                   // (a grown staging buffer starts zeroed, like the first)
+            if (grow(h, ing.d_out, need) != hipSuccess) return fail(OWW_ENOMEM, "%s: out of device memory for %zu bytes", fn, need * sizeof(int16_t));
+            HIPCHK(hipMemset(ing.d_out, 0, need * sizeof(int16_t)));
         }
     }
-    if (int rc = launch_ingest_mixed(h, d_in, row_bytes, n_out, d_on, to_staging ? (int16_t*)h->d_ing_out : out, g)) return rc;
+    if (int rc = launch_ingest(h, d_in, row_bytes, n_out, d_on, to_staging ? (int16_t*)ing.d_out : out, g)) return rc;
     if (out && !out_on_device) {
         const size_t row = (size_t)n_out * sizeof(int16_t);
         if (!stream_on) {
-            HIPCHK(copy_async(out, h->d_ing_out, (size_t)h->S * row, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(copy_async(out, ing.d_out, (size_t)h->S * row, hipMemcpyDeviceToHost, h->stream));
         } else {                                             // only the rows of the streams that took part reach the caller's buffer, run by run
             std::vector<uint8_t> on(h->S);
             if (stream_on_on_device) HIPCHK(hipMemcpy(on.data(), stream_on, h->S, hipMemcpyDeviceToHost)); else memcpy(on.data(), stream_on, h->S);
@@ -2673,43 +2562,81 @@ int oww_ingest_mixed(oww_ctx* h, const void* in, int in_on_device, int64_t row_b
                 if (!on[s]) { ++s; continue; }
                 int e = s;
                 while (e < h->S && on[e]) ++e;
-                HIPCHK(copy_async(out + (size_t)s * n_out, h->d_ing_out + (size_t)s * n_out, (size_t)(e - s) * row, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(copy_async(out + (size_t)s * n_out, ing.d_out + (size_t)s * n_out, (size_t)(e - s) * row, hipMemcpyDeviceToHost, h->stream));
                 s = e;
             }
         }
     }
     if (!in_on_device || (stream_on && !stream_on_on_device) || (out && !out_on_device)) HIPCHK(hipStreamSynchronize(h->stream));   // host buffers are the caller's again
     return OWW_OK;
+}
+
+// A checked message goes through ingest and the step behind it, which reads the staging buffer.  `n_out_is` words the single form's
+// message ("n_in * q / p = "); every refusal comes before any history moves.
+static int step_behind_ingest(oww_ctx* h, const char* fn, const char* n_out_is, const void* in, int in_on_device, long long row_bytes, long long n_out,
+                              const uint8_t* stream_on, int stream_on_on_device, float* scores, int scores_on_device, const owi::Geometry& g) {
+    if (n_out < OWW_CHUNK || n_out % OWW_CHUNK) return fail(OWW_EINVAL, "%s: n_out = %s%lld must be a positive multiple of %d", fn, n_out_is, n_out, OWW_CHUNK);
+    const int n_chunks = (int)(n_out / OWW_CHUNK);
+    if (stream_on && n_chunks != 1) return fail(OWW_EINVAL, "%s: a masked step takes one chunk, n_out = %lld", fn, n_out);
+    if (stream_on && !h->rr) return fail(OWW_EINVAL, "%s: a masked step needs the register-resident kernel families (use_mfma = 3 or 1)", fn);
+    if (n_chunks > OWW_MAX_CALL_CHUNKS) return fail(OWW_EINVAL, "%s: n_chunks=%d outside [1,%d]", fn, n_chunks, OWW_MAX_CALL_CHUNKS);
+    if (int rc = range_check(h, fn)) return rc;
+    if (int rc = ingest_message(h, fn, in, in_on_device, row_bytes, (int)n_out, stream_on, stream_on_on_device, nullptr, 1, g)) return rc;
+    if (stream_on) return oww_step_masked(h, h->ing.d_out, 1, stream_on, stream_on_on_device, scores, scores_on_device);
+    return oww_step(h, h->ing.d_out, 1, n_chunks, scores, scores_on_device);
+}
+
+int oww_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const uint8_t* stream_on, int stream_on_on_device,
+               int16_t* out, int out_on_device) {
+    OWW_GUARD_BEGIN
+    if (int rc = ingest_ready(h, "oww_ingest", false)) return rc;
+    long long n_out = 0;
+    owi::Geometry g;
+    if (int rc = owi::single_check("oww_ingest", h->ing.tab, in, n_in, n_out, g)) return rc;
+    return ingest_message(h, "oww_ingest", in, in_on_device, g.min_row_bytes, (int)n_out, stream_on, stream_on_on_device, out, out_on_device, g);
+    OWW_GUARD_END
+}
+
+int oww_step_ingest(oww_ctx* h, const void* in, int in_on_device, int32_t n_in, const uint8_t* stream_on, int stream_on_on_device,
+                    float* scores, int scores_on_device) {
+    OWW_GUARD_BEGIN
+    if (int rc = ingest_ready(h, "oww_step_ingest", false)) return rc;
+    long long n_out = 0;
+    owi::Geometry g;
+    if (int rc = owi::single_check("oww_step_ingest", h->ing.tab, in, n_in, n_out, g)) return rc;
+    return step_behind_ingest(h, "oww_step_ingest", "n_in * q / p = ", in, in_on_device, g.min_row_bytes, n_out, stream_on, stream_on_on_device, scores,
+                              scores_on_device, g);
+    OWW_GUARD_END
+}
+
+int oww_ingest_mixed(oww_ctx* h, const void* in, int in_on_device, int64_t row_bytes, int32_t n_out, const uint8_t* stream_on,
+                     int stream_on_on_device, int16_t* out, int out_on_device) {
+    OWW_GUARD_BEGIN
+    if (int rc = ingest_ready(h, "oww_ingest_mixed", true)) return rc;
+    owi::Geometry g;
+    if (int rc = owi::mixed_check("oww_ingest_mixed", h->ing.tab, in, row_bytes, n_out, g)) return rc;
+    return ingest_message(h, "oww_ingest_mixed", in, in_on_device, row_bytes, n_out, stream_on, stream_on_on_device, out, out_on_device, g);
     OWW_GUARD_END
 }
 
 int oww_step_ingest_mixed(oww_ctx* h, const void* in, int in_on_device, int64_t row_bytes, int32_t n_out, const uint8_t* stream_on,
                           int stream_on_on_device, float* scores, int scores_on_device) {
     OWW_GUARD_BEGIN
-    if (int rc = mixed_ready(h, "oww_step_ingest_mixed")) return rc;
+    if (int rc = ingest_ready(h, "oww_step_ingest_mixed", true)) return rc;
     owi::Geometry g;
-    if (int rc = owi::mixed_check("oww_step_ingest_mixed", h->ing_tab, in, row_bytes, n_out, g)) return rc;
-    if (n_out < OWW_CHUNK || n_out % OWW_CHUNK)
-        return fail(OWW_EINVAL, "oww_step_ingest_mixed: n_out = %d must be a positive multiple of %d", n_out, OWW_CHUNK);
-    const int n_chunks = n_out / OWW_CHUNK;
-    if (stream_on && n_chunks != 1) return fail(OWW_EINVAL, "oww_step_ingest_mixed: a masked step takes one chunk, n_out = %d", n_out);
-    if (stream_on && !h->rr) return fail(OWW_EINVAL, "oww_step_ingest_mixed: a masked step needs the register-resident kernel families (use_mfma = 3 or 1)");
-    if (n_chunks > OWW_MAX_CALL_CHUNKS) return fail(OWW_EINVAL, "oww_step_ingest_mixed: n_chunks=%d outside [1,%d]", n_chunks, OWW_MAX_CALL_CHUNKS);
-    if (int rc = range_check(h, "oww_step_ingest_mixed")) return rc;       // (before any history moves)
-    if (int rc = oww_ingest_mixed(h, in, in_on_device, row_bytes, n_out, stream_on, stream_on_on_device, nullptr, 1)) return rc;
-    if (stream_on) return oww_step_masked(h, h->d_ing_out, 1, stream_on, stream_on_on_device, scores, scores_on_device);
-    return oww_step(h, h->d_ing_out, 1, n_chunks, scores, scores_on_device);
+    if (int rc = owi::mixed_check("oww_step_ingest_mixed", h->ing.tab, in, row_bytes, n_out, g)) return rc;
+    return step_behind_ingest(h, "oww_step_ingest_mixed", "", in, in_on_device, row_bytes, n_out, stream_on, stream_on_on_device, scores, scores_on_device, g);
     OWW_GUARD_END
 }
 
 int oww_submit_ingest_mixed(oww_ctx* h, const void* in_host, int64_t row_bytes, const uint8_t* stream_on) {
     OWW_GUARD_BEGIN
-    if (int rc = mixed_ready(h, "oww_submit_ingest_mixed")) return rc;
+    if (int rc = ingest_ready(h, "oww_submit_ingest_mixed", true)) return rc;
     owi::Geometry g;
-    if (int rc = owi::mixed_check("oww_submit_ingest_mixed", h->ing_tab, in_host, row_bytes, OWW_CHUNK, g)) return rc;
+    if (int rc = owi::mixed_check("oww_submit_ingest_mixed", h->ing.tab, in_host, row_bytes, OWW_CHUNK, g)) return rc;
     if (stream_on && !h->rr)
         return fail(OWW_EINVAL, "oww_submit_ingest_mixed: a masked step needs the register-resident kernel families (use_mfma = 3 or 1; see oww_step_masked)");
-    return submit_impl(h, nullptr, 1, stream_on, in_host, row_bytes, &g);
+    return submit_impl(h, SubmitSource{nullptr, 1, in_host, row_bytes, g}, stream_on);
     OWW_GUARD_END
 }
 

@@ -385,6 +385,21 @@ class StreamEngine:
         self._ingest = (encoding, p, q, n_taps)
         self._ingest_classes = None
 
+    def _ingest_mask(self, stream_on):                   # as the library takes it: contiguous uint8 [S] of 0 / 1, or None
+        if stream_on is None:
+            return None
+        on = np.ascontiguousarray(np.asarray(stream_on) != 0, dtype=np.uint8)
+        if on.shape != (self.n_streams,):
+            raise ValueError(f"stream_on must be [n_streams={self.n_streams}], got {on.shape}")
+        return on
+
+    def _ingest_out(self, out, n_out):                   # the caller's 16 kHz buffer, checked, or a fresh one of zeros
+        if out is None:
+            return np.zeros((self.n_streams, n_out), dtype=np.int16)
+        if out.dtype != np.int16 or out.shape != (self.n_streams, n_out) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous int16 [{self.n_streams}, {n_out}] array")
+        return out
+
     def _ingest_args(self, data: np.ndarray, stream_on):
         if getattr(self, "_ingest", None) is None:
             raise _lib.OwwError("ingest is not configured: call configure_ingest(sample_rate, encoding) first")
@@ -395,22 +410,14 @@ class StreamEngine:
             raise ValueError(f"{encoding} data must be {np.dtype(want).name} [n_streams={self.n_streams}, n], got {data.dtype} {data.shape}")
         if (data.shape[1] * q) % p:
             raise ValueError(f"a message must hold a whole number of output samples: {data.shape[1]} * {q} is no multiple of {p}")
-        on = None
-        if stream_on is not None:
-            on = np.ascontiguousarray(np.asarray(stream_on) != 0, dtype=np.uint8)
-            if on.shape != (self.n_streams,):
-                raise ValueError(f"stream_on must be [n_streams={self.n_streams}], got {on.shape}")
-        return data, on, (data.shape[1] * q) // p
+        return data, self._ingest_mask(stream_on), (data.shape[1] * q) // p
 
     def ingest(self, data: np.ndarray, stream_on: Optional[np.ndarray] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
         """One message per stream, [S, n_in] in the configured encoding -> 16 kHz int16 [S, n_in * q / p], continuous with the stream's
         earlier messages (host, blocking).  A stream with stream_on[s] == 0 is not read, keeps its history and its row of `out` is not
         written (a fresh `out` holds zeros there)."""
         data, on, n_out = self._ingest_args(data, stream_on)
-        if out is None:
-            out = np.zeros((self.n_streams, n_out), dtype=np.int16)
-        elif out.dtype != np.int16 or out.shape != (self.n_streams, n_out) or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous int16 [{self.n_streams}, {n_out}] array")
+        out = self._ingest_out(out, n_out)
         _lib.check(self._lib.oww_ingest(self._h, _ptr(data), 0, data.shape[1], _ptr(on), 0, _ptr(out), 0))
         return out
 
@@ -475,22 +482,14 @@ class StreamEngine:
         if not isinstance(rows, np.ndarray) or rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[0] != self.n_streams \
                 or not rows.flags["C_CONTIGUOUS"]:
             raise ValueError(f"rows must be a C-contiguous uint8 [n_streams={self.n_streams}, row_bytes] array")
-        on = None
-        if stream_on is not None:
-            on = np.ascontiguousarray(np.asarray(stream_on) != 0, dtype=np.uint8)
-            if on.shape != (self.n_streams,):
-                raise ValueError(f"stream_on must be [n_streams={self.n_streams}], got {on.shape}")
-        return rows, on, int(n_out)
+        return rows, self._ingest_mask(stream_on), int(n_out)
 
     def ingest_mixed(self, rows: np.ndarray, n_out: int = CHUNK, stream_on: Optional[np.ndarray] = None,
                      out: Optional[np.ndarray] = None) -> np.ndarray:
         """One message per stream in the stream's own class, rows uint8 [S, row_bytes] (resample.pack_ingest_rows) -> 16 kHz int16
         [S, n_out], continuous with each stream's earlier messages.  Masked streams as in ingest()."""
         rows, on, n_out = self._mixed_args(rows, n_out, stream_on)
-        if out is None:
-            out = np.zeros((self.n_streams, n_out), dtype=np.int16)
-        elif out.dtype != np.int16 or out.shape != (self.n_streams, n_out) or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous int16 [{self.n_streams}, {n_out}] array")
+        out = self._ingest_out(out, n_out)
         _lib.check(self._lib.oww_ingest_mixed(self._h, _ptr(rows), 0, rows.shape[1], n_out, _ptr(on), 0, _ptr(out), 0))
         return out
 

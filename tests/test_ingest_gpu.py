@@ -379,3 +379,30 @@ def test_refusals_return_codes_and_leave_the_handle_usable(eng):
     six = six_messages(eng, 8000, "ulaw")
     assert (eng2_first == six[:, :1280]).all() and (eng2_second == six[:, 1280:2560]).all()
     assert np.isfinite(eng.step_ingest(m)).all()
+
+
+# ---- 9. a bank that stays in global memory -----------------------------------------------------------------------------------------------
+def test_a_bank_beyond_lds_equals_the_stateless_kernel_on_the_prefixed_recording(eng):
+    """16001 Hz: p = 16001, q = 16000, a bank of 16000 x 28 floats (1.8 MB) that no workgroup holds, so `ingest_kernel` reads its taps
+    from global memory -- the launch branch the host's LDS arithmetic (owwhip_ingest.h: single_check) decides.  Configured through the
+    raw ABI; two messages, so that the second one starts from a history.  The contract of section 2: bit equality."""
+    rate = n = 16001
+    p, q, taps = R.design(rate)
+    assert (p, q, taps.shape) == (16001, 16000, (16000, 26)) and q * 28 * 4 > 150 * 1024
+    fed = RR.signals(rate, 2 * n)
+    try:
+        rc, msg = _raw_configure(eng._h, 0, p, q, taps, taps.shape[1])
+        assert rc == 0, msg
+        got = np.empty((S, 2 * q), np.int16)
+        for k in range(2):
+            out = np.empty((S, q), np.int16)
+            rc, msg = _raw_ingest(eng._h, np.ascontiguousarray(fed[:, n * k:n * (k + 1)]), n, None, out)
+            assert rc == 0, msg
+            got[:, q * k:q * (k + 1)] = out
+        pre = np.concatenate([np.zeros((S, taps.shape[1] // 2), np.int16), fed], axis=1)
+        want = eng.resample(np.ascontiguousarray(pre), rate)[:, :got.shape[1]]
+        bad = np.argwhere(got != want)
+        assert not len(bad), f"{len(bad)} outputs differ from oww_resample(zeros(half) | whole), first at {bad[0]}"
+        assert (got[:, q:] != 0).any()
+    finally:
+        eng.configure_ingest(8000, "ulaw")                                   # (the engine object knows its configuration again)

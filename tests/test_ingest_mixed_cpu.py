@@ -196,6 +196,22 @@ def test_class_table_and_checks_under_the_sanitizers(tmp_path):
                         "assign_null": ("null list",)}.items():
         assert got[name].startswith("rc=-1 ") and all(w in got[name] for w in words), (name, got[name])
     assert got["decode_only"] == "rc=0 Hpad_max=0 bank_floats=1" and got["assign_ok"] == "rc=0" and got["assign_none"] == "rc=0"
+    # the single form: one row, no `class` in its messages, and single_check with the launch's LDS as oww_ingest always sized it
+    assert got["one_row"] == "rc=0 classes=1 bank_floats=56 Hpad_max=32 ntp=28 slide=1"
+    for name, words in {"one_bad0": ("encoding 7",), "one_bad1": ("n_taps=25",), "one_bad2": ("n_taps = 0",), "one_bad3": ("p=0",),
+                        "one_bad4": ("null argument: taps",), "s_zero": ("n_out=1280", "n_in=0"), "s_lds": ("n_out=1280", "30000", "LDS", "98304"),
+                        "s_null": ("null argument: in",), "s_n_out_big": ("2^24",), "s_not_whole": ("100", "441")}.items():
+        assert got[name].startswith("rc=-1 ") and all(w in got[name] for w in words), (name, got[name])
+        assert "class" not in got[name] and (not name.startswith("one_bad") or ("kept=1" in got[name] and " c: " in got[name])), (name, got[name])
+    lds = ((28 + 640 + 8 + 3) // 4 * 4) * 4 + 2048 * 2 + 2 * 28 * 4
+    assert got["s_ulaw"] == f"rc=0 n_out=1280 lds={lds} xs_len=676 taps_in_lds=1 row=640 -"
+    lds = ((28 + 16001 + 8 + 3) // 4 * 4) * 4 + 2048 * 2                     # the bank (16000 x 28 floats = 1.8 MB) stays in global memory
+    assert got["s_big_bank"] == f"rc=0 n_out=16000 lds={lds} xs_len=16040 taps_in_lds=0 bank_floats={16000 * 28} -"
+    # the fingerprint hashes the bytes the handle's two formulas hashed
+    for name in ("fp_ulaw8k", "fp_pcm44k", "fp_full", "fp_decode_table", "fp_none"):
+        assert got[name] == "equal=1", (name, got[name])
+    assert got["fp_alaw_decode"] == "equal=1 placeholder=1"
+    assert got["fp_single_vs_one_class"] == "differ=1 same_rows=1"
 
 
 # ---- the server, device mode -------------------------------------------------------------------------------------------------------------

@@ -446,3 +446,33 @@ def test_refusals_move_nothing(eng, single):
         refused(lib.oww_ingest_assign(bare._h, _vp(ids), 1, _vp(np.array([0], np.uint8))), OWW_ESTATE, "not configured")
     finally:
         bare.close()
+
+
+# ---- 9. a class whose bank stays in global memory ------------------------------------------------------------------------------------------
+def test_a_class_with_a_bank_beyond_lds_equals_the_single_format_kernel(eng, single):
+    """16001 Hz (q = 16000: a 1.8 MB bank, read from global memory) next to 8 kHz mu-law (its bank in LDS), streams alternating, two
+    messages of 16000 outputs: the launch's LDS is the 16001 Hz class's need WITHOUT its bank (owwhip_ingest.h: class_geometry)."""
+    classes, n_out, n_msg = [(16001, "pcm16"), (8000, "ulaw")], 16000, 2
+    cls = (np.arange(S) % 2).astype(np.uint8)
+    n_in = [R.class_n_in(rate, n_out) for rate, _ in classes]
+    assert n_in == [16001, 8000] and R.class_row_bytes(classes, n_out) == 32016
+    fed = [np.ascontiguousarray(RR.signals(16001, n_in[0] * n_msg)),
+           np.random.default_rng([711, 16001]).integers(0, 256, (S, n_in[1] * n_msg)).astype(np.uint8)]
+    try:
+        eng.reset()
+        eng.configure_ingest_classes(classes)
+        eng.assign_ingest(np.arange(S), cls)
+        got = []
+        for k in range(n_msg):
+            arrs = [fed[cls[s]][s, n_in[cls[s]] * k:n_in[cls[s]] * (k + 1)] for s in range(S)]
+            got.append(eng.ingest_mixed(R.pack_ingest_rows(arrs, cls, classes, n_out), n_out=n_out))
+        got = np.concatenate(got, axis=1)
+        for c, (rate, enc) in enumerate(classes):
+            single.configure_ingest(rate, enc)
+            want = np.concatenate([single.ingest(np.ascontiguousarray(fed[c][:, n_in[c] * k:n_in[c] * (k + 1)])) for k in range(n_msg)], axis=1)
+            mine = np.flatnonzero(cls == c)
+            bad = np.argwhere(got[mine] != want[mine])
+            assert not len(bad), f"class {classes[c]}: {len(bad)} outputs differ from ingest_kernel, first at stream {mine[bad[0][0]]}, output {bad[0][1]}"
+            assert (got[mine][:, n_out:] != 0).any()
+    finally:
+        fresh(eng)
