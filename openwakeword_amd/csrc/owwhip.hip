@@ -160,6 +160,12 @@ inline hipError_t copy_sync(void* dst, const void* src, size_t n, hipMemcpyKind 
 }
 
 constexpr int kSmallLaunchWgs = 2 * 256;      // stage / heads launches of at most two workgroups per CU (MI355X: 256 CUs) use the deep weight rings
+// stage B with its weights resident in LDS (owwhip_hx.h: hstage_kernel NS = 1): one persistent workgroup per CU, from this many groups
+// (= streams) on: the smallest size of the sweep 4,096 .. 131,072 in profiles/r07_resident_b_ab.txt at which stage B AND the step
+// read lower than with the ring kernels in every repeat (8,192: B 0.089 -> 0.082 ms, step 0.485 -> 0.481; at 4,096 stage B reads
+// 2-3 us lower but the step does not resolve from its own repeats)
+constexpr int kResidentBMinGroups = 8192;
+constexpr int kResidentBWgs = 256;
 
 struct FastGroup : HeadGroup {           // + where bind_weights put the group's pieces on the device
     DevBuf<NetDesc> d_nets;
@@ -276,6 +282,7 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     float hx_absmax[20] = {};        // largest |activation| of each layer in the calibration run (exact-fp32 kernels)
     std::vector<int16_t> cal_user;   // oww_set_calibration: caller's calibration audio as [n_seg][CAL_T * 1280] segments
     int small_wgs = kSmallLaunchWgs, small_wgs_heads = kSmallLaunchWgs;   // A/B aids: OWW_SMALL_WGS / OWW_SMALL_WGS_HEADS (0 = never the deep rings)
+    int resident_b = -1, resident_b_wgs = kResidentBWgs;                  // OWW_RESIDENT_B=0|1|auto (-1 = auto: by size), OWW_RESIDENT_B_WGS = grid cap
     float hx_selftest_err = 0.f, hx_selftest_ref = 0.f, hx_selftest_score_err = 0.f;   // commit-time f16-split vs exact-fp32 comparison
     bool fuse = false;               // f16-split family: mel front end fused into stage A for one-chunk streaming steps (owwhip_fused.h)
     // custom verifiers on the device (oww_set_verifier)
@@ -466,6 +473,15 @@ void launch_rstage(oww_ctx* h, const owr::RStageParams& p, int cls) {
     hipStream_t st = h->stream;
     Timed t(h, cls);
     const int nwg = (p.n_groups + WG - 1) / WG;
+    if constexpr (HX && !DBG && std::is_same<CH, owh::HB>::value) {
+        // stage B, no group list: weights resident in LDS, persistent workgroups that each walk a contiguous range of groups
+        const bool resident = p.glist == nullptr && p.n_groups > 0 && (h->resident_b < 0 ? p.n_groups >= kResidentBMinGroups : h->resident_b != 0);
+        if (resident) {
+            const int grid = std::max(1, std::min(h->resident_b_wgs, (p.n_groups + owh::RES_B_WG - 1) / owh::RES_B_WG));
+            hipLaunchKernelGGL((owh::hstage_kernel<CH, LAST, false, owh::RES_B_WG, 1>), dim3(grid), dim3(64 * owh::RES_B_WG), owh::RES_B_LDS_BYTES, st, p);
+            return;
+        }
+    }
     if (HX && !DBG && nwg <= h->small_wgs) hipLaunchKernelGGL((owh::hstage_kernel<CH, LAST, false, WG, 3>), dim3(nwg), dim3(64 * WG), 0, st, p);
     else if (HX) hipLaunchKernelGGL((owh::hstage_kernel<CH, LAST, DBG, WG>), dim3(nwg), dim3(64 * WG), 0, st, p);
     else hipLaunchKernelGGL((owr::rstage_kernel<CR, LAST, DBG>), dim3((p.n_groups + 3) / 4), dim3(256), 0, st, p);
@@ -1505,6 +1521,7 @@ int set_kernel_lds(oww_ctx* h) {
     if (!h->rnn_nets.empty()) lds(heads_rnn_kernel<RNN_SPW>, (int)rnn_lds_bytes(RNN_TMAX));
     if (h->vad) lds(owv::vad_front_kernel, owv::V_LDS_BYTES);
     lds(owf::hmelA_kernel<false>, owf::FA_LDS_BYTES); lds(owf::hmelA_kernel<true>, owf::FA_LDS_BYTES);
+    lds(owh::hstage_kernel<owh::HB, false, false, owh::RES_B_WG, 1>, owh::RES_B_LDS_BYTES);
     lds(stageA_kernel<true>, CfgA::LDS_BYTES); lds(stageA_kernel<false>, CfgA::LDS_BYTES);
     lds(stage_kernel<CfgB, true, false>, CfgB::LDS_BYTES); lds(stage_kernel<CfgB, false, false>, CfgB::LDS_BYTES);
     lds(stage_kernel<CfgC, true, false>, CfgC::LDS_BYTES); lds(stage_kernel<CfgC, false, false>, CfgC::LDS_BYTES);
@@ -1939,6 +1956,8 @@ int oww_commit(oww_ctx* h) {
     h->fuse = h->hx && !getenv("OWW_NO_FUSE");                            // (A/B switch: OWW_NO_FUSE=1 keeps the separate mel kernel)
     if (const char* e = getenv("OWW_SMALL_WGS")) h->small_wgs = atoi(e);
     if (const char* e = getenv("OWW_SMALL_WGS_HEADS")) h->small_wgs_heads = atoi(e);
+    if (const char* e = getenv("OWW_RESIDENT_B")) h->resident_b = strcmp(e, "auto") == 0 ? -1 : (atoi(e) != 0 ? 1 : 0);
+    if (const char* e = getenv("OWW_RESIDENT_B_WGS")) h->resident_b_wgs = std::max(1, atoi(e));
     if (const char* e = getenv("OWW_GENERIC_SPW")) { const int v = atoi(e); h->generic_spw = v == 4 || v == 16 ? v : 0; }
     h->post_in_heads = h->fuse && h->groups.size() == 1 && h->groups[0].ht == 4 && h->generic_nets.empty() && h->rnn_nets.empty() && h->NL > 0;
     if (int rc = set_kernel_lds(h)) return rc;

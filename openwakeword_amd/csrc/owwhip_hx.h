@@ -371,17 +371,28 @@ __device__ __forceinline__ void ring_issue(const float* __restrict__ gsrc, float
 template <int NS, int CH, int NBLK, int NCTO, int NEXT_NBLK, int WG>
 __device__ __forceinline__ const float* ring_begin(const WRing<NS>& r, int oct, const float* __restrict__ w, const float* __restrict__ w_next,
                                                    int wave, int lane) {
+    // NS = 1, RESIDENT: every layer's chunks already sit in LDS (s[l] = base of layer l = CH / NCTO of the stage, copied once per
+    // workgroup by hstage_kernel's prologue).  Nothing is issued and ring_end is empty: no wait, no barrier.
+    // The opaque zero makes the chunk's per-lane LDS address a value of this chunk step (one v_add): left to itself the compiler
+    // forms one address register per 1 KB block of the 126 KB ahead of the group loop and spills them (30 VGPRs to scratch).
+    if constexpr (NS == 1) {
+        int z = 0;
+        asm volatile("" : "+s"(z));
+        return r.s[CH / NCTO] + oct * NBLK * 256 + z;
+    } else {
     constexpr int P = NS - 1;
     const int c = oct + P;                                   // the chunk issued in this step (past NCTO: the next layer's)
     float* dst = r.s[(CH + oct + P) % NS];                   // its slot held chunk oct - 1: every wave passed the last barrier
     if (c < NCTO) ring_issue<NS, NBLK, WG>(w + (size_t)c * NBLK * 256, dst, wave, lane);
     else if (NEXT_NBLK > 0 && c - NCTO < P) ring_issue<NS, (NEXT_NBLK > 0 ? NEXT_NBLK : 1), WG>(w_next + (size_t)(c - NCTO) * NEXT_NBLK * 256, dst, wave, lane);
     return r.s[(CH + oct) % NS];
+    }
 }
 template <int NS, int NBLK, int NCTO, int NEXT_NBLK, int WG>
 __device__ __forceinline__ void ring_end(int oct) {
-    if (!(oct + 1 < NCTO || NEXT_NBLK > 0)) return;          // no chunk oct + 1 in this launch
-    if constexpr (NS == 2) owr::chunk_sync();
+    if (NS == 1 || !(oct + 1 < NCTO || NEXT_NBLK > 0)) return;   // resident weights, or no chunk oct + 1 in this launch
+    if constexpr (NS == 1) {}
+    else if constexpr (NS == 2) owr::chunk_sync();
     else {
         // chunk oct + 1 must have landed; chunks oct + 2 .. oct + P (issued after it: VMEM returns in order) may stay in flight.  NS = 3:
         // that is the chunk issued in this step; deeper rings (NS = 4, 5: launches of at most ONE workgroup per CU, where nothing else
@@ -886,6 +897,19 @@ __device__ __forceinline__ void conv_time_hxm(const Op (&h0)[KSF], const Op (&h1
 #ifndef OWH_SPRIO_B
 #define OWH_SPRIO_B 1111
 #endif
+// The resident form of stage B (persistent waves that walk groups on their own: hstage_kernel NS = 1): levels that RISE with a wave's
+// progress through its group, so that the wave nearest to its stores is served first (the fused front end's answer).
+// Same-box alternating runs at 131,072 streams (profiles/r07_resident_b_ab.txt): 1223 1.146 ms against 1.163 with 1111 and 1.176 with
+// no priorities; 0123, 1123, 1233, 2233 all within 1 % of 1223 (1.143 .. 1.158).
+#ifndef OWH_SPRIO_RB
+#define OWH_SPRIO_RB 1223
+#endif
+// resident form: history rows of conv b / conv d loaded into registers one 1x3 layer EARLY (above conv a / conv c) instead of at the
+// layer boundary.  24 more live VGPRs across a 1x3 layer: the compiler spills 12 registers (36 B of scratch) and the stage reads
+// 1.19 ms against 1.163 with the loads at the boundary (same file): off
+#ifndef OWH_RES_HIST_EARLY
+#define OWH_RES_HIST_EARLY 0
+#endif
 #ifndef OWH_SPRIO_C
 #define OWH_SPRIO_C 3210
 #endif
@@ -920,15 +944,27 @@ __device__ __forceinline__ void load_tile_lds(f32x4 (&t)[NCT], const float* base
         }
 }
 
+// the resident form of stage B (hstage_kernel<HB, ..., RES_B_WG, 1>): waves per workgroup and bytes of dynamic LDS = all four layers' chunks
+constexpr int RES_B_WG = 12, RES_B_LDS_BYTES = 126 * 1024;
+template <bool RES> __device__ __forceinline__ float* res_lds(float* ring_slot0) {
+    if constexpr (RES) { extern __shared__ __attribute__((aligned(16))) float res_dyn[]; return res_dyn; }
+    else return ring_slot0;
+}
 template <class C, bool LAST, bool DBG, int WG = OWH_WG, int NS = 2>
-__global__ __launch_bounds__(64 * WG, (DBG || NS > 3 ? 1 : (NS == 3 && C::WPS > 2 ? 2 : C::WPS))) void hstage_kernel(owr::RStageParams p) {
+__global__ __launch_bounds__(64 * WG, (DBG || NS > 3 || NS == 1 ? 1 : (NS == 3 && C::WPS > 2 ? 2 : C::WPS))) void hstage_kernel(owr::RStageParams p) {
     using namespace owr;
     constexpr int NCTI = C::NCTI, NCT = C::NCT, R = C::RP, F = C::F;   // R = rows per pass (see owr::RCfg::RP)
     static_assert(!LAST || C::NPASS == 1, "the last stage runs in one pass");
     // every pass starts at ring phase CH0 = 0 (conv a) and advances the ring by 4 * NCT chunks: with more than one pass the slot the
     // chunk prefetched by conv d lands in is the one conv a of the next pass reads only if that advance is a multiple of the ring length
     static_assert(NS == 2 || C::NPASS == 1 || (4 * NCT) % NS == 0, "multi-pass stages need a ring phase that returns to 0 after each pass");
-    static_assert(NS >= 2 && NS <= 5 && NS - 1 <= NCT, "the chunks in flight at a layer boundary belong to at most the next layer");
+    static_assert(NS >= 1 && NS <= 5 && NS - 1 <= NCT, "the chunks in flight at a layer boundary belong to at most the next layer");
+    // NS = 1, RESIDENT (stage B only: its 126 KB of packed weights fit a CU's LDS beside nothing else): ONE workgroup of WG = 12 waves
+    // per CU copies all four layers' chunks into dynamic LDS once, passes one barrier, and from then on every wave walks groups of its
+    // workgroup's contiguous range on its own -- claimed one at a time from a counter in LDS -- without a barrier or a wait on another
+    // wave.  Same layer bodies, same k order, same epilogues: results do not depend on NS (tested bit for bit).
+    constexpr bool RES = NS == 1;
+    static_assert(!RES || (!LAST && !DBG && C::NPASS == 1), "resident weights: one pass, no debug dumps, not the last stage");
     constexpr int KSA = (NCTI + 1) / 2, KS = (NCT + 1) / 2;          // k-steps per tap: first layer / other layers
     constexpr int NBA = 3 * KSA * 2, NB = 3 * KS * 2;                // 1 KB blocks per chunk
     using TK = TimeK<NCT, C::HOUT>;
@@ -937,7 +973,7 @@ __global__ __launch_bounds__(64 * WG, (DBG || NS > 3 ? 1 : (NS == 3 && C::WPS > 
     constexpr bool PIPE = OWH_PIPE != 0;
     constexpr int APCFG = NCT == 3 ? OWH_APIPE_B : NCT == 5 ? OWH_APIPE_C : LAST ? OWH_APIPE_E : OWH_APIPE_D;
     constexpr bool APM = (APCFG & 1) != 0, APT = (APCFG & 2) != 0;       // A operands one k-group ahead (apipe_step): mel / time layers
-    constexpr int SPCODE = NCT == 3 ? OWH_SPRIO_B : NCT == 5 ? OWH_SPRIO_C : LAST ? OWH_SPRIO_E : OWH_SPRIO_D;   // wave priority by layer (sprio)
+    constexpr int SPCODE = NS == 1 ? OWH_SPRIO_RB : NCT == 3 ? OWH_SPRIO_B : NCT == 5 ? OWH_SPRIO_C : LAST ? OWH_SPRIO_E : OWH_SPRIO_D;   // wave priority by layer (sprio)
     // a full odd last channel tile (stage B: 48 = 32 + 16) in the two-MFMA remainder form of split_dup
     constexpr bool REM2 = OWH_REM2 && NCT % 2 == 1 && !C::HOUT && !LAST && !(OWH_KMERGE && OWH_KMERGE_B) && !(OWH_KMERGE_MEL && OWH_KMERGE_MEL2B);
     // 1x3 layers whose 72-channel input leaves a half remainder tile, in the K-merged form (conv_mel_hxm): layer a of stage D, c of C
@@ -956,33 +992,85 @@ __global__ __launch_bounds__(64 * WG, (DBG || NS > 3 ? 1 : (NS == 3 && C::WPS > 
     // through the L2 -> CU path) while the preceding 1x3 layer computes, instead of by register loads at the layer boundary where
     // their latency is exposed with only 2-3 waves per SIMD.  Stage B: 6 KB per wave, -2.5 % (same-box A/B); stage C (10 KB per wave,
     // OWH_HIST_LDS_C) measured slower; D and E have no LDS left for it at three workgroups per CU.
-    constexpr bool HLDS = OWH_HIST_LDS && !LAST && C::NPASS == 1 && (C::SPT == 1 || (C::SPT == 2 && OWH_HIST_LDS_C));
+    // (the resident form has 34 KB of LDS left for 12 waves x 6 KB: its history rows come through registers)
+    constexpr bool HLDS = OWH_HIST_LDS && !RES && !LAST && C::NPASS == 1 && (C::SPT == 1 || (C::SPT == 2 && OWH_HIST_LDS_C));
     constexpr int HROW = NCT * 4 * 64;                                // floats of one history row of a wave's group
-    const int lane = threadIdx.x & 63;
+    const int lane0 = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int g = blockIdx.x * WG + wave;
     // the slots of the weight ring are DISTINCT LDS objects (see WRing above)
-    __shared__ __attribute__((aligned(16))) float wbuf[WBS];
-    __shared__ __attribute__((aligned(16))) float wbuf1[WBS];
+    __shared__ __attribute__((aligned(16))) float wbuf[RES ? 4 : WBS];
+    __shared__ __attribute__((aligned(16))) float wbuf1[RES ? 4 : WBS];
     __shared__ __attribute__((aligned(16))) float wbuf2[NS >= 3 ? WBS : 4];
     __shared__ __attribute__((aligned(16))) float wbuf3[NS >= 4 ? WBS : 4];
     __shared__ __attribute__((aligned(16))) float wbuf4[NS >= 5 ? WBS : 4];
-    const WRing<NS> ring{{wbuf, wbuf1, wbuf2, wbuf3, wbuf4}};
+    // resident: layer bases in dynamic LDS -- conv a NCT chunks of NBAM blocks, b of NBT, c of NBCM, d of NBT (d_conv's arrays as they are)
+    constexpr int RES_OFF_B = NCT * NBAM * 256, RES_OFF_C = RES_OFF_B + NCT * NBT * 256, RES_OFF_D = RES_OFF_C + NCT * NBCM * 256;
+    static_assert(!RES || (RES_OFF_D + NCT * NBT * 256) * 4 == RES_B_LDS_BYTES, "launch_rstage sizes the dynamic LDS with RES_B_LDS_BYTES");
+    float* const rw = res_lds<RES>(wbuf);
+    const WRing<NS> ring{{rw, RES ? rw + RES_OFF_B : wbuf1, RES ? rw + RES_OFF_C : wbuf2, RES ? rw + RES_OFF_D : wbuf3, wbuf4}};
     __shared__ __attribute__((aligned(16))) float sbn[4][NCT * 16];      // per layer: K * BatchNorm shift in tile row order = accumulator start values
     __shared__ __attribute__((aligned(16))) float hlds[HLDS ? WG * 2 * HROW : 4];
     float* const hl = hlds + (HLDS ? wave * 2 * HROW : 0);
-    const bool active = g < p.n_groups;
+    __shared__ int res_next;              // resident: the next unclaimed group of this workgroup's range
+    const bool active = RES || g < p.n_groups;
+    int g_end = 0;
+    if constexpr (RES) {
+        // the workgroup's contiguous range of groups (sizes differ by at most one), and the weights: every thread copies its share of
+        // the four packed arrays (plain 16-byte loads and LDS stores, like the fused front end's tables: once per workgroup)
+        const int nwg = gridDim.x, per = p.n_groups / nwg, rem = p.n_groups % nwg, b = blockIdx.x;
+        const int g_lo = b * per + min(b, rem);
+        g_end = g_lo + per + (b < rem ? 1 : 0);
+        if (threadIdx.x == 0) res_next = g_lo;
+        constexpr int off4[5] = {0, RES_OFF_B / 4, RES_OFF_C / 4, RES_OFF_D / 4, RES_B_LDS_BYTES / 16};
+        constexpr int NT = 64 * WG, MAXU = (off4[2] - off4[1] + NT - 1) / NT;     // (all of a thread's loads in flight before its first LDS store)
+        static_assert(off4[1] <= MAXU * NT && off4[3] - off4[2] <= MAXU * NT && off4[4] - off4[3] <= MAXU * NT, "layer b's array is the largest");
+        f32x4 t[4][MAXU];
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+#pragma unroll
+            for (int u = 0; u < MAXU; ++u) {
+                const int i = threadIdx.x + u * NT;
+                if (i < off4[l + 1] - off4[l]) t[l][u] = reinterpret_cast<const f32x4*>(p.w[l])[i];
+            }
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+#pragma unroll
+            for (int u = 0; u < MAXU; ++u) {
+                const int i = threadIdx.x + u * NT;
+                if (i < off4[l + 1] - off4[l]) reinterpret_cast<f32x4*>(rw)[off4[l] + i] = t[l][u];
+            }
+    } else {
     if (!active) g = p.n_groups - 1;
     if (p.glist) g = p.glist[g];          // a masked step with few participants runs only the groups that hold one (owwhip.hip: build_active_lists)
     else g += p.g_base;                   // (g_base: always 0 since the block-pipelined step was removed)
+    }
     lanemask_t bad = 0;
-    ring_issue<NS, NBAM, WG>(p.w[0], wbuf, wave, lane);
-    if (NS >= 3) ring_issue<NS, NBAM, WG>(p.w[0] + (size_t)NBAM * 256, wbuf1, wave, lane);   // (NS - 1 chunks in flight from the start)
-    if (NS >= 4) ring_issue<NS, NBAM, WG>(p.w[0] + (size_t)2 * NBAM * 256, wbuf2, wave, lane);
-    if (NS >= 5) ring_issue<NS, NBAM, WG>(p.w[0] + (size_t)3 * NBAM * 256, wbuf3, wave, lane);
+    if constexpr (!RES) {
+    ring_issue<NS, NBAM, WG>(p.w[0], wbuf, wave, lane0);
+    if (NS >= 3) ring_issue<NS, NBAM, WG>(p.w[0] + (size_t)NBAM * 256, wbuf1, wave, lane0);   // (NS - 1 chunks in flight from the start)
+    if (NS >= 4) ring_issue<NS, NBAM, WG>(p.w[0] + (size_t)2 * NBAM * 256, wbuf2, wave, lane0);
+    if (NS >= 5) ring_issue<NS, NBAM, WG>(p.w[0] + (size_t)3 * NBAM * 256, wbuf3, wave, lane0);
+    }
     for (int i = threadIdx.x; i < 4 * NCT * 16; i += 64 * WG) {
         const int l = i / (NCT * 16), c = i % (NCT * 16);
         sbn[l][c] = p.shift[l][c];
+    }
+    if constexpr (RES) __syncthreads();   // the only barrier of the resident form: from here on no wave waits for another
+    for (;;) {                            // resident: one claimed group per turn; the ring forms: once
+    // resident: the lane index of THIS turn (an opaque zero added): what derives from it -- row offsets, tile positions, the 64-bit
+    // per-lane bases of the hand-over rows -- is then recomputed per group (a few VALU) instead of being kept alive, i.e. spilled,
+    // across the loop (the fused front end's stream loop does the same)
+    int lane_z = 0;
+    if constexpr (RES) asm volatile("" : "+v"(lane_z));
+    const int lane = RES ? ((lane0 + lane_z) & 63) : lane0;      // (& 63: the range stays known -- scalar base + 32-bit lane offset addressing)
+    if constexpr (RES) {
+        int k = 0;
+        if (lane0 == 0) k = __hip_atomic_fetch_add(&res_next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);    // ds_add_rtn_u32
+        g = __builtin_amdgcn_readfirstlane(k);
+        if (g >= g_end) break;            // nothing left: a wave that never got a group has stored nothing
+        g += p.g_base;
+        bad = 0;
     }
     const int s_first = g * C::SPT;
     // masked steps (oww_step_masked): a stream that sits this step out is computed like any other (the workgroup shares its weight
@@ -1002,7 +1090,10 @@ __global__ __launch_bounds__(64 * WG, (DBG || NS > 3 ? 1 : (NS == 3 && C::WPS > 
         load_tile_h<NCTI, C::HIN>(X, p.xin + ((size_t)price_alias<(OWH_PRICE_HANDOVER & 2) != 0 && C::CIN == 24>(g) * C::R + pass * R + r) * (NCTI * 4 * 64), lane);
         to_ops<NCTI, C::HIN>(X, Xo[r]);
     }
-    if (pass == 0) chunk_sync();
+    constexpr bool HEARLY = RES && OWH_RES_HIST_EARLY != 0 && !MERGE;
+    f32x4 E0[HEARLY ? NCT : 1], E1[HEARLY ? NCT : 1];
+    if constexpr (HEARLY) { load_tile_h<NCT, C::HOUT>(E0, hb, lane); load_tile_h<NCT, C::HOUT>(E1, hb + NCT * 4 * 64, lane); }
+    if (!RES && pass == 0) chunk_sync();
     sprio<SPCODE, 0>();
 
     // conv a: 1x3, CIN -> C
@@ -1040,7 +1131,8 @@ __global__ __launch_bounds__(64 * WG, (DBG || NS > 3 ? 1 : (NS == 3 && C::WPS > 
         __builtin_amdgcn_sched_barrier(0);
         conv_time_hxm<TK::KSF, TK::NMK, NCT, R, true, NCT, NBCM, WG, C::HOUT, NS, APT>(H0F, H1F, AoF, M, Y, ring, p.w[1], p.w[2], sbn[1], p.clampv[1], wave, lane, bad);
     } else {
-    {
+    if constexpr (HEARLY) { to_ops<NCT, C::HOUT, REM2>(E0, H0); to_ops<NCT, C::HOUT, REM2>(E1, H1); }
+    else {
         f32x4 T0[NCT], T1[NCT];
         if (HLDS) { load_tile_lds<NCT, C::HOUT>(T0, hl, lane); load_tile_lds<NCT, C::HOUT>(T1, hl + HROW, lane); }
         else { load_tile_h<NCT, C::HOUT>(T0, hb, lane); load_tile_h<NCT, C::HOUT>(T1, hb + NCT * 4 * 64, lane); }
@@ -1065,6 +1157,7 @@ __global__ __launch_bounds__(64 * WG, (DBG || NS > 3 ? 1 : (NS == 3 && C::WPS > 
 #pragma unroll
     for (int r = 0; r < R; ++r) to_ops<NCT, C::HOUT, REM2>(Y[r], Ao[r]);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (HEARLY) { load_tile_h<NCT, C::HOUT>(E0, hd, lane); load_tile_h<NCT, C::HOUT>(E1, hd + NCT * 4 * 64, lane); }
     sprio<SPCODE, 2>();
     // conv c: 1x3
     if constexpr (MMC) {
@@ -1099,7 +1192,8 @@ __global__ __launch_bounds__(64 * WG, (DBG || NS > 3 ? 1 : (NS == 3 && C::WPS > 
         __builtin_amdgcn_sched_barrier(0);
         conv_time_hxm<TK::KSF, TK::NMK, NCT, R, true, 3 * NCT, (C::NPASS > 1 ? NBAM : 0), WG, C::HOUT, NS, APT>(H0F, H1F, AoF, M, Y, ring, p.w[3], p.w[0], sbn[3], p.clampv[3], wave, lane, bad);
     } else {
-    {
+    if constexpr (HEARLY) { to_ops<NCT, C::HOUT, REM2>(E0, H0); to_ops<NCT, C::HOUT, REM2>(E1, H1); }
+    else {
         f32x4 T0[NCT], T1[NCT];
         if (HLDS) { load_tile_lds<NCT, C::HOUT>(T0, hl, lane); load_tile_lds<NCT, C::HOUT>(T1, hl + HROW, lane); }
         else { load_tile_h<NCT, C::HOUT>(T0, hd, lane); load_tile_h<NCT, C::HOUT>(T1, hd + NCT * 4 * 64, lane); }
@@ -1200,6 +1294,8 @@ __global__ __launch_bounds__(64 * WG, (DBG || NS > 3 ? 1 : (NS == 3 && C::WPS > 
     }   // pass
     if (!LAST && C::NPASS > 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // drain the chunk the last pass prefetched
     raise_range_flag(bad, p.range_flag, s_first, C::SPT);
+    if constexpr (!RES) break;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

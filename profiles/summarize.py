@@ -17,7 +17,7 @@ def short(name):
         if tag in name and ("owr::rstage" in ("owr::" + name) or name.startswith("rstage")):
             return s + "_rr"
         if tag in name and name.startswith(("owh::hstage", "hstage")):
-            return s + "_hx"
+            return s + "_hx"                     # (ring forms and stage B's resident form <..., 12, 1> alike: the full-grid launch is kept)
     if "hmelA_kernel" in name:
         return "stageA_hx"                       # mel front end + stage A in one launch (owwhip_fused.h); same key as the separate stage A
     if "vad_front_kernel" in name:
