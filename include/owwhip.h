@@ -516,6 +516,56 @@ int  oww_get_event_features(oww_ctx* h, int32_t first, int32_t n, float* out, in
 const oww_event* oww_events_dev(const oww_ctx* h, const int32_t** count_dev);
 const float* oww_event_features_dev(const oww_ctx* h);
 
+/* ---- audio: each stream's recent 16 kHz PCM on the device, and the audio behind every event -------------------------------------------
+ * The reference keeps the last 10 s of a stream's audio beside its features (AudioFeatures.raw_data_buffer, utils.py:164,174,407), and its
+ * tooling lives on that buffer: examples/capture_activations.py:134-174 writes the last 5 s to a WAV one second after an activation,
+ * custom-verifier training clips are cut from it, and a deployment hands the command behind the wake word to a recogniser.  Here a
+ * stream's audio otherwise lives for one step, and with the ingest entries (oww_step_ingest*, oww_submit_ingest_mixed) it never exists on
+ * the host at all.  With audio configured the handle keeps a ring int16 [S][ring_chunks][1280] and one uint32 chunk counter per stream.
+ *   oww_audio_configure  before oww_commit: ring_chunks 1 .. 1024 per stream (the reference's 10 s: 125) and event_chunks 0 ..
+ *                       ring_chunks snapshot chunks per event (a positive value needs oww_events_configure: without it oww_commit
+ *                       returns OWW_EINVAL).  oww_commit allocates S x ring_chunks x 2,560 bytes (64-bit arithmetic: 131,072 x 125
+ *                       chunks are 42 GB) and, per event buffer set -- one for the synchronous calls, one per pipeline slot at the first
+ *                       oww_submit -- (capacity + 1) x event_chunks x 2,560 bytes; what does not fit is OWW_ENOMEM, with the bytes in
+ *                       the message.  A handle that never calls it allocates and launches exactly what it did before, produces the same
+ *                       bits and reports the same oww_state_info; the read entries then return OWW_ESTATE, oww_event_audio_dev NULL.
+ *   Append              every call that advances streams -- oww_step (multi-chunk and long calls: the whole call once),
+ *                       oww_step_masked, oww_step_ingest, oww_step_ingest_mixed, oww_submit, oww_submit_masked, oww_submit_ingest_mixed
+ *                       (from the slot's own buffer, on the compute stream) -- appends the call's 16 kHz samples exactly as the front end
+ *                       consumed them (ingest: the decoded and resampled staging buffer) to the ring of every stream that took part:
+ *                       its k chunks in order, of a call with k > ring_chunks the last ring_chunks, and k is added to the stream's
+ *                       counter.  A stream that sits a masked step out keeps every bit of ring and counter.  The append runs behind
+ *                       the step's launches and before the events, so a snapshot ends with the detecting chunk; it is not part of the
+ *                       oww_use_graph graph, and oww_embed, oww_embed_clips, oww_mel and the commit probes never touch a ring.
+ *                       oww_reset zeroes ring and counter of the streams it resets (utils.py:174).
+ *   oww_get_audio       the newest n_chunks (1 .. ring_chunks) chunks of streams stream_ids[n] (duplicates and any order), oldest
+ *                       first, as int16 [n][n_chunks * 1280] into `out` (host, or a 16-byte aligned device pointer with out_on_device);
+ *                       chunks the stream has not received since its reset read as zero.  counts (host [n], or NULL): the streams'
+ *                       counters.  Like oww_state_export it runs on the handle's stream behind every queued step and returns when it is
+ *                       complete.  This is the post-roll path: for "one second after the hit" ask for the stream 13 steps later.
+ *   oww_get_event_audio  snapshots of records [first, first + n) of the call oww_get_events refers to: int16 [n][event_chunks * 1280],
+ *                       the newest event_chunks chunks of the record's stream in the detecting step, oldest first, zero where the
+ *                       stream had received less since its reset.  Snapshot i belongs to stored record i (the rank, as with
+ *                       feature_index).  Validity, host / device `out` and the wait as oww_get_event_features; pipelined steps keep
+ *                       their snapshots in the slot's own device buffer until asked.  first + n beyond n_stored, or event_chunks == 0:
+ *                       OWW_EINVAL.
+ *   oww_event_audio_dev  the snapshots of the last synchronous call on the device, [capacity][event_chunks][1280], the counterpart of
+ *                       oww_event_features_dev (NULL without event_chunks); one spare snapshot behind index capacity - 1 is never written.
+ * State records: with audio a record gains two flat sections behind the others, the ring (ring_chunks x 2,560 bytes, as it lies) and a
+ * 16-byte piece with the counter, and the fingerprint covers ring_chunks: a record from a handle with another ring is refused as any
+ * other configuration mismatch.  oww_move_streams carries both; a moved or imported stream's later snapshots and oww_get_audio reads are
+ * bit for bit those of a stream that stayed.
+ * Every failing call leaves the handle untouched: out-of-range ring_chunks / event_chunks / n_chunks / stream id / record range ->
+ * OWW_EINVAL, oww_audio_configure after commit -> OWW_ESTATE.
+ * Cost model: pure data movement in 16-byte pieces, timed under kernel class 7.  Per stream and chunk the append reads 2,560 bytes and
+ * writes 2,560 (one wave per stream, one launch per call: 0.67 GB per step at 131,072 streams); a snapshot launch, only with
+ * event_chunks > 0, moves 2 x event_chunks x 2,560 bytes per stored event on a grid sized to the chip, not to the capacity;
+ * oww_get_audio moves 2 x n_chunks x 2,560 bytes per listed stream plus the copy to the host and is not counted by oww_kernel_times. */
+int  oww_audio_configure(oww_ctx* h, int32_t ring_chunks, int32_t event_chunks);
+int  oww_get_audio(oww_ctx* h, const int32_t* stream_ids, int32_t n, int32_t n_chunks, int16_t* out, int out_on_device, uint32_t* counts);
+int  oww_get_event_audio(oww_ctx* h, int32_t first, int32_t n, int16_t* out, int out_on_device);
+const int16_t* oww_event_audio_dev(const oww_ctx* h);
+
 /* ---- multi-GPU: delivery of the scores to one rank over RCCL (xGMI), for binders without torch.distributed ----------------------
  * Streams are independent, so N GPUs = N handles in N processes, each owning a contiguous range of the global streams (the
  * reference's only scale-out, utils.py:502-536 bulk_predict, splits FILES over processes the same way); nothing in the data path

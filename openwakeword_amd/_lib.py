@@ -110,6 +110,10 @@ SYMBOLS = {
     "oww_get_event_features": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int]),
     "oww_events_dev": (_P, [_P, C.POINTER(_P)]),
     "oww_event_features_dev": (_P, [_P]),
+    "oww_audio_configure": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "oww_get_audio": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int, _P]),
+    "oww_get_event_audio": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int]),
+    "oww_event_audio_dev": (_P, [_P]),
     "oww_comm_id": (C.c_int, [_P]),
     "oww_comm_init": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "oww_gather_scores": (C.c_int, [_P, _P, _P]),

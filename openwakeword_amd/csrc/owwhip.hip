@@ -28,6 +28,7 @@
 #include "owwhip_fused.h"
 #include "owwhip_state.h"
 #include "owwhip_events.h"
+#include "owwhip_audio.h"
 
 using namespace owk;
 using namespace owp;
@@ -233,6 +234,7 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     // with page-locked mirrors of counts and records that ride down behind the slot's scores
     struct EventBuf {
         DevBuf<oww_event> d_rec; DevBuf<int> d_count; DevBuf<float> d_snap;     // [cap + 1], {n_stored, n_total}, [cap + 1][rows][96]
+        DevBuf<int16_t> d_asnap;                                                // [cap + 1][event_chunks][1280] (oww_audio_configure)
         PinnedBuf<oww_event> h_rec; PinnedBuf<int> h_count;                     // ingest slots only
     };
     int evt_cap = 0, evt_rows = 0;               // 0 = no events (oww_events_configure)
@@ -240,6 +242,11 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     DevBuf<int> d_evblock; int evt_blocks = 0;
     EventBuf evt_sync, evt_slot[2];
     const EventBuf* evt_cur = nullptr;           // what oww_get_events refers to: the last synchronous call or the last collected step
+    // per-stream audio rings (oww_audio_configure; owwhip_audio.h, owwhip_audio_host.h): nothing without it
+    int aud_ring = 0, aud_evt = 0;               // ring_chunks (0 = no audio), event_chunks
+    DevBuf<int16_t> d_aring;                     // [S][aud_ring][1280]
+    DevBuf<uint32_t> d_acount;                   // [S] chunks since the stream's reset
+    DevBuf<int16_t> d_aout; DevBuf<int> d_aids; DevBuf<uint32_t> d_acnt;   // oww_get_audio: staging of a host read, the list, the counters
 
     uint64_t n_submit = 0, n_collect = 0;
     DevBuf<float> d_featinit, d_dbg;
@@ -1010,6 +1017,11 @@ int alloc_event_buf(oww_ctx* h, oww_ctx::EventBuf& b, bool host_mirror) {
     if (int rc = dalloc(h->stream, b.d_rec, (size_t)h->evt_cap + 1)) return rc;
     if (int rc = dalloc(h->stream, b.d_count, 2)) return rc;
     if (h->evt_rows > 0) if (int rc = dalloc(h->stream, b.d_snap, ((size_t)h->evt_cap + 1) * h->evt_rows * OWW_EMB_DIM, false)) return rc;
+    if (h->aud_evt > 0) {
+        const uint64_t nb = owa::snapshot_bytes(h->evt_cap, h->aud_evt);
+        if (b.d_asnap.alloc((size_t)(nb / sizeof(int16_t))))
+            return fail(OWW_ENOMEM, "oww_audio_configure: out of device memory for %llu bytes of event audio snapshots", (unsigned long long)nb);
+    }
     if (host_mirror) {
         HIPCHK(herr(b.h_rec.alloc((size_t)h->evt_cap, hipHostMallocDefault)));
         HIPCHK(herr(b.h_count.alloc(2, hipHostMallocDefault)));
@@ -1052,6 +1064,61 @@ int launch_events(oww_ctx* h, const StepArgs& a, const oww_ctx::EventBuf& buf, b
         Timed t(h, 7);
         hipLaunchKernelGGL(owe::events_write_kernel, dim3(h->evt_blocks), dim3(owe::EV_WG), 0, h->stream, p);
     }
+    if (h->aud_evt > 0) {                        // the stored records' audio: the ring already holds the detecting chunk (launch_audio_append)
+        owa::EventsAudioParams q{};
+        q.count = buf.d_count; q.rec = buf.d_rec; q.ring = h->d_aring; q.counter = h->d_acount; q.snap = buf.d_asnap;
+        q.S = h->S; q.capacity = h->evt_cap; q.event_chunks = (uint32_t)h->aud_evt; q.ring_chunks = (uint32_t)h->aud_ring;
+        const long long waves = (long long)h->evt_cap * h->aud_evt;           // the most chunk copies a call can have
+        const int grid = (int)std::min<long long>(owa::AU_EVENT_WGS, (waves + owa::AU_WG / 64 - 1) / (owa::AU_WG / 64));
+        Timed t(h, 7);
+        hipLaunchKernelGGL(owa::events_audio_kernel, dim3(grid), dim3(owa::AU_WG), 0, h->stream, q);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- per-stream audio rings (oww_audio_configure; kernels in owwhip_audio.h, arithmetic in owwhip_audio_host.h).  Like events not
+//      part of launch_step, hence of no captured graph and of no borrowed-stream entry (oww_embed, oww_embed_clips, oww_mel, the commit
+//      probes): the entry points that advance streams call launch_audio_append where they call launch_events, in front of it.
+bool audio_on(const oww_ctx* h) { return h->aud_ring > 0; }
+
+int alloc_audio(oww_ctx* h) {
+    const uint64_t nb = owa::ring_bytes(h->S, h->aud_ring);
+    if (nb / sizeof(int16_t) > (uint64_t)SIZE_MAX / sizeof(int16_t) || h->d_aring.alloc((size_t)(nb / sizeof(int16_t))))
+        return fail(OWW_ENOMEM, "oww_audio_configure: out of device memory for %llu bytes of audio rings (%d streams x %d chunks x %llu)",
+                    (unsigned long long)nb, h->S, h->aud_ring, (unsigned long long)owa::kChunkBytes);
+    if (h->d_acount.alloc((size_t)h->S))
+        return fail(OWW_ENOMEM, "oww_audio_configure: out of device memory for %llu bytes of chunk counters", (unsigned long long)owa::counter_bytes(h->S));
+    HIPCHK(hipMemsetAsync(h->d_aring, 0, (size_t)nb, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_acount, 0, (size_t)owa::counter_bytes(h->S), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// The call's k chunks per stream, [S][k * 1280] at d_src (any 2-byte alignment), into the rings of the streams that took part, behind
+// the step's launches on the handle's stream.  d_src = nullptr: zero the rings and counters of ids[n] (nullptr: of every stream).
+int launch_audio_append(oww_ctx* h, const StepArgs& a, const int16_t* d_src, int k, bool any_on = true) {
+    if (!any_on) return 0;
+    owa::AppendParams p{};
+    p.src = d_src; p.ring = h->d_aring; p.counter = h->d_acount; p.stream_on = a.on;
+    p.ids = a.lists ? a.gl[0] : nullptr; p.n = a.lists ? a.gn[0] : h->S;
+    p.S = h->S; p.k = (uint32_t)k; p.ring_chunks = (uint32_t)h->aud_ring;
+    if (p.n <= 0) return 0;
+    const dim3 grid((p.n + owa::AU_WG / 64 - 1) / (owa::AU_WG / 64));
+    {
+        Timed t(h, 7);
+        if (reinterpret_cast<uintptr_t>(d_src) & 15) hipLaunchKernelGGL(owa::audio_append_kernel<false>, grid, dim3(owa::AU_WG), 0, h->stream, p);
+        else hipLaunchKernelGGL(owa::audio_append_kernel<true>, grid, dim3(owa::AU_WG), 0, h->stream, p);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int audio_reset(oww_ctx* h, const int* d_ids, int n) {
+    owa::AppendParams p{};
+    p.ring = h->d_aring; p.counter = h->d_acount; p.ids = d_ids; p.n = d_ids ? n : h->S;
+    p.S = h->S; p.ring_chunks = (uint32_t)h->aud_ring;
+    hipLaunchKernelGGL(owa::audio_append_kernel<true>, dim3((p.n + owa::AU_WG / 64 - 1) / (owa::AU_WG / 64)), dim3(owa::AU_WG), 0, h->stream, p);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1629,6 +1696,10 @@ int state_layout(oww_ctx* h) {
     const oww_ctx::Ingest& ing = h->ing;
     if (ing.ready && ing.tab.Hpad_max) flat(ing.d_hist, (size_t)ing.tab.Hpad_max / 2, (size_t)ing.tab.Hpad_max / 2);   // oww_ingest history (int16 pairs)
     if (ing.ready && ing.mixed) flat(ing.d_cls, 1, 1);                     // ... and the stream's class: one word in a 16-byte piece of its own
+    if (audio_on(h)) {                                                     // the ring as it lies, then the counter in a 16-byte piece of its own
+        flat(h->d_aring, owa::ring_words(h->aud_ring), owa::ring_words(h->aud_ring));
+        flat(h->d_acount, owa::kCounterWords, owa::kCounterWords);
+    }
     h->st_flat_quads = off / 4;
     auto group = [&](float* live, int spg, int ppr, bool inter, uint32_t block_words) -> int {
         const int R = ppr >= 4 ? 1 : 4 / ppr;
@@ -1659,7 +1730,7 @@ int state_layout(oww_ctx* h) {
         fp = fp_mix(fp, hh.blob.data(), hh.blob.size() * sizeof(float));
     }
     fp = fp_mix(fp, h->vad_blob.data(), h->vad_blob.size() * sizeof(float));
-    h->st_fp = owi::fingerprint(fp, ing.ready, ing.mixed, ing.tab);
+    h->st_fp = owa::fingerprint(owi::fingerprint(fp, ing.ready, ing.mixed, ing.tab), h->aud_ring);
     if (!h->d_st_flat) HIPCHK(herr(h->d_st_flat.alloc(h->st_flat.size())));
     HIPCHK(copy_sync(h->d_st_flat, h->st_flat.data(), h->st_flat.size() * sizeof(ows::FlatSection), hipMemcpyHostToDevice));
     h->st_ready = true;
@@ -1923,6 +1994,7 @@ int oww_commit(oww_ctx* h) {
     if (int rc = build_nets(*h, h->NL, h->TR, h->generic_hmax)) return rc;
     if (h->evt_rows > h->TR)                     // (the ring is known only now)
         return fail(OWW_EINVAL, "oww_events_configure: feature_rows = %d exceeds the handle's feature ring (%d rows)", h->evt_rows, h->TR);
+    if (int rc = owa::commit_check(h->aud_evt, h->evt_cap)) return rc;
     // ---- f16-split family: per-layer activation scales from a calibration run on the exact-fp32 kernels (calibrate_hx) ----
     CommitClock clk(h->hx ? "f16-split" : "family");
     HxCalib cal;
@@ -1966,6 +2038,7 @@ int oww_commit(oww_ctx* h) {
     if (int rc = derive_reset_state(h, cal, clk)) return rc;
     if (h->bank_K > 0) if (int rc = alloc_bank(h)) return rc;
     if (h->vpool_cap > 0) if (int rc = alloc_verifiers(h)) return rc;
+    if (audio_on(h)) if (int rc = alloc_audio(h)) return rc;
     if (events_on(h)) if (int rc = alloc_events(h)) return rc;
     h->committed = true;
     return OWW_OK;
@@ -1995,6 +2068,7 @@ int oww_reset(oww_ctx* h, const int32_t* stream_ids, int32_t n, const float* ini
                            stream_ids ? h->d_ids : nullptr, stream_ids ? n : h->S);
         HIPCHK(hipGetLastError());
     }
+    if (audio_on(h)) if (int rc = audio_reset(h, stream_ids ? (const int*)h->d_ids : nullptr, n)) return rc;   // utils.py:174
     std::vector<int> slots;                      // head bank: Model.reset() empties every prediction buffer, the subscriptions stay
     if (h->bank_K > 0) {
         if (!stream_ids) for (int i = 0; i < h->S * h->bank_K; ++i) slots.push_back(i);
@@ -2041,6 +2115,7 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
             d_call = h->d_long;
         }
         if (int rc = launch_step_long(h, a, d_call, n_chunks)) return rc;
+        if (audio_on(h)) if (int rc = launch_audio_append(h, a, d_call, n_chunks)) return rc;
         if (events_on(h)) { if (int rc = launch_events(h, a, h->evt_sync)) return rc; h->evt_cur = &h->evt_sync; }
         // (host PCM: the caller's buffer is free to change when this returns)
         return deliver_scores(h, scores, scores_on_device, !scores_on_device || !pcm_on_device, "oww_step");
@@ -2067,6 +2142,7 @@ int oww_step(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t n_chunks
     } else {
         if (int rc = launch_step(h, a, d_pcm, n_chunks)) return rc;
     }
+    if (audio_on(h)) if (int rc = launch_audio_append(h, a, d_pcm, n_chunks)) return rc;
     if (events_on(h)) { if (int rc = launch_events(h, a, h->evt_sync)) return rc; h->evt_cur = &h->evt_sync; }
     return deliver_scores(h, scores, scores_on_device, scores && !scores_on_device, "oww_step");
     OWW_GUARD_END
@@ -2098,6 +2174,7 @@ int oww_step_masked(oww_ctx* h, const int16_t* pcm, int pcm_on_device, const uin
     }
     if (n_act != 0)                                             // (nobody takes part: nothing moves)
         if (int rc = launch_step(h, a, d_pcm, 1)) return rc;
+    if (audio_on(h)) if (int rc = launch_audio_append(h, a, d_pcm, 1, n_act != 0)) return rc;
     if (events_on(h)) { if (int rc = launch_events(h, a, h->evt_sync, n_act != 0)) return rc; h->evt_cur = &h->evt_sync; }
     return deliver_scores(h, scores, scores_on_device, scores && !scores_on_device, "oww_step_masked");
     OWW_GUARD_END
@@ -2200,6 +2277,8 @@ static int submit_impl(oww_ctx* h, const SubmitSource& src, const uint8_t* strea
         if (int rc = launch_ingest(h, sl.d_mix, src.row_bytes, OWW_CHUNK, stream_on ? (const uint8_t*)h->d_on : nullptr, h->ing.d_out, src.geo)) return rc;
     if (n_act != 0)
         if (int rc = launch_step(h, a, mix ? (const int16_t*)h->ing.d_out : (const int16_t*)sl.d_pcm, n_chunks)) return rc;
+    if (audio_on(h))                                   // from the slot's own buffer (or the ingest staging), on the compute stream
+        if (int rc = launch_audio_append(h, a, mix ? (const int16_t*)h->ing.d_out : (const int16_t*)sl.d_pcm, n_chunks, n_act != 0)) return rc;
     const oww_ctx::EventBuf& eb = h->evt_slot[h->n_submit & 1];
     if (events_on(h)) { if (int rc = launch_events(h, a, eb, n_act != 0)) return rc; h->evt_cur = nullptr; }
     const size_t nb = (size_t)h->S * h->NL * sizeof(float);
@@ -2983,6 +3062,62 @@ const oww_event* oww_events_dev(const oww_ctx* h, const int32_t** count_dev) {
 }
 
 const float* oww_event_features_dev(const oww_ctx* h) { return h && h->committed && events_on(h) ? h->evt_sync.d_snap : nullptr; }
+
+int oww_audio_configure(oww_ctx* h, int32_t ring_chunks, int32_t event_chunks) {
+    OWW_GUARD_BEGIN
+    if (int rc = owa::configure_check(h != nullptr, h && h->committed, ring_chunks, event_chunks)) return rc;
+    h->aud_ring = ring_chunks; h->aud_evt = event_chunks;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_get_audio(oww_ctx* h, const int32_t* stream_ids, int32_t n, int32_t n_chunks, int16_t* out, int out_on_device, uint32_t* counts) {
+    OWW_GUARD_BEGIN
+    if (int rc = owa::ready_check("oww_get_audio", h != nullptr, h && h->committed, h ? h->aud_ring : 0)) return rc;
+    if (int rc = owa::get_audio_check(h->S, h->aud_ring, stream_ids, n, n_chunks, out, out_on_device)) return rc;
+    if (n == 0) return OWW_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint64_t nb = owa::gather_bytes(n, n_chunks);
+    if (grow(h, h->d_aids, (size_t)n) != hipSuccess || grow(h, h->d_acnt, (size_t)n) != hipSuccess)
+        return fail(OWW_ENOMEM, "oww_get_audio: out of device memory for a list of %d streams", n);
+    if (!out_on_device && grow(h, h->d_aout, (size_t)(nb / sizeof(int16_t))) != hipSuccess)
+        return fail(OWW_ENOMEM, "oww_get_audio: out of device memory for %llu bytes", (unsigned long long)nb);
+    HIPCHK(copy_async(h->d_aids, stream_ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    owa::GatherParams p{};
+    p.ring = h->d_aring; p.counter = h->d_acount; p.ids = h->d_aids; p.out = out_on_device ? out : (int16_t*)h->d_aout; p.counts = h->d_acnt;
+    p.S = h->S; p.n_chunks = (uint32_t)n_chunks; p.ring_chunks = (uint32_t)h->aud_ring;
+    const int per_launch = std::max(1, (1 << 25) / n_chunks);          // (a launch stays below 2^32 threads: 2^25 waves)
+    for (int at = 0; at < n; at += per_launch) {
+        const int m = std::min(n - at, per_launch);
+        owa::GatherParams q = p;
+        q.ids = p.ids + at; q.out = p.out + (size_t)at * n_chunks * OWW_CHUNK; q.counts = p.counts + at;
+        hipLaunchKernelGGL(owa::audio_gather_kernel, dim3(m, n_chunks), dim3(64), 0, h->stream, q);
+    }
+    HIPCHK(hipGetLastError());
+    if (!out_on_device) HIPCHK(copy_async(out, h->d_aout, (size_t)nb, hipMemcpyDeviceToHost, h->stream));
+    if (counts) HIPCHK(copy_async(counts, h->d_acnt, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));           // behind every queued step; the host list was a copy source, host buffers are complete
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_get_event_audio(oww_ctx* h, int32_t first, int32_t n, int16_t* out, int out_on_device) {
+    OWW_GUARD_BEGIN
+    if (int rc = owa::ready_check("oww_get_event_audio", h != nullptr, h && h->committed, h ? h->aud_ring : 0)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    int cnt[2] = {0, 0};
+    if (h->aud_evt > 0) if (int rc = event_counts(h, cnt)) return rc;
+    if (int rc = owa::event_audio_check(h->aud_evt, first, n, std::min(cnt[0], h->evt_cap), out, out_on_device)) return rc;
+    if (n == 0) return OWW_OK;
+    const size_t per = (size_t)h->aud_evt * OWW_CHUNK;
+    HIPCHK(copy_async(out, h->evt_cur->d_asnap + (size_t)first * per, (size_t)n * per * sizeof(int16_t),
+                      out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+const int16_t* oww_event_audio_dev(const oww_ctx* h) { return h && h->committed && h->aud_evt > 0 ? h->evt_sync.d_asnap.get() : nullptr; }
 
 int oww_bank_configure(oww_ctx* h, int32_t slots, int32_t capacity) {
     OWW_GUARD_BEGIN

@@ -29,6 +29,7 @@ LAYER_NEW_SHAPES = ([(8, 32, 24)] * 3 + [(4, 16, 48)] * 4 + [(4, 8, 72)] * 4 + [
 EVENT_DTYPE = np.dtype([("stream", np.int32), ("column", np.int32), ("bank_id", np.int32), ("score", np.float32),
                         ("frame", np.uint32), ("feature_index", np.int32), ("reserved", np.int32, (2,))])
 EVENT_CAPACITY_MAX = 1 << 20
+AUDIO_RING_MAX = 1024    # oww_audio_configure: ring_chunks 1 .. 1024
 KERNEL_CLASSES = ["mel", "stageA", "stageB", "stageC", "stageD", "stageE", "heads", "postproc", "vad_front", "vad_lstm"]
 
 
@@ -152,6 +153,39 @@ def events_from_scores(scores, bank_scores=None, bank_sub=None, thresholds=0.5, 
     return out
 
 
+class audio_ring_model:
+    """The definition of the per-stream audio rings (include/owwhip.h: oww_audio_configure / oww_get_audio / oww_get_event_audio),
+    restated on host arrays: for users and tests without a GPU, and the reference the device path is held to -- never used by the
+    product path.  Per stream the last ring_chunks chunks of 1280 samples and a uint32 counter of the chunks received since its reset."""
+
+    def __init__(self, n_streams: int, ring_chunks: int):
+        self.n_streams, self.ring_chunks = int(n_streams), int(ring_chunks)
+        self.buf = np.zeros((self.n_streams, self.ring_chunks * CHUNK), dtype=np.int16)      # oldest sample first
+        self.counts = np.zeros(self.n_streams, dtype=np.uint32)
+
+    def append(self, pcm, participating=None) -> None:
+        """One call: pcm int16 [S, k * 1280]; participating [S] (None = every stream).  Streams that sit out keep every bit."""
+        pcm = np.asarray(pcm)
+        if pcm.dtype != np.int16 or pcm.ndim != 2 or pcm.shape[0] != self.n_streams or pcm.shape[1] == 0 or pcm.shape[1] % CHUNK:
+            raise ValueError(f"pcm must be int16 [{self.n_streams}, 1280*k], got {pcm.dtype} {pcm.shape}")
+        on = np.ones(self.n_streams, dtype=bool) if participating is None else np.asarray(participating) != 0
+        joined = np.concatenate([self.buf[on], pcm[on]], axis=1)
+        self.buf[on] = joined[:, -self.ring_chunks * CHUNK:]                     # of a call longer than the ring the last ring_chunks
+        self.counts[on] += np.uint32(pcm.shape[1] // CHUNK)
+
+    def reset(self, stream_ids=None) -> None:
+        ids = slice(None) if stream_ids is None else np.asarray(stream_ids, dtype=np.int64)
+        self.buf[ids] = 0
+        self.counts[ids] = 0
+
+    def last(self, stream_ids, n_chunks: int) -> np.ndarray:
+        """int16 [n, n_chunks * 1280]: the newest n_chunks chunks of the listed streams, oldest first; what a stream has not received
+        since its reset reads as zero (the buffer starts, and resets to, zeros)."""
+        if not 1 <= int(n_chunks) <= self.ring_chunks:
+            raise ValueError(f"n_chunks must lie in 1 .. {self.ring_chunks}, got {n_chunks}")
+        return self.buf[np.asarray(stream_ids, dtype=np.int64)][:, -int(n_chunks) * CHUNK:].copy()
+
+
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -193,6 +227,21 @@ def check_event_config(event_capacity, event_features, feature_ring: int) -> Tup
     return cap, rows
 
 
+def check_audio_config(audio_chunks, event_audio, event_capacity) -> Tuple[int, int]:
+    """The limits of oww_audio_configure, checked before the library is touched -> (ring_chunks, event_chunks)."""
+    for name, v in (("audio_chunks", audio_chunks), ("event_audio", event_audio)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    ring, ev = int(audio_chunks), int(event_audio)
+    if ring < 0 or ring > AUDIO_RING_MAX:
+        raise ValueError(f"audio_chunks must lie in 0 .. {AUDIO_RING_MAX} (0 = no audio), got {ring}")
+    if ev < 0 or ev > ring:
+        raise ValueError(f"event_audio must lie in 0 .. audio_chunks = {ring}, got {ev}")
+    if ev > 0 and int(event_capacity) <= 0:
+        raise ValueError("event_audio needs event_capacity > 0")
+    return ring, ev
+
+
 class StreamEngine:
     """One GPU, S streams.  `heads` maps model name -> head dict (see weights.synthetic_head).
 
@@ -204,7 +253,8 @@ class StreamEngine:
                  device: int = 0, max_chunks: int = 1, use_mfma: int = 3, debug_layers: bool = False,
                  feature_ring: int = 0, hip_stream: int = 0, vad: Optional[dict] = None, vad_threshold: float = 0.0,
                  calibration_pcm: Union[np.ndarray, str, None] = "default", bank_slots: int = 0, bank_capacity: int = 0,
-                 verifier_capacity: int = 0, event_capacity: int = 0, event_features: int = 0):
+                 verifier_capacity: int = 0, event_capacity: int = 0, event_features: int = 0, audio_chunks: int = 0,
+                 event_audio: int = 0):
         """`vad`: weights of the on-device voice-activity stand-in network (weights.synthetic_vad layout); when given, every
         step also runs it on the frame's two 640-sample sub-frames and gates the scores with `vad_threshold` (model.py:366-381).
         `calibration_pcm` (use_mfma = 3): audio of the deployment's domain, int16 [n, k * 1280], that oww_commit adds to its built-in
@@ -215,9 +265,13 @@ class StreamEngine:
         `verifier_capacity` > 0: a pool of that many per-stream custom verifiers (oww_verifier_configure; verifier_add /
         assign_verifiers below).
         `event_capacity` > 0: detections are reported as ordered device-side events, up to that many per call, each with a snapshot of
-        the stream's last `event_features` feature rows (oww_events_configure; set_event_thresholds / events / event_features below)."""
+        the stream's last `event_features` feature rows (oww_events_configure; set_event_thresholds / events / event_features below).
+        `audio_chunks` > 0: every stream's last `audio_chunks` chunks of 16 kHz audio stay on the device (the reference's
+        raw_data_buffer: 125), and every event carries its stream's last `event_audio` chunks (oww_audio_configure; audio /
+        event_audio below)."""
         self.event_capacity, self.event_rows = check_event_config(event_capacity, event_features,
                                                                   max([16] + [int(h["T"]) for h in heads.values()] + [int(feature_ring)]))
+        self.audio_chunks, self.event_audio_chunks = check_audio_config(audio_chunks, event_audio, event_capacity)
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self._inflight: List[np.ndarray] = []
@@ -269,6 +323,8 @@ class StreamEngine:
                 _lib.check(self._lib.oww_verifier_configure(self._h, self.verifier_capacity))
             if self.event_capacity > 0:
                 _lib.check(self._lib.oww_events_configure(self._h, self.event_capacity, self.event_rows))
+            if self.audio_chunks > 0:
+                _lib.check(self._lib.oww_audio_configure(self._h, self.audio_chunks, self.event_audio_chunks))
             _lib.check(self._lib.oww_commit(self._h))
             if vad_threshold:
                 _lib.check(self._lib.oww_set_vad_threshold(self._h, float(vad_threshold)))
@@ -746,6 +802,33 @@ class StreamEngine:
         cnt = C.c_void_p()
         rec = self._lib.oww_events_dev(self._h, C.byref(cnt))
         return int(rec or 0), int(cnt.value or 0), int(self._lib.oww_event_features_dev(self._h) or 0)
+
+    # ---- per-stream audio rings (include/owwhip.h: oww_audio_configure / oww_get_audio / oww_get_event_audio) ----
+    check_audio_config = staticmethod(check_audio_config)
+
+    def audio(self, stream_ids: Sequence[int], n_chunks: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(int16 [n, n_chunks * 1280], uint32 counts [n]): the newest n_chunks chunks of the listed streams, oldest first, zero where
+        a stream has received less since its reset, and each stream's chunk counter.  Runs behind every queued step."""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32).ravel()
+        out = np.empty((ids.size, max(int(n_chunks), 0) * CHUNK), dtype=np.int16)
+        counts = np.zeros(ids.size, dtype=np.uint32)
+        _lib.check(self._lib.oww_get_audio(self._h, _ptr(ids), ids.size, int(n_chunks), _ptr(out), 0, _ptr(counts)))
+        return out, counts
+
+    def event_audio(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """int16 [n, event_audio * 1280]: the audio behind stored events first .. first + n - 1 of the call events() refers to, ending
+        with the detecting chunk; n = None: up to the last stored event."""
+        if n is None:
+            n_stored = C.c_int32(0)
+            _lib.check(self._lib.oww_get_events(self._h, None, 0, C.byref(n_stored), None))
+            n = max(0, n_stored.value - int(first))
+        out = np.empty((int(n), self.event_audio_chunks * CHUNK), dtype=np.int16)
+        _lib.check(self._lib.oww_get_event_audio(self._h, int(first), int(n), _ptr(out), 0))
+        return out
+
+    def event_audio_dev_ptr(self) -> int:
+        """Device address of the last synchronous step's audio snapshots; 0 where there is none."""
+        return int(self._lib.oww_event_audio_dev(self._h) or 0)
 
     def event_label(self, record) -> Union[str, int]:
         """The score column's name for a fixed-head event ("name" or "name:j" for output j of a multi-output head), the bank id for a

@@ -29,7 +29,7 @@ from typing import Callable, DefaultDict, Dict, List, Optional, Sequence, Tuple,
 import numpy as np
 
 from . import weights as W
-from .engine import CHUNK, EMB_DIM, StreamEngine, check_event_config
+from .engine import CHUNK, EMB_DIM, StreamEngine, check_audio_config, check_event_config
 
 # openwakeword/__init__.py:26-60 (names only; the files are release assets that are not in the checkout)
 MODELS = {name: {"model_path": os.path.join(os.path.dirname(os.path.abspath(__file__)), "resources", "models",
@@ -630,15 +630,19 @@ class BatchedModel:
                  device: int = 0, max_chunks: int = 1, hip_stream: int = 0, vad_weights: Optional[dict] = None,
                  vad_threshold: float = 0.0, use_mfma: Optional[int] = None, calibration_pcm="default",
                  embedding_model_path: str = "", melspec_model_path: str = "", bank_slots: int = 0, bank_capacity: int = 1024,
-                 verifier_capacity: int = 0, event_capacity: int = 0, event_features: int = 0):
+                 verifier_capacity: int = 0, event_capacity: int = 0, event_features: int = 0, audio_chunks: int = 0,
+                 event_audio: int = 0):
         # bank_slots > 0: a head bank (bank_add / subscribe / bank_scores): every stream is scored by the bank heads it subscribed to,
         # up to bank_slots of them, beside the fixed `wakeword_models` (which may then be empty)
         # verifier_capacity > 0: a pool of per-stream custom verifiers (add_verifier / assign_verifiers / assign_bank_verifiers)
         # event_capacity > 0: detections as ordered device-side events, each with the stream's last event_features feature rows
         # (set_event_thresholds / events / event_features / event_label)
+        # audio_chunks > 0: every stream's last audio_chunks chunks of 16 kHz audio stay on the device (the reference's raw_data_buffer
+        # holds 125), every event with its stream's last event_audio chunks (audio / event_audio)
         if not wakeword_models and int(bank_slots) <= 0:
             raise ValueError("BatchedModel needs wakeword_models, or a head bank (bank_slots > 0)")
         check_event_config(event_capacity, event_features, 1 << 30)       # (the ring itself is known once the heads are loaded)
+        check_audio_config(audio_chunks, event_audio, event_capacity)
         self._weights = weights
         self._debounce_frames = 0
         # same weight resolution as Model: real .onnx files (heads AND the shared embedding network) unless synthetic
@@ -671,8 +675,9 @@ class BatchedModel:
                                   vad=vad_weights, vad_threshold=vad_threshold, calibration_pcm=calibration_pcm,
                                   bank_slots=int(bank_slots), bank_capacity=int(bank_capacity),
                                   verifier_capacity=int(verifier_capacity), event_capacity=int(event_capacity),
-                                  event_features=int(event_features))
+                                  event_features=int(event_features), audio_chunks=int(audio_chunks), event_audio=int(event_audio))
         self.event_capacity, self.event_rows = int(event_capacity), int(event_features)
+        self.audio_chunks, self.event_audio_chunks = int(audio_chunks), int(event_audio)
         self.bank_slots = int(bank_slots)
         self.verifier_capacity = int(verifier_capacity)
         self._model_T = {n: int(h["T"]) for n, h in heads.items()}
@@ -787,6 +792,18 @@ class BatchedModel:
         """float32 [n, event_features, 96]: the feature window behind stored events first .. first + n - 1, taken on the device in the
         step that detected (what Model._get_positive_prediction_frames collects, model.py:428-476)."""
         return self.engine.event_features(first, n)
+
+    def audio(self, stream_ids: Sequence[int], n_chunks: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(int16 [n, n_chunks * 1280], uint32 counts [n]): the newest n_chunks chunks of 16 kHz audio of the listed streams, oldest
+        first, zero where a stream has received less since its reset, and the chunks each has received (needs audio_chunks > 0)."""
+        return self.engine.audio(stream_ids, n_chunks)
+
+    def event_audio(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """int16 [n, event_audio * 1280]: the audio behind stored events first .. first + n - 1, taken on the device in the detecting
+        step and ending with the detecting chunk."""
+        return self.engine.event_audio(first, n)
+
+    check_audio_config = staticmethod(check_audio_config)
 
     def event_label(self, record) -> Union[str, int]:
         """The label of a fixed-head event (as in `labels`), the bank id of a bank event."""
