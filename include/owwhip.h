@@ -611,6 +611,46 @@ int  oww_embed_clips(oww_ctx* h, const int16_t* pcm, int32_t pcm_on_device, int3
                      float* out, int32_t out_on_device);
 int  oww_head(oww_ctx* h, int32_t head, const float* features, int32_t B, float* out);
 
+/* ---- dense scoring: every window of a feature sequence through the fixed heads -----------------------------------------------------
+ * The reference scores recordings as well as live streams: train.py:874-879 slices hours of precomputed features [N][96] into every
+ * T-row window (stride 1) and runs the head over all of them, Model._get_positive_prediction_frames (model.py:428-479, behind
+ * examples/mine_false_positives.py) keeps the windows of long audio that score above a threshold, utils.bulk_predict
+ * (utils.py:502-536) walks files chunk by chunk.  These entries score all windows of B sequences in one call.
+ *   oww_score_shape     t_max = the largest T over the handle's fixed heads, n_win = n_rows - t_max + 1; either pointer may be NULL.
+ *   oww_score_features  feats fp32 [B][n_rows][96] (host, or a 16-byte aligned device pointer with feats_on_device) ->
+ *                       out fp32 [B][n_win][n_labels] (host or device).  Replaces train.py:874-879 and model.py:313-317 per window.
+ *   oww_score_clips     int16 clips [B][n] -> the same scores over the clips' oww_embed_clips embeddings (n_rows = that entry's n_out),
+ *                       which never leave the device; emb_out (may be NULL): the embeddings [B][n_out][96] exactly as
+ *                       oww_embed_clips returns them (host, or device with emb_on_device).  Replaces model.py:428-479 and the
+ *                       per-chunk loop of utils.py:502-536.
+ * Window alignment: window w of sequence b ends at row w + t_max - 1, and a head of window length T reads rows
+ * [w + t_max - T, w + t_max), its own last T rows -- what the heads of one live handle see at one instant.  Every entry of `out` is
+ * defined.  n_rows < t_max: OWW_EINVAL.
+ * Values: out[b][w][col] is the raw head output, what model_prediction_function returns (model.py:313-317); in the fp16-split family
+ * (use_mfma = 3) and every other family it is bit for bit what oww_head returns for that head on the materialised window.  No first-5
+ * zeroing, patience, debounce, verifier or VAD gate: those are properties of a live stream.  Fixed heads only -- the bank is not
+ * scored, and a handle without fixed heads returns OWW_EINVAL.
+ * Last window: train.py:875's range(0, N - T, 1) drops the last window; these entries return all n_rows - T + 1, and out[:, :-1] is
+ * the reference's set.
+ * Independence: a window's scores depend on its rows alone -- not on B, on the other sequences or on where the window falls in a
+ * tile -- so a long array may be scored in chunks that overlap by t_max - 1 rows, with identical bits.
+ * Live streams: oww_score_features borrows no stream state (streams, rings, events, audio rings and the captured graph are
+ * untouched); oww_score_clips parks and restores streams [0, B) exactly as oww_embed_clips does (B <= n_streams, one mel clamp floor
+ * per clip).
+ * Paths: narrow fp16-split groups (<= 64 hidden units, 1-4 nets, gated pairs included: every released binary model) run the
+ * sliding-window kernel (owwhip_dense.h) at every T, one launch per pass of one or two nets: it stages, scales and splits each feature
+ * row once per tile of 256 windows (128 beyond T = 113 for one net, 72 for two) instead of once per window; every other head (wide
+ * and generic nets, recurrent heads, use_mfma 0 / 1 / 2) has its windows gathered on the device into a slab of at most 256 MiB and
+ * scored as oww_head scores them.
+ * Errors and accounting: OWW_ESTATE before oww_commit; bad arguments OWW_EINVAL with the handle untouched; sizes in 64-bit
+ * arithmetic, what does not fit is OWW_ENOMEM with the bytes in the message; the sticky range flag is raised and reported as by
+ * oww_head (position unknown).  The heads launches are timed under kernel class 6, the fallback's window gather under class 7. */
+int  oww_score_shape(oww_ctx* h, int32_t n_rows, int32_t* n_win, int32_t* t_max);
+int  oww_score_features(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows,
+                        float* out, int out_on_device);
+int  oww_score_clips(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t B, int32_t n,
+                     float* out, int out_on_device, float* emb_out, int emb_on_device);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 /* AudioFeatures.get_features (utils.py:454-460): last T rows of stream sid's feature ring, oldest first */
 int  oww_get_features(oww_ctx* h, int32_t sid, int32_t T, float* out);

@@ -29,6 +29,7 @@
 #include "owwhip_state.h"
 #include "owwhip_events.h"
 #include "owwhip_audio.h"
+#include "owwhip_dense.h"
 
 using namespace owk;
 using namespace owp;
@@ -1872,6 +1873,115 @@ int state_check_headers(const oww_ctx* h, const uint32_t* hdr /*[n][8]*/, int n)
 }  // namespace
 
 // =====================================================================================================
+// ---- dense scoring (oww_score_*; owwhip_dense.h, owwhip_dense_host.h) ------------------------------------------------------------------
+namespace {
+
+int dense_t_max(const oww_ctx* h) {
+    int t = 0;
+    for (const HeadHost& hh : h->heads) t = std::max(t, hh.T);
+    return t;
+}
+
+// (the attribute call stays in front of the timed window: with an idle device the start event is stamped at once, and host time
+// between it and the launch would be booked as kernel time)
+template <int NN, int WG>
+int launch_dense_nn(oww_ctx* h, int slots, dim3 grid, int lds, const owh::DenseParams& q) {
+    const dim3 block(64 * WG);
+    hipStream_t st = h->stream;
+#define OWW_DENSE_GO(NB)                                                                                                                     \
+    do {                                                                                                                                     \
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(owh::heads_dense_kernel<NN, NB, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
+        Timed t(h, 6);                                                                                                                       \
+        hipLaunchKernelGGL((owh::heads_dense_kernel<NN, NB, WG>), grid, block, lds, st, q);                                                      \
+    } while (0)
+    if (slots >= 4) OWW_DENSE_GO(4);
+    else if (slots == 3) OWW_DENSE_GO(3);
+    else OWW_DENSE_GO(2);
+#undef OWW_DENSE_GO
+    return 0;
+}
+
+// every window of d_feats [B][n_rows][96] through every fixed head -> d_out [B][n_win][NL]; both on the device.  Narrow fp16-split
+// groups take the sliding-window kernel, one launch per pass of one or two nets (owd::split_passes, owd::geometry); every other head
+// -- wide and generic nets, recurrent heads, the fp32 and LDS-tiled families, a T whose rows do not fit the LDS -- has its windows
+// gathered into a bounded slab and scored by run_heads as external features, slab after slab.  OWW_DENSE_PATH=ext (A/B aid) sends
+// every head down the second path.
+int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_rows, float* d_out) {
+    const int t_max = dense_t_max(h);
+    const int64_t nw = owd::n_win(n_rows, t_max);
+    const char* env = getenv("OWW_DENSE_PATH");
+    const bool slide = h->hx && h->mfma && !(env && !strcmp(env, "ext"));
+    // d_out is not cleared (it may be gigabytes): every fixed head is scored below, by a sliding pass or by the fallback, and the
+    // heads' n_out columns are exactly the NL columns of a row (build_nets lays them side by side), so every entry is written
+    std::vector<char> covered(h->heads.size(), 0);
+    if (slide) {
+        for (const FastGroup& g : h->groups) {
+            if (g.ht != 4 || g.n_nets > 4 || !owd::geometry(owd::kMaxPassNets, g.T).slots) continue;      // (two nets fit: so does one)
+            int role[4], head[4], pass[4][2];
+            for (int i = 0; i < g.n_nets; ++i) { role[i] = g.hx_net[i].role; head[i] = g.hx_net[i].head; }
+            const int n_pass = owd::split_passes(role, head, g.n_nets, pass);
+            const int off = (int)owd::row_offset(t_max, g.T);
+            for (int k = 0; k < n_pass; ++k) {
+                const int n0 = pass[k][0], nn = pass[k][1];
+                const owd::Geometry geo = owd::geometry(nn, g.T);
+                owh::DenseParams q{};
+                q.feats = d_feats + (size_t)off * 96; q.seq_stride = (long long)n_rows * 96; q.n_rows = n_rows - off;
+                q.n_win = (int)nw; q.tiles = (int)owd::tiles_per_seq(nw, geo.waves); q.T = g.T;
+                q.w1hx = g.d_w1hx + (size_t)n0 * 4 * 2 * 256; q.chunk_stride = g.n_nets * 4 * 2 * 256;
+                for (int i = 0; i < nn; ++i) q.net[i] = g.hx_net[n0 + i];
+                q.out = d_out; q.NL = h->NL; q.range_flag = h->d_range; q.fscale = std::ldexp(1.0f, h->hx_efeat);
+                const dim3 grid((unsigned)((int64_t)B * q.tiles));
+                int rc = 0;
+                if (geo.waves == owd::kWavesBig) rc = nn == 1 ? launch_dense_nn<1, owd::kWavesBig>(h, geo.slots, grid, (int)geo.staged, q)
+                                                              : launch_dense_nn<2, owd::kWavesBig>(h, geo.slots, grid, (int)geo.staged, q);
+                else rc = nn == 1 ? launch_dense_nn<1, owd::kWavesSmall>(h, geo.slots, grid, (int)geo.staged, q)
+                                  : launch_dense_nn<2, owd::kWavesSmall>(h, geo.slots, grid, (int)geo.staged, q);
+                if (rc) return rc;
+            }
+            for (int ni : g.nets) covered[h->nets[ni].head] = 1;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    // what is left, one launch unit at a time: a fast group the kernel above did not take is ONE run_heads launch for all its heads
+    // (run_heads launches the whole group of the head it is asked for), a generic or recurrent head is a launch of its own
+    int64_t budget = owd::kSlabBytes;
+    if (const char* mb = getenv("OWW_DENSE_SLAB_MB")) budget = std::max<int64_t>(1, atoll(mb)) << 20;      // (A/B aid: one slab for everything)
+    int64_t slab_bytes = 0;
+    for (size_t hi = 0; hi < h->heads.size(); ++hi)
+        if (!covered[hi]) slab_bytes = std::max(slab_bytes, owd::slab((int64_t)B * nw, h->heads[hi].T, budget).bytes);
+    if (!slab_bytes) return 0;
+    DevBuf<float> d_slab;
+    if (d_slab.alloc((size_t)slab_bytes / sizeof(float))) return fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of window slab)", fn, (long long)slab_bytes);
+    int rc = 0;
+    for (size_t hi = 0; hi < h->heads.size() && !rc; ++hi) {
+        if (covered[hi]) continue;
+        const int T = h->heads[hi].T;
+        const owd::Slab sl = owd::slab((int64_t)B * nw, T, budget);
+        for (int64_t s = 0; s < sl.n_slabs && !rc; ++s) {
+            const int64_t first = s * sl.windows, n = std::min<int64_t>(sl.windows, (int64_t)B * nw - first);
+            owh::GatherParams gp{};
+            gp.feats = d_feats + (size_t)owd::row_offset(t_max, T) * 96; gp.seq_stride = (long long)n_rows * 96;
+            gp.n_win = nw; gp.first = first; gp.n = n; gp.T = T; gp.slab = d_slab;
+            {
+                Timed t(h, 7);
+                const int64_t pieces = n * T * 24;
+                hipLaunchKernelGGL(owh::dense_gather_kernel, dim3((unsigned)std::min<int64_t>((pieces + 255) / 256, 256 * 16)), dim3(256), 0, h->stream, gp);
+            }
+            rc = run_heads(h, step_args(h), (int)n, false, d_slab, (int)hi, d_out + (size_t)first * h->NL, 0);
+        }
+        covered[hi] = 1;
+        if (h->mfma)
+            for (const FastGroup& g : h->groups) {
+                bool has = false;
+                for (int ni : g.nets) has |= h->nets[ni].head == (int)hi;
+                if (has) for (int ni : g.nets) covered[h->nets[ni].head] = 1;      // (scored by the launches above, same T)
+            }
+    }
+    return drained(h, rc);          // (the slab goes with this scope)
+}
+
+}  // namespace
+
 extern "C" {
 
 int oww_abi_version(void) { return OWW_ABI_VERSION; }
@@ -2881,6 +2991,64 @@ int oww_head(oww_ctx* h, int32_t head, const float* features, int32_t B, float* 
     for (int b = 0; b < B; ++b)
         for (int o = 0; o < hh.n_out; ++o) out[(size_t)b * hh.n_out + o] = raw[(size_t)b * h->NL + hh.out_col + o];
     return range_check(h, "oww_head");
+    OWW_GUARD_END
+}
+
+// ---- dense scoring: oww_score_shape, oww_score_features, oww_score_clips (helpers: score_device above)
+int oww_score_shape(oww_ctx* h, int32_t n_rows, int32_t* n_win, int32_t* t_max) {
+    OWW_GUARD_BEGIN
+    if (int rc = owd::ready_check("oww_score_shape", h != nullptr, h && h->committed, h ? (int)h->heads.size() : 0)) return rc;
+    const int tm = dense_t_max(h);
+    if (int rc = owd::shape_check("oww_score_shape", n_rows, tm)) return rc;
+    if (n_win) *n_win = (int32_t)owd::n_win(n_rows, tm);
+    if (t_max) *t_max = tm;
+    return 0;
+    OWW_GUARD_END
+}
+
+int oww_score_features(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows, float* out, int out_on_device) {
+    OWW_GUARD_BEGIN
+    const char* fn = "oww_score_features";
+    if (int rc = owd::ready_check(fn, h != nullptr, h && h->committed, h ? (int)h->heads.size() : 0)) return rc;
+    const int t_max = dense_t_max(h);
+    if (int rc = owd::features_check(fn, feats, feats_on_device, B, n_rows, t_max, h->NL, out, out_on_device)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int64_t nw = owd::n_win(n_rows, t_max);
+    const uint64_t fb = owd::feats_bytes(B, n_rows), ob = owd::out_bytes(B, nw, h->NL);
+    DevBuf<float> d_f, d_o;
+    if ((!feats_on_device && d_f.alloc(fb / 4)) || (!out_on_device && d_o.alloc(ob / 4)))
+        return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features, %llu bytes of scores)", fn, (unsigned long long)fb, (unsigned long long)ob);
+    if (!feats_on_device && copy_async(d_f, feats, fb, hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
+    float* o = out_on_device ? out : d_o.get();
+    if (int rc = score_device(h, fn, feats_on_device ? feats : d_f.get(), B, n_rows, o)) return drained(h, rc);
+    if (!out_on_device && copy_async(out, d_o, ob, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: D2H failed", fn));
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
+    return range_check(h, fn);
+    OWW_GUARD_END
+}
+
+int oww_score_clips(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t B, int32_t n, float* out, int out_on_device, float* emb_out,
+                    int emb_on_device) {
+    OWW_GUARD_BEGIN
+    const char* fn = "oww_score_clips";
+    if (int rc = owd::ready_check(fn, h != nullptr, h && h->committed, h ? (int)h->heads.size() : 0)) return rc;
+    const int t_max = dense_t_max(h);
+    if (int rc = owd::clips_check(fn, pcm, B, n, h->Spad, t_max, h->NL, out)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int n_rows = (int)owd::clip_rows(n);
+    const int64_t nw = owd::n_win(n_rows, t_max);
+    const uint64_t fb = owd::feats_bytes(B, n_rows), ob = owd::out_bytes(B, nw, h->NL);
+    DevBuf<float> d_f, d_o;
+    if (d_f.alloc(fb / 4) || (!out_on_device && d_o.alloc(ob / 4)))
+        return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features, %llu bytes of scores)", fn, (unsigned long long)fb, (unsigned long long)ob);
+    if (int rc = oww_embed_clips(h, pcm, pcm_on_device, B, n, d_f, 1)) return rc;      // parks and restores streams [0, B); drained on return
+    float* o = out_on_device ? out : d_o.get();
+    if (int rc = score_device(h, fn, d_f, B, n_rows, o)) return drained(h, rc);
+    if (!out_on_device && copy_async(out, d_o, ob, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: D2H failed", fn));
+    if (emb_out && copy_async(emb_out, d_f, fb, emb_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+        return drained(h, fail(OWW_EHIP, "%s: embedding copy failed", fn));
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
+    return range_check(h, fn);
     OWW_GUARD_END
 }
 

@@ -1,0 +1,223 @@
+// owwhip_dense.h -- dense scoring (include/owwhip.h: oww_score_features, oww_score_clips): every T-row window of a feature sequence
+// through the fp16-split heads.  Consecutive windows share T - 1 of their T rows, so a workgroup that scores a TILE of consecutive
+// windows stages the tile's rows once -- scaled by fscale and split into f16 hi / lo by the very split_pair<false> the heads kernel
+// uses -- and every k-step reads its B operand from LDS instead of loading and splitting its own rows: 1 / T of the feature traffic
+// and of the splits of heads_hx_kernel on the materialised windows.
+//
+// heads_dense_kernel<NN, NBUF, WG>: one workgroup = WG waves x 2 position tiles of 16 = 32 WG consecutive windows of one sequence
+// (WG = 8: 256 windows, or 4 where the rows of 256 do not fit), NN <= 2 narrow nets (HT = 4 hidden tiles) of one fast group -- a PASS
+// (owd::split_passes) -- on the group's packed weights as they are (FastGroup::d_w1hx, hx_net): a pass reads its own nets' blocks of
+// every k-step chunk.  At full size the heads launches are bound by the weight stream L2 -> LDS, once per workgroup; 256 windows per
+// workgroup halve it against heads_hx_kernel's 128, which the compact rows in LDS make room for.
+//  * staging: rows [w0, w0 + 32 WG + T - 1) of the sequence (clamped to its last row: the windows that would read beyond it are not
+//    stored) -> LDS, row stride owd::kRowWords = 100 words, unit (c, j) of a row = 8 hi halves | 8 lo halves (owd::unit_word): the 16
+//    positions of a tile, one row apart, read 16 distinct groups of 4 banks.
+//  * k loop: k-step ks = (row tr = ks / 3, features 32 (ks % 3) ..) of every window; position pos of tile t of wave v reads staged row
+//    32 v + 16 t + pos + tr.  The weight chunks stream L2 -> LDS through a ring of NBUF slots, each its OWN LDS object (hslot<>, see
+//    heads_hx_kernel: one array would make every read of the current slot wait for the chunk just issued).  The same MFMAs in the same
+//    order as heads_hx_kernel -- per k-step and pair of hidden tiles (A hi, B hi), (A hi, B lo), (A lo, B hi), tile 0 then tile 1 --
+//    so an accumulator holds bit for bit what heads_hx_kernel's holds for the materialised window.
+//  * barrier discipline: heads_hx_kernel's wait for chunk ks + 1 rides on its feature loads (younger than the chunk, in-order return).
+//    Here no VMEM load follows the chunks, so the wait is counted: every wave issues exactly 8 NN / WG DMA instructions per chunk
+//    (issue_chunk_uniform), D = NBUF - 1 chunks fly ahead, and at the end of k-step ks "at most (D - 1) x 8 NN / WG outstanding" means this
+//    wave's part of chunk ks + 1 has landed; the bare s_barrier (no release fence: it would be vmcnt(0)) publishes the other waves'
+//    parts.  The slot refilled in k-step ks is the one k-step ks - 1 read: every wave passed that k-step's barrier with its LDS reads
+//    returned (lgkmcnt(0)).  The last D k-steps wait vmcnt(0).
+//  * tail: net64_score, the function form of heads_hx_kernel's narrow tail that the bank kernel already runs bit for bit, then the
+//    gating of heads_hx_kernel.  No post-processing: dense scores are raw head outputs.
+// A workgroup's LDS (108 KB of rows at T = 16 plus the ring) leaves no room for a second one on the CU, so the ring is as deep as fits
+// (owd::geometry: 4, 3 or 2 slots) -- chunks in flight and the second wave of each SIMD, not neighbours, hide the L2 round trip.
+//
+// dense_gather_kernel: the fallback's window materialisation, [n][T][96] into a slab that owk / owh head kernels score as external
+// features (run_heads ext) -- every head form the sliding kernel does not cover, bit-identical to oww_head by construction.
+#pragma once
+#include "owwhip_dense_host.h"
+#include "owwhip_hx.h"
+
+namespace owh {
+
+struct DenseParams {
+    const float* feats;         // [B][..][96]: row 0 of window 0 of this group (the group's row offset t_max - T applied)
+    long long seq_stride;       // floats from one sequence to the next
+    int n_rows;                 // rows of a sequence from `feats` on
+    int n_win, tiles;           // windows and tiles per sequence
+    int T;
+    const float* w1hx;          // the pass's first block of k-step 0 in the group's [T*3 ksteps][nets*4 ct][2 part][64][8 halves]
+    int chunk_stride;           // floats from one k-step's chunk to the next (the whole group's chunk)
+    HeadHxNet net[4];
+    float* out;                 // [B][n_win][NL]
+    int NL;
+    int* range_flag;
+    float fscale;
+};
+
+template <int NN, int NBUF, int WG>
+__global__ __launch_bounds__(64 * WG, 1) void heads_dense_kernel(DenseParams p) {
+    using namespace owr;
+    constexpr int NT = 2;                       // position tiles of 16 windows per wave, as heads_hx_kernel
+    constexpr int TILE = 16 * NT * WG;
+    constexpr int NCT = NN * 4;                 // hidden tiles of 16
+    constexpr int NBLK = NCT * 2;               // 1 KB blocks per k-step chunk
+    constexpr int CHUNK = NBLK * 256;           // floats
+    constexpr int D = NBUF - 1;                 // chunks in flight ahead of the one being consumed
+    constexpr int KDMA = NBLK / WG;             // DMA instructions per wave and chunk
+    static_assert(NBLK % WG == 0 && (D - 1) * KDMA < 64, "the counted wait assumes the same issue count in every wave");
+    extern __shared__ __attribute__((aligned(16))) float dense_rows[];
+    const int lane = threadIdx.x & 63, pos = lane & 15, j = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int KST = p.T * 3;                    // (>= 3 > D - 1: every prologue chunk exists)
+    const int b = blockIdx.x / p.tiles, w0 = (blockIdx.x - b * p.tiles) * TILE;
+#pragma unroll
+    for (int c = 0; c < D; ++c) issue_chunk_uniform<NBLK, WG>(p.w1hx + (size_t)c * p.chunk_stride, hslot_at<CHUNK, NBUF - 1>(c), wave, lane);
+
+    // ---- stage the tile's rows: scale, split, store in B-operand order (four units per thread in flight)
+    {
+        const float* seq = p.feats + (size_t)b * p.seq_stride;
+        const int NU = (TILE + p.T - 1) * 12;
+        const float fsc = p.fscale;
+        for (int u0 = threadIdx.x; u0 < NU; u0 += 4 * 64 * WG) {
+            f32x4 r[4][2];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int u = min(u0 + q * 64 * WG, NU - 1);
+                const int row = u / 12, unit = u - row * 12;
+                const float* src = seq + (size_t)min(w0 + row, p.n_rows - 1) * 96 + unit * 8;
+                r[q][0] = *reinterpret_cast<const f32x4*>(src);
+                r[q][1] = *reinterpret_cast<const f32x4*>(src + 4);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int u = u0 + q * 64 * WG;
+                if (u >= NU) continue;
+                const int row = u / 12, unit = u - row * 12;
+                const Op o = split_pair<false>(r[q][0] * fsc, r[q][1] * fsc);
+                float* dst = dense_rows + owd::unit_word(row, unit);
+                *reinterpret_cast<f16x8*>(dst) = o.h;
+                *reinterpret_cast<f16x8*>(dst + 4) = o.l;
+            }
+        }
+    }
+    __syncthreads();                            // rows staged, prologue chunks landed (the fence drains them: once per tile)
+
+    f32x4 acc[NCT][NT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // B operand of k-step ks: position pos of tile t reads unit kstep_unit(ks, j) of staged row 16 (NT wave + t) + pos + ks / 3
+    auto load_b = [&](int ks, Op (&bo)[NT]) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const float* src = dense_rows + owd::unit_word(16 * (NT * wave + t) + pos + ks / 3, owd::kstep_unit(ks, j));
+            bo[t].h = *reinterpret_cast<const f16x8*>(src);
+            bo[t].l = *reinterpret_cast<const f16x8*>(src + 4);
+        }
+    };
+    // The staged rows never change behind the prologue, so the B operand of k-step ks + 1 is read DURING k-step ks, beside its last
+    // pair of hidden tiles, and is in registers when the barrier releases the waves -- as heads_hx_kernel's, whose split sits behind
+    // the previous k-step's MFMAs.  Read at the top of its own k-step it put an LDS round trip in the open behind every barrier, for
+    // all waves of the CU at once, 3 T times per tile.
+    Op bcur[NT], bnext[NT];
+    load_b(0, bcur);
+    // one k-step: ring slot u (static), prefetch of k-step ks + D into slot (u + D) % NBUF, MFMAs, B operand of k-step ks + 1
+    auto kstep = [&](int ks, auto uc, auto always) {
+        constexpr int u = decltype(uc)::value;
+        constexpr bool ALWAYS = decltype(always)::value;        // main loop: every k-step of the group prefetches and has a successor
+        const float* cur = hslot_at<CHUNK, NBUF - 1>(u);
+        if (ALWAYS || ks + D < KST) {                           // slot of k-step ks-1: every wave passed the last barrier
+            constexpr int un = (u + D) % NBUF;
+            issue_chunk_uniform<NBLK, WG>(p.w1hx + (size_t)(ks + D) * p.chunk_stride, hslot_at<CHUNK, NBUF - 1>(un), wave, lane);
+        }
+        // A operands one pair of hidden tiles ahead of their MFMAs, as heads_hx_kernel (OWH_HEADS_APIPE)
+        f16x8 A[2][4];
+#pragma unroll
+        for (int bk = 0; bk < 4; ++bk) A[0][bk] = lds_h(cur, bk, lane);
+#pragma unroll
+        for (int c2 = 0; c2 < NCT; c2 += 2) {
+            const int pc = (c2 / 2) & 1;
+            if (c2 + 2 < NCT) {
+#pragma unroll
+                for (int bk = 0; bk < 4; ++bk) A[pc ^ 1][bk] = lds_h(cur, (c2 + 2) * 2 + bk, lane);
+            } else if (ALWAYS || ks + 1 < KST) load_b(ks + 1, bnext);        // (flies under the last pair's MFMAs)
+            __builtin_amdgcn_sched_barrier(0);                  // (the reads stay in front of this pair's MFMAs)
+#pragma unroll
+            for (int part = 0; part < 3; ++part) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    acc[c2][t] = OWH_MFMA(part == 2 ? A[pc][1] : A[pc][0], part == 1 ? bcur[t].l : bcur[t].h, acc[c2][t]);
+                    acc[c2 + 1][t] = OWH_MFMA(part == 2 ? A[pc][3] : A[pc][2], part == 1 ? bcur[t].l : bcur[t].h, acc[c2 + 1][t]);
+                }
+            }
+        }
+        if (ALWAYS || ks + 1 < KST) {
+            __builtin_amdgcn_sched_barrier(0);
+            // this wave's part of chunk ks + 1 has landed when at most the chunks ks + 2 .. ks + D are outstanding
+            if constexpr (ALWAYS) wait_vmcnt<(D - 1) * KDMA>();
+            else wait_vmcnt<0>();
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // (lgkmcnt(0): this wave's reads of the slot, and bnext, have returned)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) bcur[t] = bnext[t];
+        }
+    };
+    auto group = [&](int ks0, auto always) {                    // NBUF consecutive k-steps, slots 0 .. NBUF-1
+        constexpr bool ALWAYS = decltype(always)::value;
+        static_for_while<0, NBUF>([&](auto uc) {
+            constexpr int U = decltype(uc)::value;
+            if (!ALWAYS && ks0 + U >= KST) return false;
+            kstep(ks0 + U, uc, always);
+            return true;
+        });
+    };
+    int ks0 = 0;
+    for (; ks0 + NBUF - 1 + D < KST; ks0 += NBUF) group(ks0, std::true_type{});
+    for (; ks0 < KST; ks0 += NBUF) group(ks0, std::false_type{});        // the last D .. NBUF + D - 1 k-steps
+
+    lanemask_t bad = 0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) nan_guard(bad, acc[0][t][0]);      // a feature beyond the f16 range
+    float score[NN][NT];
+#pragma unroll
+    for (int n = 0; n < NN; ++n) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            f32x4 h1[4] = {acc[4 * n][t], acc[4 * n + 1][t], acc[4 * n + 2][t], acc[4 * n + 3][t]};
+            score[n][t] = net64_score<NN>(p.net[n], h1, bad, j, lane);
+        }
+    }
+    // ---- gating + store (one lane group per window: j == 0)
+    if (j == 0) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int w = w0 + wave * 16 * NT + t * 16 + pos;
+            if (w >= p.n_win) continue;
+            float* o = p.out + ((size_t)b * p.n_win + w) * p.NL;
+#pragma unroll
+            for (int n = 0; n < NN; ++n) {
+                if (p.net[n].role != 0) continue;
+                float sc = score[n][t];
+                if (n + 1 < NN && p.net[n + 1].role == 1 && p.net[n + 1].head == p.net[n].head && sc > 0.5f) sc = score[n + 1][t];
+                o[p.net[n].out_col] = sc;
+            }
+        }
+    }
+    raise_range_flag(bad, p.range_flag);        // (position unknown: a window is no stream)
+}
+
+// windows [first, first + n) of the flattened [B][n_win] window list -> slab [n][T][96]; one 16-byte piece per thread and turn
+struct GatherParams {
+    const float* feats;         // the head's row offset applied
+    long long seq_stride;       // floats
+    long long n_win, first, n;
+    int T;
+    float* slab;
+};
+__global__ void dense_gather_kernel(GatherParams p) {
+    const long long per = (long long)p.T * 24, total = p.n * per;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long win = i / per, q = i - win * per;
+        const long long gw = p.first + win, b = gw / p.n_win, w = gw - b * p.n_win;
+        reinterpret_cast<owr::f32x4*>(p.slab)[i] = *reinterpret_cast<const owr::f32x4*>(p.feats + b * p.seq_stride + w * 96 + q * 4);
+    }
+}
+
+}  // namespace owh

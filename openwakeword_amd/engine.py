@@ -984,6 +984,49 @@ class StreamEngine:
         _lib.check(self._lib.oww_head(self._h, idx, _ptr(f), f.shape[0], _ptr(out)))
         return out
 
+    # ---- dense scoring (include/owwhip.h: oww_score_shape / oww_score_features / oww_score_clips)
+    def score_shape(self, n_rows: int) -> Tuple[int, int]:
+        """(n_win, t_max) for sequences of n_rows feature rows: t_max = the largest window length over the fixed heads,
+        n_win = n_rows - t_max + 1."""
+        n_win, t_max = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.oww_score_shape(self._h, int(n_rows), C.byref(n_win), C.byref(t_max)))
+        return int(n_win.value), int(t_max.value)
+
+    def score_features(self, feats: np.ndarray) -> np.ndarray:
+        """Every window of feature sequences through the fixed heads (train.py:874-879): [B, n_rows, 96] -> raw head outputs
+        [B, n_win, n_labels].  Window w ends at row w + t_max - 1 and each head reads its own last T rows; all n_rows - t_max + 1
+        windows are returned (out[:, :-1] is the set train.py:875 scores).  No post-processing, no stream state touched."""
+        f = np.ascontiguousarray(feats, dtype=np.float32)
+        if f.ndim == 2:
+            f = f[None]
+        if f.ndim != 3 or f.shape[2] != EMB_DIM:
+            raise ValueError(f"score_features expects [B, n_rows, 96], got {f.shape}")
+        B, n_rows, _ = f.shape
+        n_win, _ = self.score_shape(n_rows)
+        out = np.empty((B, n_win, self.n_labels), dtype=np.float32)
+        _lib.check(self._lib.oww_score_features(self._h, _ptr(f), 0, B, n_rows, _ptr(out), 0))
+        return out
+
+    def score_clips(self, pcm: np.ndarray, return_features: bool = False):
+        """int16 clips [B, n] -> [B, n_win, n_labels]: score_features over the clips' embed_clips embeddings, which stay on the device
+        (with return_features: also the embeddings [B, n_out, 96], exactly what embed_clips returns).  Borrows streams [0, B) as
+        embed_clips does.  These are embed_clips-path scores (one mel clamp floor per clip, no seeded feature ring)."""
+        pcm = np.ascontiguousarray(pcm)
+        if pcm.dtype != np.int16 or pcm.ndim != 2:
+            raise ValueError("score_clips expects a 2-D int16 array [B, samples]")
+        B, n = pcm.shape
+        if B < 1 or B > self.n_streams_padded:
+            raise ValueError(f"between 1 and {self.n_streams_padded} clips per call (the handle's stream count)")
+        F = (n - 512) // 160 + 1
+        if n < 512 or F < 76:
+            raise ValueError("clips are shorter than one 76-frame embedding window (12512 samples, 782 ms)")
+        n_rows = (F - 76) // 8 + 1
+        n_win, _ = self.score_shape(n_rows)
+        out = np.empty((B, n_win, self.n_labels), dtype=np.float32)
+        emb = np.empty((B, n_rows, EMB_DIM), dtype=np.float32) if return_features else None
+        _lib.check(self._lib.oww_score_clips(self._h, _ptr(pcm), 0, B, n, _ptr(out), 0, _ptr(emb) if return_features else None, 0))
+        return (out, emb) if return_features else out
+
     # ---- introspection
     def get_features(self, sid: int, T: int = 16) -> np.ndarray:
         out = np.empty((T, EMB_DIM), dtype=np.float32)

@@ -718,6 +718,19 @@ class BatchedModel:
         self.engine.set_postproc(pat, thr, frames)
         self._debounce_frames = frames
 
+    def score_clips(self, clips: np.ndarray, return_features: bool = False):
+        """Dense scores of equally long clips: int16 [B, n] -> {label: [B, n_win]}, one raw score per 80 ms window position of every
+        clip (model.py:428-479 scans long audio like this, one window at a time).  Window w ends at embedding row w + t_max - 1 of the
+        clip, t_max the longest window of the fixed models.  Batches larger than the stream count run in several calls.  These are
+        embed_clips-path scores: one mel clamp floor per clip, no seeded feature ring and no post-processing -- not the streaming path's.
+        With return_features also the embeddings [B, n_out, 96]."""
+        clips = np.ascontiguousarray(np.atleast_2d(clips))
+        cap = self.engine.n_streams_padded
+        parts = [self.engine.score_clips(clips[lo:lo + cap], return_features=True) for lo in range(0, clips.shape[0], cap)]
+        raw = np.concatenate([p[0] for p in parts], axis=0)
+        out = {lab: raw[:, :, c] for lab, c in zip(self.labels, self._keep)}
+        return (out, np.concatenate([p[1] for p in parts], axis=0)) if return_features else out
+
     # ---- head bank: per-stream subscriptions to wake-word heads (include/owwhip.h: oww_bank_*) ----
     def bank_add(self, model: Union[str, dict], weights: Union[str, dict, None] = None) -> int:
         """Add a head to the bank while the streams run -> bank id.  `model` is resolved like an entry of `wakeword_models`: a

@@ -182,3 +182,69 @@ def bulk_predict(file_paths, wakeword_models, prediction_function: str = "predic
         return {f: results[s] for s, f in enumerate(file_paths)}
     finally:
         bm.close()
+
+
+def _dense_model(wakeword_models, n_streams: int, **kw):
+    """(BatchedModel-like scorer, owned): `wakeword_models` is a list of model names / paths (a BatchedModel is built and owned), or an
+    object that already scores densely (a BatchedModel, or anything with its `engine`, `labels`, `_keep` and `_model_T`)."""
+    if hasattr(wakeword_models, "engine"):
+        return wakeword_models, False
+    from .model import BatchedModel
+    return BatchedModel(max(int(n_streams), 1), list(wakeword_models), weights=kw.get("weights"), device=int(kw.get("device", 0))), True
+
+
+def dense_chunks(n_rows: int, t_max: int, chunk_rows: int):
+    """The chunks `score_feature_file` walks: (first window, one past the last window, first row, one past the last row) of each.
+    Consecutive chunks overlap by t_max - 1 rows, so every window lies whole in exactly one of them."""
+    n_rows, t_max, chunk_rows = int(n_rows), int(t_max), int(chunk_rows)
+    if chunk_rows < t_max:
+        raise ValueError(f"chunk_rows = {chunk_rows} holds no window (t_max = {t_max})")
+    n_win = n_rows - t_max + 1
+    step = chunk_rows - (t_max - 1)
+    return [(lo, min(lo + step, n_win), lo, min(lo + step, n_win) + t_max - 1) for lo in range(0, max(n_win, 0), step)]
+
+
+def score_feature_file(path_or_array, wakeword_models, chunk_rows: int = 1 << 18, **kw) -> dict:
+    """The scan of train.py:874-879 on the device: every T-row window (stride 1) of precomputed features `[N, 96]` -- a `.npy` path, read
+    through a memmap, or an array -- through the models -> {label: [n_win] raw scores}, n_win = N - t_max + 1.  Window w ends at row
+    w + t_max - 1 and each model reads its own last T rows; train.py:875's `range(0, N - T, 1)` drops the last window, so `[:-1]` of a
+    model's scores is the reference's set.  The array is scored `chunk_rows` rows at a time, chunks overlapping by t_max - 1 rows:
+    a window's scores depend on its rows alone, so the result does not depend on `chunk_rows`.
+    `wakeword_models`: model names / paths (keyword arguments `weights`, `device` as for `Model`), or a `BatchedModel`."""
+    feats = np.load(path_or_array, mmap_mode="r") if isinstance(path_or_array, (str, os.PathLike)) else np.asarray(path_or_array)
+    if feats.ndim != 2 or feats.shape[1] != EMB_DIM:
+        raise ValueError(f"features must be [N, 96], got {feats.shape}")
+    bm, own = _dense_model(wakeword_models, 1, **kw)
+    try:
+        n_win, t_max = bm.engine.score_shape(feats.shape[0])
+        raw = np.empty((n_win, bm.engine.n_labels), dtype=np.float32)
+        for w0, w1, r0, r1 in dense_chunks(feats.shape[0], t_max, chunk_rows):
+            raw[w0:w1] = bm.engine.score_features(np.ascontiguousarray(feats[r0:r1], dtype=np.float32)[None])[0]
+        return {lab: raw[:, c] for lab, c in zip(bm.labels, bm._keep)}
+    finally:
+        if own:
+            bm.close()
+
+
+def mine_windows(clips, wakeword_models, threshold: float = 0.5, **kw) -> dict:
+    """The feature windows of equally long clips `int16 [B, n]` that score at least `threshold` -> {label: [N, T, 96]}, the shape
+    `Model._get_positive_prediction_frames(return_type="features")` returns (model.py:428-479; examples/mine_false_positives.py).
+    Scores come from `score_clips`; the windows are cut on the host from the embeddings that call returns: window w of a model with
+    window length T is rows [w + t_max - T, w + t_max) of its clip.  These are embed_clips-path scores -- one mel clamp floor per
+    clip, no seeded feature ring -- not the streaming path's, so a clip's first t_max - 1 positions (which the reference scores on a
+    ring still holding its seed) are not scored.  Multiclass models: a window is kept under every class label that reaches the threshold."""
+    clips = np.ascontiguousarray(np.atleast_2d(clips))
+    bm, own = _dense_model(wakeword_models, min(clips.shape[0], 64), **kw)
+    try:
+        scores, emb = bm.score_clips(clips, return_features=True)
+        t_max = max(bm._model_T.values())
+        out = {}
+        for lab, c in zip(bm.labels, bm._keep):
+            T = bm._model_T[bm._parent[c]]
+            b, w = np.nonzero(scores[lab] >= threshold)
+            idx = (w + (t_max - T))[:, None] + np.arange(T)[None, :]
+            out[lab] = emb[b[:, None], idx] if b.size else np.zeros((0, T, EMB_DIM), dtype=np.float32)
+        return out
+    finally:
+        if own:
+            bm.close()
