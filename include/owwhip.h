@@ -628,8 +628,8 @@ int  oww_head(oww_ctx* h, int32_t head, const float* features, int32_t B, float*
  * defined.  n_rows < t_max: OWW_EINVAL.
  * Values: out[b][w][col] is the raw head output, what model_prediction_function returns (model.py:313-317); in the fp16-split family
  * (use_mfma = 3) and every other family it is bit for bit what oww_head returns for that head on the materialised window.  No first-5
- * zeroing, patience, debounce, verifier or VAD gate: those are properties of a live stream.  Fixed heads only -- the bank is not
- * scored, and a handle without fixed heads returns OWW_EINVAL.
+ * zeroing, patience, debounce, verifier or VAD gate: those are properties of a live stream.  Fixed heads only -- bank heads are
+ * scored by oww_bank_score_* below -- and a handle without fixed heads returns OWW_EINVAL.
  * Last window: train.py:875's range(0, N - T, 1) drops the last window; these entries return all n_rows - T + 1, and out[:, :-1] is
  * the reference's set.
  * Independence: a window's scores depend on its rows alone -- not on B, on the other sequences or on where the window falls in a
@@ -650,6 +650,44 @@ int  oww_score_features(oww_ctx* h, const float* feats, int feats_on_device, int
                         float* out, int out_on_device);
 int  oww_score_clips(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t B, int32_t n,
                      float* out, int out_on_device, float* emb_out, int emb_on_device);
+
+/* ---- dense scoring over the head bank: validate many heads on one corpus --------------------------------------------------------------
+ * Before a newly trained head goes live its false-accept rate is checked on a negative corpus.  The reference does this for a list of
+ * candidate models: train.py:225-258 (_select_best_model) runs every model of self.best_models over the false-positive validation
+ * features, which train.py:874-879 slices into every T-row window, and train.py:100 counts the windows with pred >= 0.5 (divided by
+ * the hours at train.py:513-522).  These entries score every window of B sequences with a LIST of bank heads in one call.
+ *   oww_bank_score_shape     t_max = the largest T over the LISTED bank heads, n_win = n_rows - t_max + 1; either pointer may be NULL.
+ *   oww_bank_score_features  feats fp32 [B][n_rows][96] (host, or a 16-byte aligned device pointer with feats_on_device) ->
+ *                            out fp32 [B][n_win][n_ids] (host, or a 16-byte aligned device pointer): out[b][w][i] is the raw sigmoid
+ *                            output of bank head bank_ids[i] on window w.
+ *   oww_bank_score_stats     the same scores reduced on the device, inside the kernel that computes them; the matrix (1,024 heads x 8
+ *                            hours: 1.5 GB) is never written.  Host arrays, each [B][n_ids]:
+ *                              count[b][i]  = #{w : out[b][w][i] >= thresholds[i]}   (thresholds NULL = 0.5, train.py:100's default)
+ *                              max[b][i]    = the maximum over w;   argmax[b][i] = the smallest w that attains it
+ *                            bit for bit what numpy computes from the matrix, whatever the scheduling: integer atomics on a key
+ *                            that orders like the score (a sigmoid output is >= +0) with the complement of w below it.
+ * Window alignment: as oww_score_features with t_max taken over the listed heads -- window w ends at row w + t_max - 1 and head i of
+ * length T_i reads rows [w + t_max - T_i, w + t_max).  Values: bit for bit what the same net scores as a fixed head through
+ * oww_score_features; no first-5 zeroing, patience, verifier or VAD gate.  Duplicate ids give duplicate columns.  train.py:875 drops
+ * the last window; these entries do not.
+ * Live streams: the entries run on the handle's stream and read and write nothing of the live streams: subscriptions, bank raw
+ * scores, scores and rings, the routing table, events and the captured graph are untouched.
+ * Paths: the listed narrow heads (<= 64 hidden units) run as ONE launch of heads_dense_bank_kernel (owwhip_dense.h): grid = (sequence x
+ * tile) x head slices, a workgroup stages its tile's rows once and walks the heads of its slice (OWW_DENSE_BANK_HPW overrides the
+ * heads per workgroup: an A/B aid).  Wide heads (65-128 units) and everything with OWW_DENSE_PATH=ext take the fallback: window
+ * gather into the bounded slab, heads_bank_kernel as oww_bank_add's self-test launches it, a small kernel from the slab's scores into
+ * the column or the statistics -- the same bits.
+ * Errors (nothing has moved): OWW_ESTATE before oww_commit or without a bank; OWW_EINVAL for n_ids < 1, an id that is not a live
+ * bank head (named in the message), n_rows < t_max, a NaN threshold, a null or misaligned device pointer; sizes in 64-bit arithmetic,
+ * what does not fit is OWW_ENOMEM with the bytes in the message.  The sticky range flag is raised and reported as by oww_head
+ * (position unknown); when it is up, the statistics of that call are not defined.  Heads launches are timed under kernel class 6,
+ * gathers and the fallback's scatter / reduction under class 7. */
+int  oww_bank_score_shape(oww_ctx* h, const int32_t* bank_ids, int32_t n_ids, int32_t n_rows, int32_t* n_win, int32_t* t_max);
+int  oww_bank_score_features(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows,
+                             const int32_t* bank_ids, int32_t n_ids, float* out, int out_on_device);
+int  oww_bank_score_stats(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows,
+                          const int32_t* bank_ids, int32_t n_ids, const float* thresholds,
+                          int32_t* count, float* max, int32_t* argmax);
 
 /* ---- introspection ------------------------------------------------------------------------------ */
 /* AudioFeatures.get_features (utils.py:454-460): last T rows of stream sid's feature ring, oldest first */

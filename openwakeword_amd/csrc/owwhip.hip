@@ -1980,6 +1980,128 @@ int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_
     return drained(h, rc);          // (the slab goes with this scope)
 }
 
+// ---- dense scoring over the head bank (oww_bank_score_*; owwhip_dense.h: heads_dense_bank_kernel, owwhip_dense_bank_host.h) ----------
+template <int WG>
+int launch_dense_bank(oww_ctx* h, int slots, dim3 grid, int lds, const owh::DenseBankParams& q) {
+    const dim3 block(64 * WG);
+    hipStream_t st = h->stream;
+#define OWW_DENSE_BANK_GO(NB)                                                                                                                \
+    do {                                                                                                                                     \
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(owh::heads_dense_bank_kernel<NB, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
+        Timed t(h, 6);                                                                                                                       \
+        hipLaunchKernelGGL((owh::heads_dense_bank_kernel<NB, WG>), grid, block, lds, st, q);                                                    \
+    } while (0)
+    if (slots >= 4) OWW_DENSE_BANK_GO(4);
+    else if (slots == 3) OWW_DENSE_BANK_GO(3);
+    else OWW_DENSE_BANK_GO(2);
+#undef OWW_DENSE_BANK_GO
+    return 0;
+}
+
+// T of every live bank head by id (0 = empty slot): what owd::bank_ids_check reads
+std::vector<int> bank_live_T(const oww_ctx* h) {
+    std::vector<int> t(h->bank.size(), 0);
+    for (size_t i = 0; i < h->bank.size(); ++i) if (h->bank[i].live) t[i] = h->bank[i].T;
+    return t;
+}
+
+// every window of d_feats [B][n_rows][96] through the listed bank heads (checked: live; t_max their largest T) -> d_out [B][n_win][n_ids]
+// or, d_out == nullptr, into the statistics d_count / d_key [B][n_ids] (cleared by the caller) against d_thr / thr [n_ids].  The narrow
+// heads (ht 4) run as ONE launch of heads_dense_bank_kernel on the slice plan; wide heads, whatever the plan refuses and, with
+// OWW_DENSE_PATH=ext, everything take the fallback head by head: windows gathered into the bounded slab, heads_bank_kernel in its ext
+// mode (the launch of oww_bank_add's self-test), dense_bank_slab_kernel from the slab's scores into the column or the statistics.
+int bank_score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_rows, const int32_t* ids, int n_ids, int t_max, float* d_out,
+                      const float* d_thr, const float* thr, int* d_count, unsigned long long* d_key) {
+    const int64_t nw = owd::n_win(n_rows, t_max);
+    const char* env = getenv("OWW_DENSE_PATH");
+    const bool slide = !(env && !strcmp(env, "ext"));
+    const float fscale = std::ldexp(1.0f, h->hx_efeat);
+    std::vector<owh::DenseBankItem> items;
+    int t_s = 0;
+    for (int i = 0; i < n_ids; ++i)
+        if (slide && h->bank[ids[i]].ht == 4) { items.push_back(owh::DenseBankItem{ids[i], i}); t_s = std::max(t_s, h->bank[ids[i]].T); }
+    const owd::BankPlan plan = items.empty() ? owd::BankPlan{} : owd::bank_plan((int64_t)items.size(), B, nw, t_s, owd::bank_hpw_env());
+    if (!plan.hpw) items.clear();
+    std::vector<char> covered((size_t)n_ids, 0);
+    DevBuf<owh::DenseBankItem> d_items;
+    if (!items.empty()) {
+        if (d_items.alloc(items.size())) return fail(OWW_ENOMEM, "%s: out of device memory (%zu bytes of head list)", fn, items.size() * sizeof(owh::DenseBankItem));
+        if (copy_async(d_items, items.data(), items.size() * sizeof(owh::DenseBankItem), hipMemcpyHostToDevice, h->stream) != hipSuccess)
+            return fail(OWW_EHIP, "%s: H2D failed", fn);
+        const int off = (int)owd::row_offset(t_max, t_s);
+        owh::DenseBankParams q{};
+        q.feats = d_feats + (size_t)off * 96; q.seq_stride = (long long)n_rows * 96; q.n_rows = n_rows - off;
+        q.n_win = (int)nw; q.seq_tiles = (int)plan.seq_tiles; q.tiles = (int)plan.tiles; q.t_s = t_s;
+        q.heads = h->d_bank_heads; q.items = d_items; q.n_items = (int)items.size(); q.hpw = plan.hpw;
+        q.out = d_out; q.n_ids = n_ids; q.thr = d_thr; q.count = d_count; q.key = d_key; q.range_flag = h->d_range; q.fscale = fscale;
+        const dim3 grid((unsigned)plan.grid);
+        if (int rc = plan.geo.waves == owd::kWavesBig ? launch_dense_bank<owd::kWavesBig>(h, plan.geo.slots, grid, (int)plan.geo.staged, q)
+                                                      : launch_dense_bank<owd::kWavesSmall>(h, plan.geo.slots, grid, (int)plan.geo.staged, q)) return drained(h, rc);
+        HIPCHK(hipGetLastError());
+        for (const owh::DenseBankItem& it : items) covered[it.col] = 1;
+    }
+    // ---- the fallback, one head at a time
+    int64_t budget = owd::kSlabBytes;
+    if (const char* mb = getenv("OWW_DENSE_SLAB_MB")) budget = std::max<int64_t>(1, atoll(mb)) << 20;
+    int64_t slab_bytes = 0, slab_windows = 0;
+    for (int i = 0; i < n_ids; ++i) {
+        if (covered[i]) continue;
+        const owd::Slab sl = owd::slab((int64_t)B * nw, h->bank[ids[i]].T, budget);
+        slab_bytes = std::max(slab_bytes, sl.bytes); slab_windows = std::max(slab_windows, sl.windows);
+    }
+    if (!slab_bytes) return drained(h, 0);      // (the head list is the copy's source)
+    DevBuf<float> d_slab, d_sc; DevBuf<int> d_ent; DevBuf<owh::BankTile> d_til;
+    const int64_t max_tiles = (slab_windows + 127) / 128;
+    if (d_slab.alloc((size_t)slab_bytes / sizeof(float)) || d_sc.alloc((size_t)slab_windows) || d_ent.alloc((size_t)slab_windows) || d_til.alloc((size_t)max_tiles))
+        return drained(h, fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of window slab)", fn, (long long)(slab_bytes + slab_windows * 8 + max_tiles * 16)));
+    std::vector<int> ent((size_t)slab_windows);
+    for (int64_t k = 0; k < slab_windows; ++k) ent[(size_t)k] = (int)k;
+    if (copy_async(d_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
+    std::vector<owh::BankTile> til;
+    int64_t til_n = -1;                         // the window count d_til describes
+    for (int i = 0; i < n_ids; ++i) {
+        if (covered[i]) continue;
+        const oww_ctx::BankHead& bh = h->bank[ids[i]];
+        const owd::Slab sl = owd::slab((int64_t)B * nw, bh.T, budget);
+        for (int64_t s = 0; s < sl.n_slabs; ++s) {
+            const int64_t first = s * sl.windows, n = std::min<int64_t>(sl.windows, (int64_t)B * nw - first);
+            if (n != til_n) {
+                if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
+                til.clear();
+                for (int64_t o0 = 0; o0 < n; o0 += 128) til.push_back(owh::BankTile{0, (int)o0, (int)std::min<int64_t>(128, n - o0), 0});
+                if (copy_sync(d_til, til.data(), til.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice) != hipSuccess) return fail(OWW_EHIP, "%s: H2D failed", fn);
+                til_n = n;
+            }
+            owh::GatherParams gp{};
+            gp.feats = d_feats + (size_t)owd::row_offset(t_max, bh.T) * 96; gp.seq_stride = (long long)n_rows * 96;
+            gp.n_win = nw; gp.first = first; gp.n = n; gp.T = bh.T; gp.slab = d_slab;
+            {
+                Timed t(h, 7);
+                const int64_t pieces = n * bh.T * 24;
+                hipLaunchKernelGGL(owh::dense_gather_kernel, dim3((unsigned)std::min<int64_t>((pieces + 255) / 256, 256 * 16)), dim3(256), 0, h->stream, gp);
+            }
+            owh::BankParams bp{};
+            bp.feat = d_slab; bp.ext = 1; bp.TR = bh.T; bp.tiles = d_til; bp.entries = d_ent; bp.heads = h->d_bank_heads + ids[i]; bp.K = 1;
+            bp.raw = d_sc; bp.range_flag = h->d_range; bp.fscale = fscale;
+            {
+                Timed t(h, 6);
+                const dim3 grid((unsigned)til.size());
+                if (bh.ht == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 4>), grid, dim3(256), 0, h->stream, bp);
+                else hipLaunchKernelGGL((owh::heads_bank_kernel<4, 8>), grid, dim3(256), 0, h->stream, bp);
+            }
+            owh::BankSlabParams sp{};
+            sp.scores = d_sc; sp.n_win = nw; sp.first = first; sp.n = n; sp.out = d_out; sp.n_ids = n_ids; sp.col = i;
+            sp.thr = thr ? thr[i] : 0.5f; sp.count = d_count; sp.key = d_key;
+            {
+                Timed t(h, 7);
+                hipLaunchKernelGGL(owh::dense_bank_slab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, sp);
+            }
+        }
+    }
+    if (hipGetLastError() != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: a fallback launch failed", fn));
+    return drained(h, 0);           // (the slab and the lists go with this scope)
+}
+
 }  // namespace
 
 extern "C" {
@@ -3049,6 +3171,82 @@ int oww_score_clips(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t B
         return drained(h, fail(OWW_EHIP, "%s: embedding copy failed", fn));
     if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
     return range_check(h, fn);
+    OWW_GUARD_END
+}
+
+// ---- dense scoring over the head bank: oww_bank_score_shape, oww_bank_score_features, oww_bank_score_stats (bank_score_device above)
+int oww_bank_score_shape(oww_ctx* h, const int32_t* bank_ids, int32_t n_ids, int32_t n_rows, int32_t* n_win, int32_t* t_max) {
+    OWW_GUARD_BEGIN
+    const char* fn = "oww_bank_score_shape";
+    if (int rc = owd::bank_ready_check(fn, h != nullptr, h && h->committed, h ? h->bank_K : 0)) return rc;
+    int tm = 0;
+    if (int rc = owd::bank_ids_check(fn, bank_ids, n_ids, bank_live_T(h).data(), h->bank_cap, &tm)) return rc;
+    if (int rc = owd::shape_check(fn, n_rows, tm)) return rc;
+    if (n_win) *n_win = (int32_t)owd::n_win(n_rows, tm);
+    if (t_max) *t_max = tm;
+    return 0;
+    OWW_GUARD_END
+}
+
+int oww_bank_score_features(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows, const int32_t* bank_ids, int32_t n_ids,
+                            float* out, int out_on_device) {
+    OWW_GUARD_BEGIN
+    const char* fn = "oww_bank_score_features";
+    if (int rc = owd::bank_ready_check(fn, h != nullptr, h && h->committed, h ? h->bank_K : 0)) return rc;
+    int t_max = 0;
+    if (int rc = owd::bank_ids_check(fn, bank_ids, n_ids, bank_live_T(h).data(), h->bank_cap, &t_max)) return rc;
+    if (int rc = owd::bank_features_check(fn, feats, feats_on_device, B, n_rows, t_max, n_ids, out, out_on_device)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int64_t nw = owd::n_win(n_rows, t_max);
+    const uint64_t fb = owd::feats_bytes(B, n_rows), ob = owd::out_bytes(B, nw, n_ids);
+    DevBuf<float> d_f, d_o;
+    if ((!feats_on_device && d_f.alloc(fb / 4)) || (!out_on_device && d_o.alloc(ob / 4)))
+        return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features, %llu bytes of scores)", fn, (unsigned long long)fb, (unsigned long long)ob);
+    if (!feats_on_device && copy_async(d_f, feats, fb, hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
+    float* o = out_on_device ? out : d_o.get();
+    if (int rc = bank_score_device(h, fn, feats_on_device ? feats : d_f.get(), B, n_rows, bank_ids, n_ids, t_max, o, nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (!out_on_device && copy_async(out, d_o, ob, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: D2H failed", fn));
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
+    return range_check(h, fn);
+    OWW_GUARD_END
+}
+
+int oww_bank_score_stats(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows, const int32_t* bank_ids, int32_t n_ids,
+                         const float* thresholds, int32_t* count, float* max, int32_t* argmax) {
+    OWW_GUARD_BEGIN
+    const char* fn = "oww_bank_score_stats";
+    if (int rc = owd::bank_ready_check(fn, h != nullptr, h && h->committed, h ? h->bank_K : 0)) return rc;
+    int t_max = 0;
+    if (int rc = owd::bank_ids_check(fn, bank_ids, n_ids, bank_live_T(h).data(), h->bank_cap, &t_max)) return rc;
+    if (int rc = owd::bank_stats_check(fn, feats, feats_on_device, B, n_rows, t_max, n_ids, thresholds, count, max, argmax)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint64_t fb = owd::feats_bytes(B, n_rows);
+    const size_t cells = (size_t)B * (size_t)n_ids;
+    std::vector<float> thr((size_t)n_ids, 0.5f);                // train.py:100's default
+    if (thresholds) thr.assign(thresholds, thresholds + n_ids);
+    DevBuf<float> d_f, d_thr; DevBuf<int> d_count; DevBuf<unsigned long long> d_key;
+    if ((!feats_on_device && d_f.alloc(fb / 4)) || d_thr.alloc((size_t)n_ids) || d_count.alloc(cells) || d_key.alloc(cells))
+        return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features, %llu bytes of statistics)", fn, (unsigned long long)fb,
+                    (unsigned long long)owd::stats_bytes(B, n_ids));
+    if ((!feats_on_device && copy_async(d_f, feats, fb, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
+        copy_async(d_thr, thr.data(), thr.size() * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemsetAsync(d_count, 0, cells * sizeof(int), h->stream) != hipSuccess ||
+        hipMemsetAsync(d_key, 0, cells * sizeof(unsigned long long), h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
+    if (int rc = bank_score_device(h, fn, feats_on_device ? feats : d_f.get(), B, n_rows, bank_ids, n_ids, t_max, nullptr, d_thr, thr.data(), d_count, d_key))
+        return drained(h, rc);
+    std::vector<unsigned long long> key(cells);
+    if (copy_async(count, d_count, cells * sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        copy_async(key.data(), d_key, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: D2H failed", fn));
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
+    for (size_t c = 0; c < cells; ++c) {
+        const uint32_t bits = owd::stat_key_bits(key[c]);
+        memcpy(&max[c], &bits, sizeof bits);
+        argmax[c] = (int32_t)owd::stat_key_window(key[c]);
+    }
+    if (h->h_range && *(volatile int*)h->h_range)
+        return fail(OWW_ERANGE, "%s: an activation left the f16 range of the fp16-split kernels -- the statistics of this call are not defined (a score "
+                    "that is no number takes part in neither the count nor the maximum in a defined way); clear with oww_range_status(h, 1)", fn);
+    return 0;
     OWW_GUARD_END
 }
 

@@ -31,6 +31,7 @@
 // dense_gather_kernel: the fallback's window materialisation, [n][T][96] into a slab that owk / owh head kernels score as external
 // features (run_heads ext) -- every head form the sliding kernel does not cover, bit-identical to oww_head by construction.
 #pragma once
+#include "owwhip_dense_bank_host.h"
 #include "owwhip_dense_host.h"
 #include "owwhip_hx.h"
 
@@ -217,6 +218,266 @@ __global__ void dense_gather_kernel(GatherParams p) {
         const long long win = i / per, q = i - win * per;
         const long long gw = p.first + win, b = gw / p.n_win, w = gw - b * p.n_win;
         reinterpret_cast<owr::f32x4*>(p.slab)[i] = *reinterpret_cast<const owr::f32x4*>(p.feats + b * p.seq_stride + w * 96 + q * 4);
+    }
+}
+
+// ---- dense scoring over the head bank (include/owwhip.h: oww_bank_score_features, oww_bank_score_stats) --------------
+// heads_dense_bank_kernel<NBUF, WG>: heads_dense_kernel<1, NBUF, WG> with the head a loop variable.  ONE launch covers every listed
+// narrow bank head (HT = 4): block = (head slice, sequence, tile) (owd::bank_plan), and a workgroup stages its tile's rows once -- the
+// rows of the LONGEST head of the launch, t_s: 32 WG + t_s - 1 of them from row w0 + t_max - t_s on, same layout, split and scale --
+// and then walks the hpw heads of its slice, each with its own BankHeadDev (w1hx, net, T) from the handle's bank:
+//  * a head of length T reads its own last T rows of every window: its k-step ks takes the B operand from staged row
+//    16 (2 wave + t) + pos + (t_s - T) + ks / 3 (owd::bank_staged_row), then the same MFMA triplets in the same order and net64_score<1>,
+//    so a score is bit for bit heads_bank_kernel's, and with it the fixed heads kernel's, for the materialised window.
+//  * hand-over of the ring.  A head's last k-step ends without a barrier (nothing follows it in heads_dense_kernel).  Here the next
+//    head's prologue refills slots 0 .. D-1, one of which the slowest wave may still be reading: so lgkmcnt(0) + a bare s_barrier
+//    first, then the next head's first D chunks are issued -- under this head's tail (net64_score, the store or the reduction), which
+//    covers their L2 round trip -- and the next head begins with vmcnt(0) + __syncthreads(): the chunks have landed in every wave and
+//    the tail's stores and atomics have retired, so the k loop starts from "nothing outstanding", which is what its counted waits
+//    (every wave exactly KDMA DMA instructions per chunk, D - 1 chunks in flight behind the one waited for) assume.  Inside a head the
+//    discipline is heads_dense_kernel's, unchanged: counted wait, lgkmcnt(0), bare s_barrier; every ring slot its own LDS object.
+//  * matrix mode (out != nullptr): out[b][w][col] = score.  Statistics mode: count of scores >= thr[col], and the maximum with the
+//    first window that attains it as ONE integer key (owd::stat_key) -- reduced over the wave's 32 windows in registers, then one
+//    atomicAdd and one 64-bit atomicMax per wave and head.  Integer atomics commute: the result does not depend on scheduling.
+struct DenseBankItem { int head, col; };       // bank id, column of the caller's list
+struct DenseBankParams {
+    const float* feats;         // [B][..][96]: first staged row of window 0 (the launch's row offset t_max - t_s applied)
+    long long seq_stride;       // floats from one sequence to the next
+    int n_rows;                 // rows of a sequence from `feats` on
+    int n_win, seq_tiles, tiles;    // windows and tiles per sequence; B x seq_tiles
+    int t_s;                    // the largest T of the launch's heads
+    const BankHeadDev* heads;   // the handle's bank
+    const DenseBankItem* items; // [n_items] the launch's heads
+    int n_items, hpw;
+    float* out;                 // [B][n_win][n_ids], or nullptr = statistics
+    int n_ids;
+    const float* thr;           // [n_ids]
+    int* count;                 // [B][n_ids]
+    unsigned long long* key;    // [B][n_ids]
+    int* range_flag;
+    float fscale;
+};
+
+template <int NBUF, int WG>
+__global__ __launch_bounds__(64 * WG, 1) void heads_dense_bank_kernel(DenseBankParams p) {
+    using namespace owr;
+    constexpr int NT = 2;
+    constexpr int TILE = 16 * NT * WG;
+    constexpr int NCT = 4;                      // one narrow net
+    constexpr int NBLK = NCT * 2;
+    constexpr int CHUNK = NBLK * 256;
+    constexpr int D = NBUF - 1;
+    constexpr int KDMA = NBLK / WG;
+    static_assert(NBLK % WG == 0 && (D - 1) * KDMA < 64, "the counted wait assumes the same issue count in every wave");
+    extern __shared__ __attribute__((aligned(16))) float dense_rows[];
+    const int lane = threadIdx.x & 63, pos = lane & 15, j = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int slice = owd::bank_block_slice(blockIdx.x, p.tiles), tile = owd::bank_block_tile(blockIdx.x, p.tiles);
+    const int b = tile / p.seq_tiles, w0 = (tile - b * p.seq_tiles) * TILE;
+    const int i0 = owd::bank_slice_first(slice, p.hpw), nh = owd::bank_slice_count(slice, p.hpw, p.n_items);
+    auto prologue = [&](const float* w1hx) {    // (KST >= 3 >= D: every prologue chunk exists)
+#pragma unroll
+        for (int c = 0; c < D; ++c) issue_chunk_uniform<NBLK, WG>(w1hx + (size_t)c * CHUNK, hslot_at<CHUNK, NBUF - 1>(c), wave, lane);
+    };
+    prologue(p.heads[p.items[i0].head].w1hx);
+
+    // ---- stage the tile's rows once for all heads of the slice (heads_dense_kernel's staging with T = t_s)
+    {
+        const float* seq = p.feats + (size_t)b * p.seq_stride;
+        const int NU = (TILE + p.t_s - 1) * 12;
+        const float fsc = p.fscale;
+        for (int u0 = threadIdx.x; u0 < NU; u0 += 4 * 64 * WG) {
+            f32x4 r[4][2];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int u = min(u0 + q * 64 * WG, NU - 1);
+                const int row = u / 12, unit = u - row * 12;
+                const float* src = seq + (size_t)min(w0 + row, p.n_rows - 1) * 96 + unit * 8;
+                r[q][0] = *reinterpret_cast<const f32x4*>(src);
+                r[q][1] = *reinterpret_cast<const f32x4*>(src + 4);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int u = u0 + q * 64 * WG;
+                if (u >= NU) continue;
+                const int row = u / 12, unit = u - row * 12;
+                const Op o = split_pair<false>(r[q][0] * fsc, r[q][1] * fsc);
+                float* dst = dense_rows + owd::unit_word(row, unit);
+                *reinterpret_cast<f16x8*>(dst) = o.h;
+                *reinterpret_cast<f16x8*>(dst + 4) = o.l;
+            }
+        }
+    }
+
+    lanemask_t bad = 0;
+    for (int r = 0; r < nh; ++r) {
+        const DenseBankItem it = p.items[i0 + r];
+        const BankHeadDev* hd = p.heads + it.head;
+        const float* w1hx = hd->w1hx;
+        const int T = hd->T, KST = T * 3;
+        // this head's first D chunks have landed in every wave, the last head's stores and atomics have retired (and, r = 0, the rows
+        // are staged): the k loop starts with nothing outstanding
+        wait_vmcnt<0>();
+        __syncthreads();
+
+        f32x4 acc[NCT][NT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        auto load_b = [&](int ks, Op (&bo)[NT]) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const float* src = dense_rows + owd::unit_word(owd::bank_staged_row(wave, t, pos, p.t_s, T, ks), owd::kstep_unit(ks, j));
+                bo[t].h = *reinterpret_cast<const f16x8*>(src);
+                bo[t].l = *reinterpret_cast<const f16x8*>(src + 4);
+            }
+        };
+        Op bcur[NT], bnext[NT];
+        load_b(0, bcur);
+        // one k-step, as heads_dense_kernel<1>: ring slot u (static), prefetch of k-step ks + D, MFMAs, B operand of k-step ks + 1
+        auto kstep = [&](int ks, auto uc, auto always) {
+            constexpr int u = decltype(uc)::value;
+            constexpr bool ALWAYS = decltype(always)::value;
+            const float* cur = hslot_at<CHUNK, NBUF - 1>(u);
+            if (ALWAYS || ks + D < KST) {                           // slot of k-step ks-1: every wave passed the last barrier
+                constexpr int un = (u + D) % NBUF;
+                issue_chunk_uniform<NBLK, WG>(w1hx + (size_t)(ks + D) * CHUNK, hslot_at<CHUNK, NBUF - 1>(un), wave, lane);
+            }
+            f16x8 A[2][4];
+#pragma unroll
+            for (int bk = 0; bk < 4; ++bk) A[0][bk] = lds_h(cur, bk, lane);
+#pragma unroll
+            for (int c2 = 0; c2 < NCT; c2 += 2) {
+                const int pc = (c2 / 2) & 1;
+                if (c2 + 2 < NCT) {
+#pragma unroll
+                    for (int bk = 0; bk < 4; ++bk) A[pc ^ 1][bk] = lds_h(cur, (c2 + 2) * 2 + bk, lane);
+                } else if (ALWAYS || ks + 1 < KST) load_b(ks + 1, bnext);        // (flies under the last pair's MFMAs)
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int part = 0; part < 3; ++part) {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        acc[c2][t] = OWH_MFMA(part == 2 ? A[pc][1] : A[pc][0], part == 1 ? bcur[t].l : bcur[t].h, acc[c2][t]);
+                        acc[c2 + 1][t] = OWH_MFMA(part == 2 ? A[pc][3] : A[pc][2], part == 1 ? bcur[t].l : bcur[t].h, acc[c2 + 1][t]);
+                    }
+                }
+            }
+            if (ALWAYS || ks + 1 < KST) {
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (ALWAYS) wait_vmcnt<(D - 1) * KDMA>();
+                else wait_vmcnt<0>();
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#pragma unroll
+                for (int t = 0; t < NT; ++t) bcur[t] = bnext[t];
+            }
+        };
+        auto group = [&](int ks0, auto always) {
+            constexpr bool ALWAYS = decltype(always)::value;
+            static_for_while<0, NBUF>([&](auto uc) {
+                constexpr int U = decltype(uc)::value;
+                if (!ALWAYS && ks0 + U >= KST) return false;
+                kstep(ks0 + U, uc, always);
+                return true;
+            });
+        };
+        int ks0 = 0;
+        for (; ks0 + NBUF - 1 + D < KST; ks0 += NBUF) group(ks0, std::true_type{});
+        for (; ks0 < KST; ks0 += NBUF) group(ks0, std::false_type{});
+
+        // ---- hand-over: every wave's reads of the last slots have returned before the next head's prologue refills slots 0 .. D-1
+        if (r + 1 < nh) {
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            prologue(p.heads[p.items[i0 + r + 1].head].w1hx);
+        }
+
+        // ---- tail (the next head's first chunks fly under it)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) nan_guard(bad, acc[0][t][0]);
+        const HeadHxNet net = hd->net;
+        float score[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            f32x4 h1[4] = {acc[0][t], acc[1][t], acc[2][t], acc[3][t]};
+            score[t] = net64_score<1>(net, h1, bad, j, lane);
+        }
+        if (p.out) {
+            if (j == 0) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const int w = w0 + wave * 16 * NT + t * 16 + pos;
+                    if (w < p.n_win) p.out[((size_t)b * p.n_win + w) * p.n_ids + it.col] = score[t];
+                }
+            }
+        } else {
+            const float thr = p.thr[it.col];
+            int hits = 0;
+            unsigned long long key = 0ull;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int w = w0 + wave * 16 * NT + t * 16 + pos;
+                const bool valid = j == 0 && w < p.n_win;
+                hits += __popcll(__ballot(valid && score[t] >= thr));
+                if (valid) {
+                    const unsigned long long k = owd::stat_key(__float_as_uint(score[t]), (unsigned)w);
+                    key = k > key ? k : key;
+                }
+            }
+#pragma unroll
+            for (int m = 1; m < 16; m <<= 1) {                  // lanes 0..15 carry the wave's windows (j == 0), the others 0
+                const unsigned long long o = __shfl_xor(key, m);
+                key = o > key ? o : key;
+            }
+            if (lane == 0) {
+                const size_t at = (size_t)b * p.n_ids + it.col;
+                if (hits) atomicAdd(p.count + at, hits);
+                if (key) atomicMax(p.key + at, key);
+            }
+        }
+    }
+    raise_range_flag(bad, p.range_flag);        // (position unknown: a window is no stream)
+}
+
+// The fallback's last step: the scores of one slab (windows [first, first + n) of the flattened [B][n_win] list, one bank head, as
+// heads_bank_kernel left them in its ext mode) -> column `col` of the matrix, or into the statistics with the keys of the kernel above.
+// A wave whose windows lie in one sequence reduces in registers first; one that straddles two sequences lets every lane speak.
+struct BankSlabParams {
+    const float* scores;        // [n]
+    long long n_win, first, n;
+    float* out; int n_ids, col;
+    float thr; int* count; unsigned long long* key;
+};
+__global__ void dense_bank_slab_kernel(BankSlabParams p) {
+    const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) & ~63ll;        // the wave's first window of the slab
+    if (i0 >= p.n) return;
+    const long long i = i0 + (threadIdx.x & 63);
+    const bool valid = i < p.n;
+    const long long gw = p.first + (valid ? i : p.n - 1), b = gw / p.n_win, w = gw - b * p.n_win;
+    const float sc = p.scores[valid ? i : p.n - 1];
+    if (p.out) {
+        if (valid) p.out[(size_t)gw * p.n_ids + p.col] = sc;
+        return;
+    }
+    const long long b_first = (p.first + i0) / p.n_win, b_last = (p.first + min(i0 + 63, p.n - 1)) / p.n_win;
+    unsigned long long key = valid ? owd::stat_key(__float_as_uint(sc), (unsigned)w) : 0ull;
+    const bool hit = valid && sc >= p.thr;
+    if (b_first == b_last) {
+        const int hits = __popcll(__ballot(hit));
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const unsigned long long o = __shfl_xor(key, m);
+            key = o > key ? o : key;
+        }
+        if ((threadIdx.x & 63) == 0) {
+            const size_t at = (size_t)b * p.n_ids + p.col;
+            if (hits) atomicAdd(p.count + at, hits);
+            if (key) atomicMax(p.key + at, key);
+        }
+    } else if (valid) {
+        const size_t at = (size_t)b * p.n_ids + p.col;
+        if (hit) atomicAdd(p.count + at, 1);
+        atomicMax(p.key + at, key);
     }
 }
 

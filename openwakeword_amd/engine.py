@@ -1027,6 +1027,57 @@ class StreamEngine:
         _lib.check(self._lib.oww_score_clips(self._h, _ptr(pcm), 0, B, n, _ptr(out), 0, _ptr(emb) if return_features else None, 0))
         return (out, emb) if return_features else out
 
+    # ---- dense scoring over the head bank (include/owwhip.h: oww_bank_score_shape / oww_bank_score_features / oww_bank_score_stats)
+    @staticmethod
+    def _bank_ids(ids) -> np.ndarray:
+        a = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        if a.size < 1:
+            raise ValueError("need at least one bank id")
+        return a
+
+    @staticmethod
+    def _bank_feats(feats) -> np.ndarray:
+        f = np.ascontiguousarray(feats, dtype=np.float32)
+        if f.ndim == 2:
+            f = f[None]
+        if f.ndim != 3 or f.shape[2] != EMB_DIM:
+            raise ValueError(f"bank scoring expects [B, n_rows, 96], got {f.shape}")
+        return f
+
+    def bank_score_shape(self, ids: Sequence[int], n_rows: int) -> Tuple[int, int]:
+        """(n_win, t_max) for sequences of n_rows feature rows scored with the listed bank heads: t_max = their largest window
+        length, n_win = n_rows - t_max + 1."""
+        a = self._bank_ids(ids)
+        n_win, t_max = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.oww_bank_score_shape(self._h, _ptr(a), a.size, int(n_rows), C.byref(n_win), C.byref(t_max)))
+        return int(n_win.value), int(t_max.value)
+
+    def bank_score_features(self, feats: np.ndarray, ids: Sequence[int]) -> np.ndarray:
+        """Every window of feature sequences [B, n_rows, 96] through the listed bank heads -> raw sigmoid outputs [B, n_win, n_ids]
+        (column i: bank head ids[i]; duplicates allowed).  Window w ends at row w + t_max - 1 and each head reads its own last T rows.
+        No post-processing; subscriptions, bank scores and every other piece of live state stay as they are."""
+        f, a = self._bank_feats(feats), self._bank_ids(ids)
+        B, n_rows, _ = f.shape
+        n_win, _ = self.bank_score_shape(a, n_rows)
+        out = np.empty((B, n_win, a.size), dtype=np.float32)
+        _lib.check(self._lib.oww_bank_score_features(self._h, _ptr(f), 0, B, n_rows, _ptr(a), a.size, _ptr(out), 0))
+        return out
+
+    def bank_score_stats(self, feats: np.ndarray, ids: Sequence[int], thresholds: Optional[Sequence[float]] = None) -> Dict[str, np.ndarray]:
+        """What a validation scan wants of bank_score_features' matrix, reduced on the device (the matrix is never written):
+        {"count": int32 [B, n_ids] windows with score >= thresholds[i] (None = 0.5, train.py:100), "max": float32 [B, n_ids],
+        "argmax": int32 [B, n_ids] the first window that attains the maximum} -- bit for bit numpy's on the matrix."""
+        f, a = self._bank_feats(feats), self._bank_ids(ids)
+        B, n_rows, _ = f.shape
+        thr = None
+        if thresholds is not None:
+            thr = np.ascontiguousarray(thresholds, dtype=np.float32).ravel()
+            if thr.shape != (a.size,):
+                raise ValueError(f"need one threshold per listed head ({a.size})")
+        count, mx, arg = (np.empty((B, a.size), dtype=t) for t in (np.int32, np.float32, np.int32))
+        _lib.check(self._lib.oww_bank_score_stats(self._h, _ptr(f), 0, B, n_rows, _ptr(a), a.size, _ptr(thr), _ptr(count), _ptr(mx), _ptr(arg)))
+        return {"count": count, "max": mx, "argmax": arg}
+
     # ---- introspection
     def get_features(self, sid: int, T: int = 16) -> np.ndarray:
         out = np.empty((T, EMB_DIM), dtype=np.float32)

@@ -781,6 +781,21 @@ class BatchedModel:
         collect_batch (an empty slot reads 0.0)."""
         return self.engine.bank_scores()
 
+    # ---- dense scoring over the bank: validate heads on a corpus (include/owwhip.h: oww_bank_score_*) ----
+    def bank_score_shape(self, ids: Sequence[int], n_rows: int):
+        """(n_win, t_max) of sequences of n_rows feature rows under the listed bank heads (t_max = their longest window)."""
+        return self.engine.bank_score_shape(ids, n_rows)
+
+    def bank_score_features(self, feats: np.ndarray, ids: Sequence[int]) -> np.ndarray:
+        """Every window of feature sequences [B, n_rows, 96] through the listed bank heads -> raw scores [B, n_win, n_ids]; window w
+        ends at row w + t_max - 1 and each head reads its own last T rows.  The live streams and their subscriptions do not notice."""
+        return self.engine.bank_score_features(feats, ids)
+
+    def bank_score_stats(self, feats: np.ndarray, ids: Sequence[int], thresholds: Optional[Sequence[float]] = None) -> Dict[str, np.ndarray]:
+        """{"count", "max", "argmax"}, each [B, n_ids]: the windows with score >= thresholds[i] (None = 0.5, train.py:100), the
+        largest score and the first window that attains it -- reduced on the device, the score matrix is never written."""
+        return self.engine.bank_score_stats(feats, ids, thresholds)
+
     # ---- detection events: the hits of a call as ordered records with feature snapshots (include/owwhip.h: oww_events_*) ----
     def set_event_thresholds(self, thresholds: Optional[dict] = None, bank: Optional[float] = None) -> None:
         """Event thresholds by label ({label: value}; labels not named keep theirs, NaN = the label never reports) and for the bank

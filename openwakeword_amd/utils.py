@@ -248,3 +248,32 @@ def mine_windows(clips, wakeword_models, threshold: float = 0.5, **kw) -> dict:
     finally:
         if own:
             bm.close()
+
+
+def validate_bank(path_or_array, model, ids, thresholds=None, chunk_rows: int = 1 << 18, hours: float = None) -> dict:
+    """The scan of train.py:225-258 (`_select_best_model`) for bank heads: every T-row window (stride 1) of precomputed negative
+    features `[N, 96]` -- a `.npy` path, read through a memmap, or an array -- through the bank heads `ids` of `model` (a `BatchedModel`
+    or `StreamEngine` with a head bank), counted on the device -> {id: {"n_false_positives": windows with score >= its threshold
+    (`thresholds` None = 0.5, train.py:100), "false_positives_per_hour", "max_score", "argmax_window": the first window that attains
+    it}}.  Window w ends at row w + t_max - 1, t_max the longest window of the listed heads, and each head reads its own last T rows.
+    The array is scored `chunk_rows` rows at a time, chunks overlapping by t_max - 1 rows: counts add, and of two chunks with the
+    same maximum the earlier one keeps the argmax, so the result does not depend on `chunk_rows`.  The hours are n_win * 0.08 / 3600
+    unless `hours` is given (train.py:245 divides by a caller-given `val_set_hrs`).  train.py:875's `range(0, N - T, 1)` drops the
+    last window; this scan does not, so a hit on the very last window is counted here and not there."""
+    feats = np.load(path_or_array, mmap_mode="r") if isinstance(path_or_array, (str, os.PathLike)) else np.asarray(path_or_array)
+    if feats.ndim != 2 or feats.shape[1] != EMB_DIM:
+        raise ValueError(f"features must be [N, 96], got {feats.shape}")
+    ids = [int(i) for i in ids]
+    n_win, t_max = model.bank_score_shape(ids, feats.shape[0])
+    count = np.zeros(len(ids), dtype=np.int64)
+    best = np.full(len(ids), -np.inf, dtype=np.float32)
+    where = np.zeros(len(ids), dtype=np.int64)
+    for w0, _, r0, r1 in dense_chunks(feats.shape[0], t_max, chunk_rows):
+        st = model.bank_score_stats(np.ascontiguousarray(feats[r0:r1], dtype=np.float32)[None], ids, thresholds)
+        count += st["count"][0]
+        better = st["max"][0] > best                    # (strictly: a tie stays with the earlier chunk)
+        best = np.where(better, st["max"][0], best)
+        where = np.where(better, st["argmax"][0].astype(np.int64) + w0, where)
+    hrs = n_win * 0.08 / 3600.0 if hours is None else float(hours)
+    return {i: {"n_false_positives": int(count[k]), "false_positives_per_hour": float(count[k] / hrs), "max_score": float(best[k]),
+                "argmax_window": int(where[k])} for k, i in enumerate(ids)}
