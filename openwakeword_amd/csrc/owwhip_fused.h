@@ -312,7 +312,7 @@ __global__ __launch_bounds__(64 * FA_WG, (FA_WG + 3) / 4) void hmelA_kernel(MelA
 #elif OWF_PRIO == 2
         __builtin_amdgcn_s_setprio(OWF_PRIO_HI); // (variant, inverse: the log-mel phase outranks)
 #endif
-        if (bad) { owh::raise_range_flag(bad, q.a.range_flag, s, 1); bad = 0; }
+        if (bad) { owh::keep_stream_loud_a(q.a.hist_mel, s); owh::raise_range_flag(bad, q.a.range_flag, s, 1); bad = 0; }
         __builtin_amdgcn_sched_barrier(0);
     }
     owh::raise_range_flag(bad, q.a.range_flag);

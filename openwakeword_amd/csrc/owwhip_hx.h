@@ -90,8 +90,15 @@ __device__ __forceinline__ void raise_range_flag(lanemask_t bad, int* flag, int 
     }
 }
 
+// Stage A's share of "a stream that was out of range keeps saying so until it is reset" (see the end of hstage_kernel): bin 0 of the
+// older mel history row becomes the f16 pair (NaN, NaN), which conv0's guard sees in every later step.  After hstageA_stream, which
+// has just rewritten the history (same lane, program order).
+__device__ __forceinline__ void keep_stream_loud_a(float* hist_mel, int s) {
+    if ((threadIdx.x & 63) == 0) reinterpret_cast<unsigned*>(hist_mel + (size_t)s * 64)[0] = 0x7e007e00u;
+}
+
 #ifndef OWH_MIXSPLIT
-#define OWH_MIXSPLIT 1     // residual halves by v_fma_mix{lo,hi}_f16 (f16 source read in place): 1.5 instead of 2.6 VALU ops per value
+#define OWH_MIXSPLIT 1    // residual halves by v_fma_mix{lo,hi}_f16 (f16 source read in place): 1.5 instead of 2.6 VALU ops per value
 #endif
 template <bool MIX = (OWH_MIXSPLIT != 0)>
 __device__ __forceinline__ Op split_pair(const f32x4 a, const f32x4 b) {
@@ -1293,7 +1300,19 @@ __global__ __launch_bounds__(64 * WG, (DBG || NS > 3 || NS == 1 ? 1 : (NS == 3 &
     }
     }   // pass
     if (!LAST && C::NPASS > 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // drain the chunk the last pass prefetched
-    raise_range_flag(bad, p.range_flag, s_first, C::SPT);
+    if (bad != 0) {
+        // The activation has swallowed the NaN, so from the next step on the stream would score finite, wrong and silent, and the one
+        // position word names one wave per step.  A stream that was out of range therefore keeps saying so until it is reset or
+        // imported: its word of conv b's history row 0 (tile 0, register 0, lane = position) becomes NaN, which the same guard sees
+        // in every later step.  Off the clean path: one scalar branch, shared with the flag.  Lane 0 writes for the wave's 16
+        // positions (bits 0..15 of the mask: lane group 0); a per-lane store here kept two more values alive through the kernel
+        // and cost 0.4 % of the step.  (A stream that sits a masked step out is flagged only if its own state is out of range already.)
+        if (lane0 == 0) {
+            float* hb0 = p.hist_b + (size_t)g * C::HIST_FLOATS;
+            for (int q = 0; q < 16; ++q) if ((bad >> q) & 1) hb0[q] = __builtin_nanf("");
+        }
+        raise_range_flag(bad, p.range_flag, s_first, C::SPT);
+    }
     if constexpr (!RES) break;
     }
 }
@@ -1387,10 +1406,16 @@ __device__ __forceinline__ void hstageA_stream(const owr::RAParams& p, int s, _F
         const int o = (lane >> 5) * sa::RS + 1 + (lane & 31);
         reinterpret_cast<unsigned short*>(sP)[o] = (unsigned short)(w & 0xffffu);
         reinterpret_cast<unsigned short*>(sP)[sa::PLANE + o] = (unsigned short)(w >> 16);
+        // conv0's range guard sits on its INPUTS: a mel value beyond the f16 range arrives as hi = inf, lo = -inf, the accumulator is
+        // NaN, and med3(NaN, K h, +-inf) = min3 of the other two -- finite, so no later layer would see it.  The rows the fused front
+        // end computes are bounded; what can be out of range is an imported history (here: a half with all exponent bits set) and
+        // the mel rows somebody hands to oww_embed (below).
+        bad |= __ballot(((w & 0x7c00u) == 0x7c00u) | ((w & 0x7c000000u) == 0x7c000000u));
     }
     if (!MEL_IN_LDS) {
         const f32x4 m4 = *reinterpret_cast<const f32x4*>(p.mel + (size_t)s * p.mel_stride + p.mel_off + lane * 4);
         const int row = lane >> 3, col = (lane & 7) * 4;
+        bad |= __ballot(!(fabsf(m4[0]) < 65520.f && fabsf(m4[1]) < 65520.f && fabsf(m4[2]) < 65520.f && fabsf(m4[3]) < 65520.f));   // (NaN too)
 #pragma unroll
         for (int e = 0; e < 4; ++e) stageA_put_mel(sP, 2 + row, col + e, m4[e]);
     }
@@ -1664,7 +1689,7 @@ __global__ __launch_bounds__(256, DBG ? 1 : OWH_WPS_A) void hstageA_kernel(owr::
         const int s = s0 + p.s_base;
         if (p.stream_on && !p.stream_on[s]) continue;            // masked step: this stream sits it out
         hstageA_stream<DBG, false>(p, s, sPl[wave], sW0, sW[0], sW[1], &sbn[0][0][0], gtab, bad, lane);
-        if (bad) { raise_range_flag(bad, p.range_flag, s, 1); bad = 0; }
+        if (bad) { keep_stream_loud_a(p.hist_mel, s); raise_range_flag(bad, p.range_flag, s, 1); bad = 0; }
     }
 }
 
