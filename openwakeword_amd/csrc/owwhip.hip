@@ -1882,24 +1882,60 @@ int dense_t_max(const oww_ctx* h) {
     return t;
 }
 
-// (the attribute call stays in front of the timed window: with an idle device the start event is stamped at once, and host time
-// between it and the launch would be booked as kernel time)
-template <int NN, int WG>
-int launch_dense_nn(oww_ctx* h, int slots, dim3 grid, int lds, const owh::DenseParams& q) {
-    const dim3 block(64 * WG);
-    hipStream_t st = h->stream;
-#define OWW_DENSE_GO(NB)                                                                                                                     \
-    do {                                                                                                                                     \
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(owh::heads_dense_kernel<NN, NB, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-        Timed t(h, 6);                                                                                                                       \
-        hipLaunchKernelGGL((owh::heads_dense_kernel<NN, NB, WG>), grid, block, lds, st, q);                                                      \
-    } while (0)
-    if (slots >= 4) OWW_DENSE_GO(4);
-    else if (slots == 3) OWW_DENSE_GO(3);
-    else OWW_DENSE_GO(2);
-#undef OWW_DENSE_GO
+// One launch of a sliding kernel, fixed heads or bank: k4 / k3 / k2 are its instantiations for a ring of 4, 3 and 2 slots
+// (owd::geometry; its staged rows are the dynamic LDS).  (The attribute call stays in front of the timed window: with an idle device the
+// start event is stamped at once, and host time between it and the launch would be booked as kernel time.)
+template <class P>
+int launch_dense(oww_ctx* h, const owd::Geometry& geo, dim3 grid, const P& q, void (*k4)(P), void (*k3)(P), void (*k2)(P)) {
+    void (*const k)(P) = geo.slots >= 4 ? k4 : geo.slots == 3 ? k3 : k2;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.staged));
+    Timed t(h, 6);
+    hipLaunchKernelGGL(k, grid, dim3(64 * geo.waves), (int)geo.staged, h->stream, q);
     return 0;
 }
+template <int NN, int WG>
+int launch_dense_nn(oww_ctx* h, const owd::Geometry& geo, dim3 grid, const owh::DenseParams& q) {
+    return launch_dense(h, geo, grid, q, owh::heads_dense_kernel<NN, 4, WG>, owh::heads_dense_kernel<NN, 3, WG>, owh::heads_dense_kernel<NN, 2, WG>);
+}
+template <int WG>
+int launch_dense_bank(oww_ctx* h, const owd::Geometry& geo, dim3 grid, const owh::DenseBankParams& q) {
+    return launch_dense(h, geo, grid, q, owh::heads_dense_bank_kernel<4, WG>, owh::heads_dense_bank_kernel<3, WG>, owh::heads_dense_bank_kernel<2, WG>);
+}
+
+// the A/B aids of both dense paths: OWW_DENSE_PATH=ext = every head down the gather fallback, OWW_DENSE_SLAB_MB = the slab budget
+struct DenseEnv { bool slide; int64_t budget; };
+DenseEnv dense_env() {
+    const char* path = getenv("OWW_DENSE_PATH");
+    const char* mb = getenv("OWW_DENSE_SLAB_MB");
+    return DenseEnv{!(path && !strcmp(path, "ext")), mb ? std::max<int64_t>(1, atoll(mb)) << 20 : owd::kSlabBytes};
+}
+
+// The gather fallback of one call: the windows of d_feats [B][n_rows][96] materialised into a bounded slab, slab after slab.  want(T)
+// for every head that takes it sizes the slab, each(h, T, f) gathers a head's windows slab by slab and hands f(first, n) -- windows
+// [first, first + n) of the flattened [B][nw] list are in d_slab -- to the caller's head launches; it stops at f's first error.
+struct SlabWalk {
+    const float* d_feats; int B, n_rows, t_max; int64_t nw, budget;
+    int64_t bytes = 0, windows = 0;             // of the largest slab wanted (0: nobody takes the fallback)
+    DevBuf<float> d_slab;
+    void want(int T) { const owd::Slab sl = owd::slab((int64_t)B * nw, T, budget); bytes = std::max(bytes, sl.bytes); windows = std::max(windows, sl.windows); }
+    template <class F>
+    int each(oww_ctx* h, int T, F&& f) {
+        const owd::Slab sl = owd::slab((int64_t)B * nw, T, budget);
+        for (int64_t s = 0; s < sl.n_slabs; ++s) {
+            const int64_t first = s * sl.windows, n = std::min<int64_t>(sl.windows, (int64_t)B * nw - first);
+            owh::GatherParams gp{};
+            gp.feats = d_feats + (size_t)owd::row_offset(t_max, T) * 96; gp.seq_stride = (long long)n_rows * 96;
+            gp.n_win = nw; gp.first = first; gp.n = n; gp.T = T; gp.slab = d_slab;
+            {
+                Timed t(h, 7);
+                const int64_t pieces = n * T * 24;
+                hipLaunchKernelGGL(owh::dense_gather_kernel, dim3((unsigned)std::min<int64_t>((pieces + 255) / 256, 256 * 16)), dim3(256), 0, h->stream, gp);
+            }
+            if (int rc = f(first, n)) return rc;
+        }
+        return 0;
+    }
+};
 
 // every window of d_feats [B][n_rows][96] through every fixed head -> d_out [B][n_win][NL]; both on the device.  Narrow fp16-split
 // groups take the sliding-window kernel, one launch per pass of one or two nets (owd::split_passes, owd::geometry); every other head
@@ -1909,8 +1945,8 @@ int launch_dense_nn(oww_ctx* h, int slots, dim3 grid, int lds, const owh::DenseP
 int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_rows, float* d_out) {
     const int t_max = dense_t_max(h);
     const int64_t nw = owd::n_win(n_rows, t_max);
-    const char* env = getenv("OWW_DENSE_PATH");
-    const bool slide = h->hx && h->mfma && !(env && !strcmp(env, "ext"));
+    const DenseEnv env = dense_env();
+    const bool slide = h->hx && h->mfma && env.slide;
     // d_out is not cleared (it may be gigabytes): every fixed head is scored below, by a sliding pass or by the fallback, and the
     // heads' n_out columns are exactly the NL columns of a row (build_nets lays them side by side), so every entry is written
     std::vector<char> covered(h->heads.size(), 0);
@@ -1932,10 +1968,8 @@ int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_
                 q.out = d_out; q.NL = h->NL; q.range_flag = h->d_range; q.fscale = std::ldexp(1.0f, h->hx_efeat);
                 const dim3 grid((unsigned)((int64_t)B * q.tiles));
                 int rc = 0;
-                if (geo.waves == owd::kWavesBig) rc = nn == 1 ? launch_dense_nn<1, owd::kWavesBig>(h, geo.slots, grid, (int)geo.staged, q)
-                                                              : launch_dense_nn<2, owd::kWavesBig>(h, geo.slots, grid, (int)geo.staged, q);
-                else rc = nn == 1 ? launch_dense_nn<1, owd::kWavesSmall>(h, geo.slots, grid, (int)geo.staged, q)
-                                  : launch_dense_nn<2, owd::kWavesSmall>(h, geo.slots, grid, (int)geo.staged, q);
+                if (geo.waves == owd::kWavesBig) rc = nn == 1 ? launch_dense_nn<1, owd::kWavesBig>(h, geo, grid, q) : launch_dense_nn<2, owd::kWavesBig>(h, geo, grid, q);
+                else rc = nn == 1 ? launch_dense_nn<1, owd::kWavesSmall>(h, geo, grid, q) : launch_dense_nn<2, owd::kWavesSmall>(h, geo, grid, q);
                 if (rc) return rc;
             }
             for (int ni : g.nets) covered[h->nets[ni].head] = 1;
@@ -1944,31 +1978,17 @@ int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_
     }
     // what is left, one launch unit at a time: a fast group the kernel above did not take is ONE run_heads launch for all its heads
     // (run_heads launches the whole group of the head it is asked for), a generic or recurrent head is a launch of its own
-    int64_t budget = owd::kSlabBytes;
-    if (const char* mb = getenv("OWW_DENSE_SLAB_MB")) budget = std::max<int64_t>(1, atoll(mb)) << 20;      // (A/B aid: one slab for everything)
-    int64_t slab_bytes = 0;
+    SlabWalk sw{d_feats, B, n_rows, t_max, nw, env.budget};
     for (size_t hi = 0; hi < h->heads.size(); ++hi)
-        if (!covered[hi]) slab_bytes = std::max(slab_bytes, owd::slab((int64_t)B * nw, h->heads[hi].T, budget).bytes);
-    if (!slab_bytes) return 0;
-    DevBuf<float> d_slab;
-    if (d_slab.alloc((size_t)slab_bytes / sizeof(float))) return fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of window slab)", fn, (long long)slab_bytes);
+        if (!covered[hi]) sw.want(h->heads[hi].T);
+    if (!sw.bytes) return 0;
+    if (sw.d_slab.alloc((size_t)sw.bytes / sizeof(float))) return fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of window slab)", fn, (long long)sw.bytes);
     int rc = 0;
     for (size_t hi = 0; hi < h->heads.size() && !rc; ++hi) {
         if (covered[hi]) continue;
-        const int T = h->heads[hi].T;
-        const owd::Slab sl = owd::slab((int64_t)B * nw, T, budget);
-        for (int64_t s = 0; s < sl.n_slabs && !rc; ++s) {
-            const int64_t first = s * sl.windows, n = std::min<int64_t>(sl.windows, (int64_t)B * nw - first);
-            owh::GatherParams gp{};
-            gp.feats = d_feats + (size_t)owd::row_offset(t_max, T) * 96; gp.seq_stride = (long long)n_rows * 96;
-            gp.n_win = nw; gp.first = first; gp.n = n; gp.T = T; gp.slab = d_slab;
-            {
-                Timed t(h, 7);
-                const int64_t pieces = n * T * 24;
-                hipLaunchKernelGGL(owh::dense_gather_kernel, dim3((unsigned)std::min<int64_t>((pieces + 255) / 256, 256 * 16)), dim3(256), 0, h->stream, gp);
-            }
-            rc = run_heads(h, step_args(h), (int)n, false, d_slab, (int)hi, d_out + (size_t)first * h->NL, 0);
-        }
+        rc = sw.each(h, h->heads[hi].T, [&](int64_t first, int64_t n) {
+            return run_heads(h, step_args(h), (int)n, false, sw.d_slab, (int)hi, d_out + (size_t)first * h->NL, 0);
+        });
         covered[hi] = 1;
         if (h->mfma)
             for (const FastGroup& g : h->groups) {
@@ -1981,23 +2001,6 @@ int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_
 }
 
 // ---- dense scoring over the head bank (oww_bank_score_*; owwhip_dense.h: heads_dense_bank_kernel, owwhip_dense_bank_host.h) ----------
-template <int WG>
-int launch_dense_bank(oww_ctx* h, int slots, dim3 grid, int lds, const owh::DenseBankParams& q) {
-    const dim3 block(64 * WG);
-    hipStream_t st = h->stream;
-#define OWW_DENSE_BANK_GO(NB)                                                                                                                \
-    do {                                                                                                                                     \
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(owh::heads_dense_bank_kernel<NB, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-        Timed t(h, 6);                                                                                                                       \
-        hipLaunchKernelGGL((owh::heads_dense_bank_kernel<NB, WG>), grid, block, lds, st, q);                                                    \
-    } while (0)
-    if (slots >= 4) OWW_DENSE_BANK_GO(4);
-    else if (slots == 3) OWW_DENSE_BANK_GO(3);
-    else OWW_DENSE_BANK_GO(2);
-#undef OWW_DENSE_BANK_GO
-    return 0;
-}
-
 // T of every live bank head by id (0 = empty slot): what owd::bank_ids_check reads
 std::vector<int> bank_live_T(const oww_ctx* h) {
     std::vector<int> t(h->bank.size(), 0);
@@ -2013,13 +2016,12 @@ std::vector<int> bank_live_T(const oww_ctx* h) {
 int bank_score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_rows, const int32_t* ids, int n_ids, int t_max, float* d_out,
                       const float* d_thr, const float* thr, int* d_count, unsigned long long* d_key) {
     const int64_t nw = owd::n_win(n_rows, t_max);
-    const char* env = getenv("OWW_DENSE_PATH");
-    const bool slide = !(env && !strcmp(env, "ext"));
+    const DenseEnv env = dense_env();
     const float fscale = std::ldexp(1.0f, h->hx_efeat);
     std::vector<owh::DenseBankItem> items;
     int t_s = 0;
     for (int i = 0; i < n_ids; ++i)
-        if (slide && h->bank[ids[i]].ht == 4) { items.push_back(owh::DenseBankItem{ids[i], i}); t_s = std::max(t_s, h->bank[ids[i]].T); }
+        if (env.slide && h->bank[ids[i]].ht == 4) { items.push_back(owh::DenseBankItem{ids[i], i}); t_s = std::max(t_s, h->bank[ids[i]].T); }
     const owd::BankPlan plan = items.empty() ? owd::BankPlan{} : owd::bank_plan((int64_t)items.size(), B, nw, t_s, owd::bank_hpw_env());
     if (!plan.hpw) items.clear();
     std::vector<char> covered((size_t)n_ids, 0);
@@ -2035,53 +2037,38 @@ int bank_score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, i
         q.heads = h->d_bank_heads; q.items = d_items; q.n_items = (int)items.size(); q.hpw = plan.hpw;
         q.out = d_out; q.n_ids = n_ids; q.thr = d_thr; q.count = d_count; q.key = d_key; q.range_flag = h->d_range; q.fscale = fscale;
         const dim3 grid((unsigned)plan.grid);
-        if (int rc = plan.geo.waves == owd::kWavesBig ? launch_dense_bank<owd::kWavesBig>(h, plan.geo.slots, grid, (int)plan.geo.staged, q)
-                                                      : launch_dense_bank<owd::kWavesSmall>(h, plan.geo.slots, grid, (int)plan.geo.staged, q)) return drained(h, rc);
+        if (int rc = plan.geo.waves == owd::kWavesBig ? launch_dense_bank<owd::kWavesBig>(h, plan.geo, grid, q)
+                                                      : launch_dense_bank<owd::kWavesSmall>(h, plan.geo, grid, q)) return drained(h, rc);
         HIPCHK(hipGetLastError());
         for (const owh::DenseBankItem& it : items) covered[it.col] = 1;
     }
     // ---- the fallback, one head at a time
-    int64_t budget = owd::kSlabBytes;
-    if (const char* mb = getenv("OWW_DENSE_SLAB_MB")) budget = std::max<int64_t>(1, atoll(mb)) << 20;
-    int64_t slab_bytes = 0, slab_windows = 0;
-    for (int i = 0; i < n_ids; ++i) {
-        if (covered[i]) continue;
-        const owd::Slab sl = owd::slab((int64_t)B * nw, h->bank[ids[i]].T, budget);
-        slab_bytes = std::max(slab_bytes, sl.bytes); slab_windows = std::max(slab_windows, sl.windows);
-    }
-    if (!slab_bytes) return drained(h, 0);      // (the head list is the copy's source)
-    DevBuf<float> d_slab, d_sc; DevBuf<int> d_ent; DevBuf<owh::BankTile> d_til;
-    const int64_t max_tiles = (slab_windows + 127) / 128;
-    if (d_slab.alloc((size_t)slab_bytes / sizeof(float)) || d_sc.alloc((size_t)slab_windows) || d_ent.alloc((size_t)slab_windows) || d_til.alloc((size_t)max_tiles))
-        return drained(h, fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of window slab)", fn, (long long)(slab_bytes + slab_windows * 8 + max_tiles * 16)));
-    std::vector<int> ent((size_t)slab_windows);
-    for (int64_t k = 0; k < slab_windows; ++k) ent[(size_t)k] = (int)k;
+    SlabWalk sw{d_feats, B, n_rows, t_max, nw, env.budget};
+    for (int i = 0; i < n_ids; ++i)
+        if (!covered[i]) sw.want(h->bank[ids[i]].T);
+    if (!sw.bytes) return drained(h, 0);        // (the head list is the copy's source)
+    DevBuf<float> d_sc; DevBuf<int> d_ent; DevBuf<owh::BankTile> d_til;
+    const int64_t max_tiles = (sw.windows + 127) / 128;
+    if (sw.d_slab.alloc((size_t)sw.bytes / sizeof(float)) || d_sc.alloc((size_t)sw.windows) || d_ent.alloc((size_t)sw.windows) || d_til.alloc((size_t)max_tiles))
+        return drained(h, fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of window slab)", fn, (long long)(sw.bytes + sw.windows * 8 + max_tiles * 16)));
+    std::vector<int> ent((size_t)sw.windows);
+    for (int64_t k = 0; k < sw.windows; ++k) ent[(size_t)k] = (int)k;
     if (copy_async(d_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
     std::vector<owh::BankTile> til;
     int64_t til_n = -1;                         // the window count d_til describes
     for (int i = 0; i < n_ids; ++i) {
         if (covered[i]) continue;
         const oww_ctx::BankHead& bh = h->bank[ids[i]];
-        const owd::Slab sl = owd::slab((int64_t)B * nw, bh.T, budget);
-        for (int64_t s = 0; s < sl.n_slabs; ++s) {
-            const int64_t first = s * sl.windows, n = std::min<int64_t>(sl.windows, (int64_t)B * nw - first);
-            if (n != til_n) {
+        const int rc = sw.each(h, bh.T, [&](int64_t first, int64_t n) {
+            if (n != til_n) {                   // (the launches that read the old list, and the gather just enqueued, end first)
                 if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
                 til.clear();
                 for (int64_t o0 = 0; o0 < n; o0 += 128) til.push_back(owh::BankTile{0, (int)o0, (int)std::min<int64_t>(128, n - o0), 0});
                 if (copy_sync(d_til, til.data(), til.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice) != hipSuccess) return fail(OWW_EHIP, "%s: H2D failed", fn);
                 til_n = n;
             }
-            owh::GatherParams gp{};
-            gp.feats = d_feats + (size_t)owd::row_offset(t_max, bh.T) * 96; gp.seq_stride = (long long)n_rows * 96;
-            gp.n_win = nw; gp.first = first; gp.n = n; gp.T = bh.T; gp.slab = d_slab;
-            {
-                Timed t(h, 7);
-                const int64_t pieces = n * bh.T * 24;
-                hipLaunchKernelGGL(owh::dense_gather_kernel, dim3((unsigned)std::min<int64_t>((pieces + 255) / 256, 256 * 16)), dim3(256), 0, h->stream, gp);
-            }
             owh::BankParams bp{};
-            bp.feat = d_slab; bp.ext = 1; bp.TR = bh.T; bp.tiles = d_til; bp.entries = d_ent; bp.heads = h->d_bank_heads + ids[i]; bp.K = 1;
+            bp.feat = sw.d_slab; bp.ext = 1; bp.TR = bh.T; bp.tiles = d_til; bp.entries = d_ent; bp.heads = h->d_bank_heads + ids[i]; bp.K = 1;
             bp.raw = d_sc; bp.range_flag = h->d_range; bp.fscale = fscale;
             {
                 Timed t(h, 6);
@@ -2096,11 +2083,41 @@ int bank_score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, i
                 Timed t(h, 7);
                 hipLaunchKernelGGL(owh::dense_bank_slab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, sp);
             }
-        }
+            return 0;
+        });
+        if (rc) return drained(h, rc);
     }
     if (hipGetLastError() != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: a fallback launch failed", fn));
     return drained(h, 0);           // (the slab and the lists go with this scope)
 }
+
+// The device side of a dense entry's features and score matrix: the caller's buffer where it is on the device, a copy owned here
+// where it is not.  The matrix entries use open() and finish(); oww_bank_score_stats, whose outputs are its own, the features half.
+struct DenseIO {
+    oww_ctx* h; const char* fn;
+    DevBuf<float> d_f, d_o;
+    const float* feats = nullptr; float* out = nullptr;     // on the device
+    float* host_out = nullptr; uint64_t ob = 0;             // where `out` goes in the end (nullptr: it is the caller's already)
+    // src on the device is used as it is; else a buffer of fb bytes, which upload() fills from src.  True = out of device memory.
+    bool alloc_feats(const float* src, int on_device, uint64_t fb) {
+        if (!on_device && d_f.alloc(fb / 4)) return true;
+        feats = on_device ? src : d_f.get();
+        return false;
+    }
+    hipError_t upload(const float* src, uint64_t fb) { return src != feats ? copy_async(d_f, src, fb, hipMemcpyHostToDevice, h->stream) : hipSuccess; }
+    // both buffers, and the features on their way in (src == nullptr: a buffer that the caller fills)
+    int open(const float* src, int src_on_device, uint64_t fb, float* dst, int dst_on_device, uint64_t ob_) {
+        if (alloc_feats(src, src_on_device, fb) || (!dst_on_device && d_o.alloc(ob_ / 4)))
+            return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features, %llu bytes of scores)", fn, (unsigned long long)fb, (unsigned long long)ob_);
+        out = dst_on_device ? dst : d_o.get(); host_out = dst_on_device ? nullptr : dst; ob = ob_;
+        if (src && upload(src, fb) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
+        return 0;
+    }
+    // the matrix on its way out; then the end of the call (oww_score_clips copies its embeddings between the two)
+    int download() { return host_out && copy_async(host_out, d_o, ob, hipMemcpyDeviceToHost, h->stream) != hipSuccess ? drained(h, fail(OWW_EHIP, "%s: D2H failed", fn)) : 0; }
+    int settle() { return hipStreamSynchronize(h->stream) != hipSuccess ? fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError())) : range_check(h, fn); }
+    int finish() { const int rc = download(); return rc ? rc : settle(); }
+};
 
 }  // namespace
 
@@ -3135,17 +3152,10 @@ int oww_score_features(oww_ctx* h, const float* feats, int feats_on_device, int3
     const int t_max = dense_t_max(h);
     if (int rc = owd::features_check(fn, feats, feats_on_device, B, n_rows, t_max, h->NL, out, out_on_device)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
-    const int64_t nw = owd::n_win(n_rows, t_max);
-    const uint64_t fb = owd::feats_bytes(B, n_rows), ob = owd::out_bytes(B, nw, h->NL);
-    DevBuf<float> d_f, d_o;
-    if ((!feats_on_device && d_f.alloc(fb / 4)) || (!out_on_device && d_o.alloc(ob / 4)))
-        return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features, %llu bytes of scores)", fn, (unsigned long long)fb, (unsigned long long)ob);
-    if (!feats_on_device && copy_async(d_f, feats, fb, hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
-    float* o = out_on_device ? out : d_o.get();
-    if (int rc = score_device(h, fn, feats_on_device ? feats : d_f.get(), B, n_rows, o)) return drained(h, rc);
-    if (!out_on_device && copy_async(out, d_o, ob, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: D2H failed", fn));
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
-    return range_check(h, fn);
+    DenseIO io{h, fn};
+    if (int rc = io.open(feats, feats_on_device, owd::feats_bytes(B, n_rows), out, out_on_device, owd::out_bytes(B, owd::n_win(n_rows, t_max), h->NL))) return rc;
+    if (int rc = score_device(h, fn, io.feats, B, n_rows, io.out)) return drained(h, rc);
+    return io.finish();
     OWW_GUARD_END
 }
 
@@ -3158,19 +3168,15 @@ int oww_score_clips(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t B
     if (int rc = owd::clips_check(fn, pcm, B, n, h->Spad, t_max, h->NL, out)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     const int n_rows = (int)owd::clip_rows(n);
-    const int64_t nw = owd::n_win(n_rows, t_max);
-    const uint64_t fb = owd::feats_bytes(B, n_rows), ob = owd::out_bytes(B, nw, h->NL);
-    DevBuf<float> d_f, d_o;
-    if (d_f.alloc(fb / 4) || (!out_on_device && d_o.alloc(ob / 4)))
-        return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features, %llu bytes of scores)", fn, (unsigned long long)fb, (unsigned long long)ob);
-    if (int rc = oww_embed_clips(h, pcm, pcm_on_device, B, n, d_f, 1)) return rc;      // parks and restores streams [0, B); drained on return
-    float* o = out_on_device ? out : d_o.get();
-    if (int rc = score_device(h, fn, d_f, B, n_rows, o)) return drained(h, rc);
-    if (!out_on_device && copy_async(out, d_o, ob, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: D2H failed", fn));
-    if (emb_out && copy_async(emb_out, d_f, fb, emb_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+    const uint64_t fb = owd::feats_bytes(B, n_rows);
+    DenseIO io{h, fn};
+    if (int rc = io.open(nullptr, 0, fb, out, out_on_device, owd::out_bytes(B, owd::n_win(n_rows, t_max), h->NL))) return rc;
+    if (int rc = oww_embed_clips(h, pcm, pcm_on_device, B, n, io.d_f, 1)) return rc;   // parks and restores streams [0, B); drained on return
+    if (int rc = score_device(h, fn, io.feats, B, n_rows, io.out)) return drained(h, rc);
+    if (int rc = io.download()) return rc;
+    if (emb_out && copy_async(emb_out, io.d_f, fb, emb_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream) != hipSuccess)
         return drained(h, fail(OWW_EHIP, "%s: embedding copy failed", fn));
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
-    return range_check(h, fn);
+    return io.settle();
     OWW_GUARD_END
 }
 
@@ -3197,17 +3203,11 @@ int oww_bank_score_features(oww_ctx* h, const float* feats, int feats_on_device,
     if (int rc = owd::bank_ids_check(fn, bank_ids, n_ids, bank_live_T(h).data(), h->bank_cap, &t_max)) return rc;
     if (int rc = owd::bank_features_check(fn, feats, feats_on_device, B, n_rows, t_max, n_ids, out, out_on_device)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
-    const int64_t nw = owd::n_win(n_rows, t_max);
-    const uint64_t fb = owd::feats_bytes(B, n_rows), ob = owd::out_bytes(B, nw, n_ids);
-    DevBuf<float> d_f, d_o;
-    if ((!feats_on_device && d_f.alloc(fb / 4)) || (!out_on_device && d_o.alloc(ob / 4)))
-        return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features, %llu bytes of scores)", fn, (unsigned long long)fb, (unsigned long long)ob);
-    if (!feats_on_device && copy_async(d_f, feats, fb, hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
-    float* o = out_on_device ? out : d_o.get();
-    if (int rc = bank_score_device(h, fn, feats_on_device ? feats : d_f.get(), B, n_rows, bank_ids, n_ids, t_max, o, nullptr, nullptr, nullptr, nullptr)) return rc;
-    if (!out_on_device && copy_async(out, d_o, ob, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: D2H failed", fn));
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
-    return range_check(h, fn);
+    DenseIO io{h, fn};
+    if (int rc = io.open(feats, feats_on_device, owd::feats_bytes(B, n_rows), out, out_on_device, owd::out_bytes(B, owd::n_win(n_rows, t_max), n_ids))) return rc;
+    // (drained: bank_score_device returns undrained where its head list could not be allocated or uploaded, with the features in flight)
+    if (int rc = bank_score_device(h, fn, io.feats, B, n_rows, bank_ids, n_ids, t_max, io.out, nullptr, nullptr, nullptr, nullptr)) return drained(h, rc);
+    return io.finish();
     OWW_GUARD_END
 }
 
@@ -3224,15 +3224,16 @@ int oww_bank_score_stats(oww_ctx* h, const float* feats, int feats_on_device, in
     const size_t cells = (size_t)B * (size_t)n_ids;
     std::vector<float> thr((size_t)n_ids, 0.5f);                // train.py:100's default
     if (thresholds) thr.assign(thresholds, thresholds + n_ids);
-    DevBuf<float> d_f, d_thr; DevBuf<int> d_count; DevBuf<unsigned long long> d_key;
-    if ((!feats_on_device && d_f.alloc(fb / 4)) || d_thr.alloc((size_t)n_ids) || d_count.alloc(cells) || d_key.alloc(cells))
+    DenseIO io{h, fn};
+    DevBuf<float> d_thr; DevBuf<int> d_count; DevBuf<unsigned long long> d_key;
+    if (io.alloc_feats(feats, feats_on_device, fb) || d_thr.alloc((size_t)n_ids) || d_count.alloc(cells) || d_key.alloc(cells))
         return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features, %llu bytes of statistics)", fn, (unsigned long long)fb,
                     (unsigned long long)owd::stats_bytes(B, n_ids));
-    if ((!feats_on_device && copy_async(d_f, feats, fb, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
+    if (io.upload(feats, fb) != hipSuccess ||
         copy_async(d_thr, thr.data(), thr.size() * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemsetAsync(d_count, 0, cells * sizeof(int), h->stream) != hipSuccess ||
         hipMemsetAsync(d_key, 0, cells * sizeof(unsigned long long), h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
-    if (int rc = bank_score_device(h, fn, feats_on_device ? feats : d_f.get(), B, n_rows, bank_ids, n_ids, t_max, nullptr, d_thr, thr.data(), d_count, d_key))
+    if (int rc = bank_score_device(h, fn, io.feats, B, n_rows, bank_ids, n_ids, t_max, nullptr, d_thr, thr.data(), d_count, d_key))
         return drained(h, rc);
     std::vector<unsigned long long> key(cells);
     if (copy_async(count, d_count, cells * sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||

@@ -9,22 +9,33 @@
 // (owd::split_passes) -- on the group's packed weights as they are (FastGroup::d_w1hx, hx_net): a pass reads its own nets' blocks of
 // every k-step chunk.  At full size the heads launches are bound by the weight stream L2 -> LDS, once per workgroup; 256 windows per
 // workgroup halve it against heads_hx_kernel's 128, which the compact rows in LDS make room for.
-//  * staging: rows [w0, w0 + 32 WG + T - 1) of the sequence (clamped to its last row: the windows that would read beyond it are not
-//    stored) -> LDS, row stride owd::kRowWords = 100 words, unit (c, j) of a row = 8 hi halves | 8 lo halves (owd::unit_word): the 16
-//    positions of a tile, one row apart, read 16 distinct groups of 4 banks.
+//  * staging (dense_stage_rows): rows [w0, w0 + 32 WG + T - 1) of the sequence (clamped to its last row: the windows that would read
+//    beyond it are not stored) -> LDS, row stride owd::kRowWords = 100 words, unit (c, j) of a row = 8 hi halves | 8 lo halves
+//    (owd::unit_word): the 16 positions of a tile, one row apart, read 16 distinct groups of 4 banks.
 //  * k loop: k-step ks = (row tr = ks / 3, features 32 (ks % 3) ..) of every window; position pos of tile t of wave v reads staged row
 //    32 v + 16 t + pos + tr.  The weight chunks stream L2 -> LDS through a ring of NBUF slots, each its OWN LDS object (hslot<>, see
-//    heads_hx_kernel: one array would make every read of the current slot wait for the chunk just issued).  The same MFMAs in the same
-//    order as heads_hx_kernel -- per k-step and pair of hidden tiles (A hi, B hi), (A hi, B lo), (A lo, B hi), tile 0 then tile 1 --
-//    so an accumulator holds bit for bit what heads_hx_kernel's holds for the materialised window.
+//    heads_hx_kernel: one array would make every read of the current slot wait for the chunk just issued); dense_ring_prologue issues
+//    the first NBUF - 1.  The same MFMAs in the same order as heads_hx_kernel -- per k-step and pair of hidden tiles (A hi, B hi),
+//    (A hi, B lo), (A lo, B hi), tile 0 then tile 1 -- so an accumulator holds bit for bit what heads_hx_kernel's holds for the
+//    materialised window.
 //  * barrier discipline: heads_hx_kernel's wait for chunk ks + 1 rides on its feature loads (younger than the chunk, in-order return).
 //    Here no VMEM load follows the chunks, so the wait is counted: every wave issues exactly 8 NN / WG DMA instructions per chunk
 //    (issue_chunk_uniform), D = NBUF - 1 chunks fly ahead, and at the end of k-step ks "at most (D - 1) x 8 NN / WG outstanding" means this
 //    wave's part of chunk ks + 1 has landed; the bare s_barrier (no release fence: it would be vmcnt(0)) publishes the other waves'
 //    parts.  The slot refilled in k-step ks is the one k-step ks - 1 read: every wave passed that k-step's barrier with its LDS reads
-//    returned (lgkmcnt(0)).  The last D k-steps wait vmcnt(0).
+//    returned (lgkmcnt(0)).  The last D k-steps wait vmcnt(0).  So the k loop must be entered with the first D chunks landed in every
+//    wave and nothing else outstanding in vmcnt, and it ends without a barrier.
 //  * tail: net64_score, the function form of heads_hx_kernel's narrow tail that the bank kernel already runs bit for bit, then the
 //    gating of heads_hx_kernel.  No post-processing: dense scores are raw head outputs.
+// heads_dense_bank_kernel<NBUF, WG> (further down) is the same over the head bank, with the head a loop variable.  The two kernels
+// share the staging, the ring prologue and the statistics' commit step as functions.  The k loop stays INLINE in both, two copies of
+// one text (the bank's reads staged row + t_s - T and strides its own CHUNK): as a shared function -- scalars by value or by
+// reference, the stride an argument or a template policy, the staged rows, the lane's first row or the B-operand loader handed in by
+// the caller, acc and the B operands caller-owned -- the fixed kernel's twelve instantiations keep their registers, but every form
+// moved the bank kernel's register allocation: 19 to 28 SGPR spills where it has 18 / 26, and 40 to 160 instructions more per
+// instantiation (outside the k loop: the statistics pointers no longer stay in SGPRs across it).  The same hazard as the note above
+// heads_gemm1 (owwhip_hx.h) records for heads_hx_kernel; a change to one k loop is made in the other by hand, and
+// tests/test_dense_bank_gpu.py holds the two to the same bits.
 // A workgroup's LDS (108 KB of rows at T = 16 plus the ring) leaves no room for a second one on the CU, so the ring is as deep as fits
 // (owd::geometry: 4, 3 or 2 slots) -- chunks in flight and the second wave of each SIMD, not neighbours, hide the L2 round trip.
 //
@@ -36,6 +47,50 @@
 #include "owwhip_hx.h"
 
 namespace owh {
+
+// ---- the pieces both sliding kernels are made of ------------------------------------------------------------------------------------
+// Rows [w0, w0 + 32 WG + t_stage - 1) of `seq` (clamped to row n_rows - 1) -> dense_rows: scale, split, store in B-operand order, four
+// units per thread in flight.  No barrier of its own: the caller publishes the rows.
+template <int WG>
+__device__ __forceinline__ void dense_stage_rows(float* dense_rows, const float* seq, const int w0, const int n_rows, const int t_stage, const float fsc) {
+    using namespace owr;
+    const int NU = (32 * WG + t_stage - 1) * 12;
+    for (int u0 = threadIdx.x; u0 < NU; u0 += 4 * 64 * WG) {
+        f32x4 r[4][2];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int u = min(u0 + q * 64 * WG, NU - 1);
+            const int row = u / 12, unit = u - row * 12;
+            const float* src = seq + (size_t)min(w0 + row, n_rows - 1) * 96 + unit * 8;
+            r[q][0] = *reinterpret_cast<const f32x4*>(src);
+            r[q][1] = *reinterpret_cast<const f32x4*>(src + 4);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int u = u0 + q * 64 * WG;
+            if (u >= NU) continue;
+            const int row = u / 12, unit = u - row * 12;
+            const Op o = split_pair<false>(r[q][0] * fsc, r[q][1] * fsc);
+            float* dst = dense_rows + owd::unit_word(row, unit);
+            *reinterpret_cast<f16x8*>(dst) = o.h;
+            *reinterpret_cast<f16x8*>(dst + 4) = o.l;
+        }
+    }
+}
+
+// The first D = NBUF - 1 k-step chunks of w1hx (NCT hidden tiles; chunk_stride floats apart) into ring slots 0 .. D-1.  (A net has
+// 3 T >= 3 >= D k-steps: every prologue chunk exists.)
+template <int NCT, int NBUF, int WG>
+__device__ __forceinline__ void dense_ring_prologue(const float* w1hx, const int chunk_stride, const int wave, const int lane) {
+#pragma unroll
+    for (int c = 0; c < NBUF - 1; ++c) issue_chunk_uniform<NCT * 2, WG>(w1hx + (size_t)c * chunk_stride, hslot_at<NCT * 2 * 256, NBUF - 1>(c), wave, lane);
+}
+
+// the last step of a wave's statistics reduction, for the lane that holds the wave's hits and its largest key
+__device__ __forceinline__ void dense_stats_commit(int* count, unsigned long long* key_out, const size_t at, const int hits, const unsigned long long key) {
+    if (hits) atomicAdd(count + at, hits);
+    if (key) atomicMax(key_out + at, key);
+}
 
 struct DenseParams {
     const float* feats;         // [B][..][96]: row 0 of window 0 of this group (the group's row offset t_max - T applied)
@@ -68,36 +123,8 @@ __global__ __launch_bounds__(64 * WG, 1) void heads_dense_kernel(DenseParams p) 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int KST = p.T * 3;                    // (>= 3 > D - 1: every prologue chunk exists)
     const int b = blockIdx.x / p.tiles, w0 = (blockIdx.x - b * p.tiles) * TILE;
-#pragma unroll
-    for (int c = 0; c < D; ++c) issue_chunk_uniform<NBLK, WG>(p.w1hx + (size_t)c * p.chunk_stride, hslot_at<CHUNK, NBUF - 1>(c), wave, lane);
-
-    // ---- stage the tile's rows: scale, split, store in B-operand order (four units per thread in flight)
-    {
-        const float* seq = p.feats + (size_t)b * p.seq_stride;
-        const int NU = (TILE + p.T - 1) * 12;
-        const float fsc = p.fscale;
-        for (int u0 = threadIdx.x; u0 < NU; u0 += 4 * 64 * WG) {
-            f32x4 r[4][2];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int u = min(u0 + q * 64 * WG, NU - 1);
-                const int row = u / 12, unit = u - row * 12;
-                const float* src = seq + (size_t)min(w0 + row, p.n_rows - 1) * 96 + unit * 8;
-                r[q][0] = *reinterpret_cast<const f32x4*>(src);
-                r[q][1] = *reinterpret_cast<const f32x4*>(src + 4);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int u = u0 + q * 64 * WG;
-                if (u >= NU) continue;
-                const int row = u / 12, unit = u - row * 12;
-                const Op o = split_pair<false>(r[q][0] * fsc, r[q][1] * fsc);
-                float* dst = dense_rows + owd::unit_word(row, unit);
-                *reinterpret_cast<f16x8*>(dst) = o.h;
-                *reinterpret_cast<f16x8*>(dst + 4) = o.l;
-            }
-        }
-    }
+    dense_ring_prologue<NCT, NBUF, WG>(p.w1hx, p.chunk_stride, wave, lane);
+    dense_stage_rows<WG>(dense_rows, p.feats + (size_t)b * p.seq_stride, w0, p.n_rows, p.T, p.fscale);
     __syncthreads();                            // rows staged, prologue chunks landed (the fence drains them: once per tile)
 
     f32x4 acc[NCT][NT];
@@ -224,18 +251,16 @@ __global__ void dense_gather_kernel(GatherParams p) {
 // ---- dense scoring over the head bank (include/owwhip.h: oww_bank_score_features, oww_bank_score_stats) --------------
 // heads_dense_bank_kernel<NBUF, WG>: heads_dense_kernel<1, NBUF, WG> with the head a loop variable.  ONE launch covers every listed
 // narrow bank head (HT = 4): block = (head slice, sequence, tile) (owd::bank_plan), and a workgroup stages its tile's rows once -- the
-// rows of the LONGEST head of the launch, t_s: 32 WG + t_s - 1 of them from row w0 + t_max - t_s on, same layout, split and scale --
-// and then walks the hpw heads of its slice, each with its own BankHeadDev (w1hx, net, T) from the handle's bank:
+// rows of the LONGEST head of the launch, t_s: 32 WG + t_s - 1 of them from row w0 + t_max - t_s on (dense_stage_rows) -- and then
+// walks the hpw heads of its slice, each with its own BankHeadDev (w1hx, net, T) from the handle's bank:
 //  * a head of length T reads its own last T rows of every window: its k-step ks takes the B operand from staged row
 //    16 (2 wave + t) + pos + (t_s - T) + ks / 3 (owd::bank_staged_row), then the same MFMA triplets in the same order and net64_score<1>,
 //    so a score is bit for bit heads_bank_kernel's, and with it the fixed heads kernel's, for the materialised window.
-//  * hand-over of the ring.  A head's last k-step ends without a barrier (nothing follows it in heads_dense_kernel).  Here the next
-//    head's prologue refills slots 0 .. D-1, one of which the slowest wave may still be reading: so lgkmcnt(0) + a bare s_barrier
-//    first, then the next head's first D chunks are issued -- under this head's tail (net64_score, the store or the reduction), which
-//    covers their L2 round trip -- and the next head begins with vmcnt(0) + __syncthreads(): the chunks have landed in every wave and
-//    the tail's stores and atomics have retired, so the k loop starts from "nothing outstanding", which is what its counted waits
-//    (every wave exactly KDMA DMA instructions per chunk, D - 1 chunks in flight behind the one waited for) assume.  Inside a head the
-//    discipline is heads_dense_kernel's, unchanged: counted wait, lgkmcnt(0), bare s_barrier; every ring slot its own LDS object.
+//  * hand-over of the ring.  A head's k loop ends without a barrier, and the next head's prologue refills slots 0 .. D-1, one of which
+//    the slowest wave may still be reading: so lgkmcnt(0) + a bare s_barrier first, then the next head's first D chunks are issued --
+//    under this head's tail (net64_score, the store or the reduction), which covers their L2 round trip -- and the next head begins
+//    with vmcnt(0) + __syncthreads(): the chunks have landed in every wave and the tail's stores and atomics have retired, which is
+//    the k loop's entry condition (the head of this file).  Inside a head the discipline is heads_dense_kernel's, unchanged.
 //  * matrix mode (out != nullptr): out[b][w][col] = score.  Statistics mode: count of scores >= thr[col], and the maximum with the
 //    first window that attains it as ONE integer key (owd::stat_key) -- reduced over the wave's 32 windows in registers, then one
 //    atomicAdd and one 64-bit atomicMax per wave and head.  Integer atomics commute: the result does not depend on scheduling.
@@ -275,39 +300,8 @@ __global__ __launch_bounds__(64 * WG, 1) void heads_dense_bank_kernel(DenseBankP
     const int slice = owd::bank_block_slice(blockIdx.x, p.tiles), tile = owd::bank_block_tile(blockIdx.x, p.tiles);
     const int b = tile / p.seq_tiles, w0 = (tile - b * p.seq_tiles) * TILE;
     const int i0 = owd::bank_slice_first(slice, p.hpw), nh = owd::bank_slice_count(slice, p.hpw, p.n_items);
-    auto prologue = [&](const float* w1hx) {    // (KST >= 3 >= D: every prologue chunk exists)
-#pragma unroll
-        for (int c = 0; c < D; ++c) issue_chunk_uniform<NBLK, WG>(w1hx + (size_t)c * CHUNK, hslot_at<CHUNK, NBUF - 1>(c), wave, lane);
-    };
-    prologue(p.heads[p.items[i0].head].w1hx);
-
-    // ---- stage the tile's rows once for all heads of the slice (heads_dense_kernel's staging with T = t_s)
-    {
-        const float* seq = p.feats + (size_t)b * p.seq_stride;
-        const int NU = (TILE + p.t_s - 1) * 12;
-        const float fsc = p.fscale;
-        for (int u0 = threadIdx.x; u0 < NU; u0 += 4 * 64 * WG) {
-            f32x4 r[4][2];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int u = min(u0 + q * 64 * WG, NU - 1);
-                const int row = u / 12, unit = u - row * 12;
-                const float* src = seq + (size_t)min(w0 + row, p.n_rows - 1) * 96 + unit * 8;
-                r[q][0] = *reinterpret_cast<const f32x4*>(src);
-                r[q][1] = *reinterpret_cast<const f32x4*>(src + 4);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int u = u0 + q * 64 * WG;
-                if (u >= NU) continue;
-                const int row = u / 12, unit = u - row * 12;
-                const Op o = split_pair<false>(r[q][0] * fsc, r[q][1] * fsc);
-                float* dst = dense_rows + owd::unit_word(row, unit);
-                *reinterpret_cast<f16x8*>(dst) = o.h;
-                *reinterpret_cast<f16x8*>(dst + 4) = o.l;
-            }
-        }
-    }
+    dense_ring_prologue<NCT, NBUF, WG>(p.heads[p.items[i0].head].w1hx, CHUNK, wave, lane);
+    dense_stage_rows<WG>(dense_rows, p.feats + (size_t)b * p.seq_stride, w0, p.n_rows, p.t_s, p.fscale);       // once for all heads of the slice
 
     lanemask_t bad = 0;
     for (int r = 0; r < nh; ++r) {
@@ -389,7 +383,7 @@ __global__ __launch_bounds__(64 * WG, 1) void heads_dense_bank_kernel(DenseBankP
         // ---- hand-over: every wave's reads of the last slots have returned before the next head's prologue refills slots 0 .. D-1
         if (r + 1 < nh) {
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            prologue(p.heads[p.items[i0 + r + 1].head].w1hx);
+            dense_ring_prologue<NCT, NBUF, WG>(p.heads[p.items[i0 + r + 1].head].w1hx, CHUNK, wave, lane);
         }
 
         // ---- tail (the next head's first chunks fly under it)
@@ -429,11 +423,7 @@ __global__ __launch_bounds__(64 * WG, 1) void heads_dense_bank_kernel(DenseBankP
                 const unsigned long long o = __shfl_xor(key, m);
                 key = o > key ? o : key;
             }
-            if (lane == 0) {
-                const size_t at = (size_t)b * p.n_ids + it.col;
-                if (hits) atomicAdd(p.count + at, hits);
-                if (key) atomicMax(p.key + at, key);
-            }
+            if (lane == 0) dense_stats_commit(p.count, p.key, (size_t)b * p.n_ids + it.col, hits, key);
         }
     }
     raise_range_flag(bad, p.range_flag);        // (position unknown: a window is no stream)
@@ -462,6 +452,7 @@ __global__ void dense_bank_slab_kernel(BankSlabParams p) {
     const long long b_first = (p.first + i0) / p.n_win, b_last = (p.first + min(i0 + 63, p.n - 1)) / p.n_win;
     unsigned long long key = valid ? owd::stat_key(__float_as_uint(sc), (unsigned)w) : 0ull;
     const bool hit = valid && sc >= p.thr;
+    const size_t at = (size_t)b * p.n_ids + p.col;
     if (b_first == b_last) {
         const int hits = __popcll(__ballot(hit));
 #pragma unroll
@@ -469,13 +460,8 @@ __global__ void dense_bank_slab_kernel(BankSlabParams p) {
             const unsigned long long o = __shfl_xor(key, m);
             key = o > key ? o : key;
         }
-        if ((threadIdx.x & 63) == 0) {
-            const size_t at = (size_t)b * p.n_ids + p.col;
-            if (hits) atomicAdd(p.count + at, hits);
-            if (key) atomicMax(p.key + at, key);
-        }
+        if ((threadIdx.x & 63) == 0) dense_stats_commit(p.count, p.key, at, hits, key);
     } else if (valid) {
-        const size_t at = (size_t)b * p.n_ids + p.col;
         if (hit) atomicAdd(p.count + at, 1);
         atomicMax(p.key + at, key);
     }

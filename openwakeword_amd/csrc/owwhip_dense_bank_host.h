@@ -104,16 +104,14 @@ inline int bank_sizes_check(const char* fn, int64_t B, int64_t n_rows, int64_t t
 inline int bank_features_check(const char* fn, const void* feats, int feats_on_device, int64_t B, int64_t n_rows, int64_t t_max, int64_t n_ids,
                                const void* out, int out_on_device) {
     if (!feats || !out || B < 1) return fail(OWW_EINVAL, "%s: bad argument (B = %lld, null features or output)", fn, (long long)B);
-    if (int rc = shape_check(fn, n_rows, t_max)) return rc;
-    if (feats_on_device && (reinterpret_cast<uintptr_t>(feats) & 15)) return fail(OWW_EINVAL, "%s: device features must be 16-byte aligned", fn);
+    if (int rc = rows_check(fn, feats, feats_on_device, n_rows, t_max)) return rc;
     if (out_on_device && (reinterpret_cast<uintptr_t>(out) & 15)) return fail(OWW_EINVAL, "%s: a device output must be 16-byte aligned", fn);
     return bank_sizes_check(fn, B, n_rows, t_max, n_ids, true);
 }
 inline int bank_stats_check(const char* fn, const void* feats, int feats_on_device, int64_t B, int64_t n_rows, int64_t t_max, int64_t n_ids,
                             const float* thresholds, const void* count, const void* max, const void* argmax) {
     if (!feats || !count || !max || !argmax || B < 1) return fail(OWW_EINVAL, "%s: bad argument (B = %lld, null features or output)", fn, (long long)B);
-    if (int rc = shape_check(fn, n_rows, t_max)) return rc;
-    if (feats_on_device && (reinterpret_cast<uintptr_t>(feats) & 15)) return fail(OWW_EINVAL, "%s: device features must be 16-byte aligned", fn);
+    if (int rc = rows_check(fn, feats, feats_on_device, n_rows, t_max)) return rc;
     if (thresholds)
         for (int64_t i = 0; i < n_ids; ++i)
             if (std::isnan(thresholds[i])) return fail(OWW_EINVAL, "%s: threshold %lld is NaN", fn, (long long)i);

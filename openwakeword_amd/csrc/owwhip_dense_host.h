@@ -121,11 +121,16 @@ inline int shape_check(const char* fn, int64_t n_rows, int64_t t_max) {
     if (n_rows < t_max) return fail(OWW_EINVAL, "%s: n_rows = %lld is less than one window (t_max = %lld)", fn, (long long)n_rows, (long long)t_max);
     return 0;
 }
+// a feature matrix of any entry, fixed heads or bank: one window at least, and aligned where it is the caller's device buffer
+inline int rows_check(const char* fn, const void* feats, int feats_on_device, int64_t n_rows, int64_t t_max) {
+    if (int rc = shape_check(fn, n_rows, t_max)) return rc;
+    if (feats_on_device && (reinterpret_cast<uintptr_t>(feats) & 15)) return fail(OWW_EINVAL, "%s: device features must be 16-byte aligned", fn);
+    return 0;
+}
 inline int features_check(const char* fn, const void* feats, int feats_on_device, int64_t B, int64_t n_rows, int64_t t_max, int64_t n_labels,
                           const void* out, int out_on_device) {
     if (!feats || !out || B < 1) return fail(OWW_EINVAL, "%s: bad argument (B = %lld, null features or output)", fn, (long long)B);
-    if (int rc = shape_check(fn, n_rows, t_max)) return rc;
-    if (feats_on_device && (reinterpret_cast<uintptr_t>(feats) & 15)) return fail(OWW_EINVAL, "%s: device features must be 16-byte aligned", fn);
+    if (int rc = rows_check(fn, feats, feats_on_device, n_rows, t_max)) return rc;
     (void)out_on_device;
     const int64_t nw = n_win(n_rows, t_max);
     const uint64_t fb = feats_bytes(B, n_rows), ob = out_bytes(B, nw, n_labels);
