@@ -21,6 +21,10 @@
 #include "owwhip_pack.h"
 #include "owwhip_ingest.h"
 #include "owwhip_mem.h"
+#include "owwhip_masked_host.h"
+#include "owwhip_bank_host.h"
+#include "owwhip_verifier_host.h"
+#include "owwhip_state_host.h"
 #include "owwhip_kernels.h"
 #include "owwhip_rr.h"
 #include "owwhip_hx.h"
@@ -332,10 +336,7 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     DevBuf<uint32_t> d_bank_npred;
     DevBuf<owh::BankHeadDev> d_bank_heads; DevBuf<int> d_bank_pat; DevBuf<float> d_bank_thr;
     DevBuf<owh::BankTile> d_bank_tiles; DevBuf<int> d_bank_entries;
-    // routing table, per width class (0: <= 64 hidden units, 1: <= 128): tiles [tile0, tile0 + ntiles) of d_bank_tiles, WG waves each
-    int bank_ntiles[2] = {}, bank_tile0[2] = {}, bank_wg[2] = {1, 1}, bank_entries_n[2] = {};
-    std::vector<std::pair<int, int>> bank_head_tiles[2];   // OWH_BANK_PER_HEAD builds: [first tile, count] of every subscribed head
-    double bank_wbytes = 0.0;                    // first-layer weight bytes one step streams over all tiles
+    owb::Route bank_rt;                          // the routing table as uploaded (bank_route; owwhip_bank_host.h)
     // per-stream custom verifiers (oww_verifier_*): a pool of folded verifiers, one (verifier, threshold) per (stream, fixed column) and
     // per (stream, bank slot), and the device list of the pairs to verify that stream_verifier_kernel walks
     int vpool_cap = 0;                           // 0 = not configured (oww_verifier_configure)
@@ -349,10 +350,10 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     DevBuf<SvEntry> d_svlist; int sv_n = 0;      // [S * (NL + K)] capacity; sv_n entries in use
     DevBuf<unsigned long long> d_sv_eval;        // evaluations of the last step
     // stream state records (oww_state_*, oww_move_streams; owwhip_state.h): built by the first of those calls, nothing before it
-    struct StateGroupSec { float* live /* a view */; int spg, ppr; bool il; uint32_t block_words, off; };
     bool st_ready = false;
     std::vector<ows::FlatSection> st_flat;       // host copy of d_st_flat
-    std::vector<StateGroupSec> st_group;
+    std::vector<ows::GroupSection> st_group;     // (live: a view)
+    bool st_levels[4] = {};                      // which of ows::kStateLevels a group section uses
     DevBuf<ows::FlatSection> d_st_flat;
     uint32_t st_record_words = 0, st_flat_quads = 0;
     uint64_t st_fp = 0;                          // fingerprint of family, layouts, ring sizes, scales and weights
@@ -772,16 +773,16 @@ int rccl_load() {
 void comm_release(oww_ctx* h);
 
 // ---- head bank: the routed heads launch (one per width class that has subscribers) and its post-processing
-bool bank_active(const oww_ctx* h) { return h->bank_ntiles[0] + h->bank_ntiles[1] > 0; }
+bool bank_active(const oww_ctx* h) { return !h->bank_rt.tiles.empty(); }
 
 void launch_bank_tiles(oww_ctx* h, owh::BankParams q, int c, int tile0, int ntiles) {
     q.tiles = h->d_bank_tiles + tile0;
-    const dim3 grid(ntiles), block(64 * h->bank_wg[c]);
+    const dim3 grid(ntiles), block(64 * h->bank_rt.wg[c]);
     if (c == 0) {
-        if (h->bank_wg[c] == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 4>), grid, block, 0, h->stream, q);
+        if (h->bank_rt.wg[c] == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 4>), grid, block, 0, h->stream, q);
         else hipLaunchKernelGGL((owh::heads_bank_kernel<1, 4>), grid, block, 0, h->stream, q);
     } else {
-        if (h->bank_wg[c] == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 8>), grid, block, 0, h->stream, q);
+        if (h->bank_rt.wg[c] == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 8>), grid, block, 0, h->stream, q);
         else hipLaunchKernelGGL((owh::heads_bank_kernel<1, 8>), grid, block, 0, h->stream, q);
     }
 }
@@ -793,12 +794,12 @@ int run_bank(oww_ctx* h, const StepArgs& a, bool accumulate_max) {
     q.raw = h->d_bank_raw; q.accumulate_max = accumulate_max ? 1 : 0; q.range_flag = h->d_range; q.stream_on = a.on;
     q.fscale = std::ldexp(1.0f, h->hx_efeat);
     for (int c = 0; c < 2; ++c) {
-        if (!h->bank_ntiles[c]) continue;
+        if (!h->bank_rt.ntiles[c]) continue;
 #if OWH_BANK_PER_HEAD
-        for (const auto& [t0, nt] : h->bank_head_tiles[c]) { Timed t(h, 6); launch_bank_tiles(h, q, c, t0, nt); }   // (d) of tools/bench_head_bank.py
+        for (const auto& [t0, nt] : h->bank_rt.head_tiles[c]) { Timed t(h, 6); launch_bank_tiles(h, q, c, t0, nt); }   // (d) of tools/bench_head_bank.py
 #else
         Timed t(h, 6);
-        launch_bank_tiles(h, q, c, h->bank_tile0[c], h->bank_ntiles[c]);
+        launch_bank_tiles(h, q, c, h->bank_rt.tile0[c], h->bank_rt.ntiles[c]);
 #endif
     }
     HIPCHK(hipGetLastError());
@@ -884,20 +885,15 @@ int launch_vad(oww_ctx* h, const StepArgs& a, const int16_t* d_pcm, int n_sample
     return 0;
 }
 
-// Lists for a masked step with few participants: [stream ids | C groups | D groups | E groups | VAD groups] into one pinned staging
-// buffer, copied to the device on the compute stream (ordered before the step's kernels), and entered into a (lists, gl, gn).  Returns
-// the number of participants, -1 when the dense launches should be used (more than 7/8 of the streams take part: the lists then save
-// nothing; below that they do even for a mask that touches most groups, and a serving edge that places connections by cohort --
-// serve.py::SlotAllocator -- makes participation per group all-or-nothing, so the launches shrink with the mask), or an OWW_E* code
-// - 100 on failure.  Only a return > 0 fills a.
+// Lists for a masked step with few participants (owwhip_masked_host.h): [stream ids | C groups | D groups | E groups | VAD groups] built
+// straight into one pinned staging buffer, copied to the device on the compute stream (ordered before the step's kernels), and entered
+// into a (lists, gl, gn).  Returns the number of participants, -1 when the dense launches should be used, or an OWW_E* code - 100 on
+// failure.  Only a return > 0 fills a.
 int build_active_lists(oww_ctx* h, const uint8_t* on, StepArgs& a) {
-    const int S = h->S;
-    int n_act = 0;
-    for (int s = 0; s < S; ++s) n_act += on[s] != 0;          // (vectorised by the compiler)
-    if (n_act == 0) return 0;
+    const int S = h->S, n_act = owl::participants(on, S);
+    if (n_act <= 0) return n_act;
     if (!h->hx || !h->fuse || !h->generic_nets.empty() || !h->rnn_nets.empty()) return -1;       // the group lists are read by the default family's launches only
-    if ((long long)n_act * 8 > (long long)S * 7) return -1;
-    const size_t need = (size_t)S + S / 2 + S / 4 + S / 8 + S / 16 + 64;       // (regions of the five lists, see below)
+    const size_t need = owl::lists_capacity(S);
     if (grow(h, h->d_lists, need) != hipSuccess) return fail(OWW_ENOMEM, "oww_step_masked: out of device memory") - 100;
     for (int i = 0; i < 2; ++i) {
         if (need > h->h_lists[i].capacity()) {                    // (its own double buffering: the copy that read the old block has run)
@@ -909,46 +905,12 @@ int build_active_lists(oww_ctx* h, const uint8_t* on, StepArgs& a) {
     const unsigned turn = h->lists_turn++ & 1u;
     (void)hipEventSynchronize(h->lists_ev[turn]);              // the copy that last read this staging buffer has run
     int* out = h->h_lists[turn];
-    // one pass over the mask, eight streams (one 64-bit word = one stage-E group) at a time; the five lists grow side by side in
-    // fixed regions of the staging buffer and are packed afterwards
-    const size_t base[5] = {0, (size_t)S, (size_t)S + S / 2 + 8, (size_t)S + S / 2 + S / 4 + 16, (size_t)S + S / 2 + S / 4 + S / 8 + 24};
-    int n[5] = {0, 0, 0, 0, 0};
-    const int W8 = S / 8;
-    int last_v = -1;
-    auto visit = [&](int s0, const uint8_t* b, int cnt) {        // streams s0 .. s0+cnt-1 (cnt <= 8), at least one of them on
-        const int g8 = s0 / 8;
-        out[base[3] + n[3]++] = g8;
-        if (g8 / 2 != last_v) { last_v = g8 / 2; out[base[4] + n[4]++] = g8 / 2; }
-        for (int q = 0; q < cnt; q += 4) {
-            bool any4 = false;
-            for (int c = q; c < std::min(cnt, q + 4); c += 2) {
-                bool any2 = false;
-                for (int i = c; i < std::min(cnt, c + 2); ++i) if (b[i]) { out[base[0] + n[0]++] = s0 + i; any2 = true; }
-                if (any2) { out[base[1] + n[1]++] = (s0 + c) / 2; any4 = true; }
-            }
-            if (any4) out[base[2] + n[2]++] = (s0 + q) / 4;
-        }
-    };
-    for (int w = 0; w < W8; ++w) {
-        uint64_t v;
-        memcpy(&v, on + (size_t)w * 8, 8);
-        if (v) visit(w * 8, on + (size_t)w * 8, 8);
-    }
-    if (S % 8) {
-        bool any = false;
-        for (int s = W8 * 8; s < S; ++s) any = any || on[s] != 0;
-        if (any) visit(W8 * 8, on + (size_t)W8 * 8, S - W8 * 8);
-    }
-    size_t off = 0;
-    for (int k = 0; k < 5; ++k) {
-        if (base[k] != off) memmove(out + off, out + base[k], (size_t)n[k] * sizeof(int));
-        a.gl[k] = h->d_lists + off; a.gn[k] = n[k];
-        off += (size_t)n[k];
-    }
-    if (off) {
-        if (copy_async(h->d_lists, out, off * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(OWW_EHIP, "oww_step_masked: list upload failed") - 100;
-        (void)hipEventRecord(h->lists_ev[turn], h->stream);
-    }
+    size_t off[5];
+    owl::build_lists(on, S, out, a.gn, off);
+    for (int k = 0; k < 5; ++k) a.gl[k] = h->d_lists + off[k];
+    const size_t total = off[4] + (size_t)a.gn[4];              // (> 0: somebody takes part)
+    if (copy_async(h->d_lists, out, total * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(OWW_EHIP, "oww_step_masked: list upload failed") - 100;
+    (void)hipEventRecord(h->lists_ev[turn], h->stream);
     a.lists = true;
     return n_act;
 }
@@ -1350,13 +1312,8 @@ int selftest_hx(oww_ctx* h, const HxCalib& cal) {
     return 0;
 }
 
-// ---- head bank helpers (oww_bank_*) ---------------------------------------------------------------------------------------------------
-// every queued launch of the handle has finished: the routing table, the bank images and the slot state may change
-int bank_quiesce(oww_ctx* h) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
+// ---- head bank helpers (oww_bank_*): their callers have waited for every queued launch of the handle, so the routing table, the bank
+//      images and the slot state may change -----------------------------------------------------------------------------------------------
 // restart the listed slots (index stream * K + slot): prediction count, ring, raw and final score
 int bank_clear(oww_ctx* h, std::vector<int> slots) {
     std::sort(slots.begin(), slots.end());
@@ -1370,73 +1327,24 @@ int bank_clear(oww_ctx* h, std::vector<int> slots) {
     return 0;
 }
 
-// Routing table from the subscriptions: per width class, each subscribed head's entries (stream * K + slot, ascending) cut into tiles
-// of 32 WG entries; WG = 4 waves (128 entries, one weight stream per 128) when the class's mean group holds >= 96 entries, else one
-// wave (32).  Tiles largest first.  One upload per change; the captured step graph is invalidated (its launches bake the tile count).
+// Routing table from the subscriptions (owb::route: owwhip_bank_host.h).  One upload per change; the captured step graph is invalidated
+// (its launches bake the tile count).
 int bank_route(oww_ctx* h) {
-    const int K = h->bank_K, cap = h->bank_cap;
-    std::vector<std::vector<int>> lists(cap);
-    for (int i = 0; i < h->S * K; ++i) if (h->bank_sub[i] >= 0) lists[h->bank_sub[i]].push_back(i);
-    std::vector<int> entries;
-    std::vector<owh::BankTile> tiles;
-    h->bank_wbytes = 0.0;
-    for (int c = 0; c < 2; ++c) {
-        long long n_ent = 0; int n_grp = 0;
-        for (int b = 0; b < cap; ++b)
-            if (h->bank[b].live && (h->bank[b].ht == 8) == (c == 1) && !lists[b].empty()) { n_ent += (long long)lists[b].size(); ++n_grp; }
-        int wg = n_grp > 0 && n_ent >= 96LL * n_grp ? 4 : 1;
-        if (const char* e = getenv("OWW_BANK_WG")) { const int v = atoi(e); if (v == 1 || v == 4) wg = v; }   // (A/B aid)
-        h->bank_wg[c] = wg;
-        h->bank_tile0[c] = (int)tiles.size();
-        h->bank_entries_n[c] = (int)n_ent;
-        h->bank_head_tiles[c].clear();
-        std::vector<owh::BankTile> ct;
-        for (int b = 0; b < cap; ++b) {
-            if (!h->bank[b].live || (h->bank[b].ht == 8) != (c == 1) || lists[b].empty()) continue;
-            const int base = (int)entries.size(), n = (int)lists[b].size();
-            entries.insert(entries.end(), lists[b].begin(), lists[b].end());
-            h->bank_head_tiles[c].push_back({h->bank_tile0[c] + (int)ct.size(), (n + 32 * wg - 1) / (32 * wg)});
-            for (int o = 0; o < n; o += 32 * wg) ct.push_back(owh::BankTile{b, base + o, std::min(32 * wg, n - o), 0});
-            h->bank_wbytes += (double)((n + 32 * wg - 1) / (32 * wg)) * (double)h->bank[b].w1_bytes;
-        }
-#if !OWH_BANK_PER_HEAD
-        std::stable_sort(ct.begin(), ct.end(), [](const owh::BankTile& a, const owh::BankTile& b) { return a.n > b.n; });
-#endif
-        tiles.insert(tiles.end(), ct.begin(), ct.end());
-        h->bank_ntiles[c] = (int)ct.size();
-    }
-    HIPCHK(grow(h, h->d_bank_tiles, tiles.size()));
-    if (!tiles.empty()) HIPCHK(copy_sync(h->d_bank_tiles, tiles.data(), tiles.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice));
-    if (!entries.empty()) HIPCHK(copy_sync(h->d_bank_entries, entries.data(), entries.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->bank_rt = owb::route(h->bank_sub.data(), h->S, h->bank_K, h->bank.data(), h->bank_cap, owb::wg_env(), !OWH_BANK_PER_HEAD);
+    const owb::Route& r = h->bank_rt;
+    HIPCHK(grow(h, h->d_bank_tiles, r.tiles.size()));
+    if (!r.tiles.empty()) HIPCHK(copy_sync(h->d_bank_tiles, r.tiles.data(), r.tiles.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice));
+    if (!r.entries.empty()) HIPCHK(copy_sync(h->d_bank_entries, r.entries.data(), r.entries.size() * sizeof(int), hipMemcpyHostToDevice));
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }     // the launch list changed
     return 0;
 }
 
 // ---- per-stream verifier helpers (oww_verifier_*) ------------------------------------------------------------------------------------
-// The list stream_verifier_kernel walks, from the assignment tables: stream-major; per stream its fixed columns (a pool verifier, or
-// the column's handle-wide verifier where the pair keeps the default), then its bank slots (pool verifiers only).  Empty while no
-// pair carries a per-stream assignment: verifier_kernel then serves the handle-wide verifiers as before.  Callers have quiesced the
+// The list stream_verifier_kernel walks, from the assignment tables (owsv::sv_list: owwhip_verifier_host.h).  Callers have quiesced the
 // handle's stream; the captured step graph is invalidated (it bakes the list length).
 int sv_rebuild(oww_ctx* h) {
-    std::vector<SvEntry> list;
-    if (h->vasg_n > 0) {
-        const int NL = h->NL, K = h->bank_K;
-        list.reserve((size_t)h->S * NL);
-        for (int s = 0; s < h->S; ++s) {
-            for (int c = 0; c < NL; ++c) {
-                const size_t at = (size_t)s * NL + c;
-                const int v = h->vasg_fix[at];
-                if (v >= 0) list.push_back(SvEntry{s, (int16_t)c, (int16_t)h->vpool_T[v], v, h->vthr_fix[at]});
-                else if (v == OWW_VERIFIER_DEFAULT && !h->ver_T.empty() && h->ver_T[c] > 0)
-                    list.push_back(SvEntry{s, (int16_t)c, (int16_t)h->ver_T[c], ~c, h->ver_thr[c]});
-            }
-            for (int k = 0; k < K; ++k) {
-                const size_t at = (size_t)s * K + k;
-                const int v = h->vasg_bank[at];
-                if (v >= 0) list.push_back(SvEntry{s, (int16_t)~k, (int16_t)h->vpool_T[v], v, h->vthr_bank[at]});
-            }
-        }
-    }
+    const std::vector<SvEntry> list = owsv::sv_list(h->S, h->NL, h->bank_K, h->vasg_fix, h->vthr_fix, h->vasg_bank, h->vthr_bank, h->vpool_T, h->ver_T,
+                                                    h->ver_thr, h->vasg_n);
     if (!list.empty()) HIPCHK(copy_sync(h->d_svlist, list.data(), list.size() * sizeof(SvEntry), hipMemcpyHostToDevice));
     h->sv_n = (int)list.size();
     const unsigned long long zero = 0;
@@ -1671,17 +1579,12 @@ int alloc_verifiers(oww_ctx* h) {
 
 // ---- stream state records (oww_state_info / oww_state_export / oww_state_import / oww_move_streams; kernels in owwhip_state.h) ---------
 
-// Record layout and fingerprint of this handle, and the device copy of the flat section table.  Built by the first call that needs
-// it: a handle that never exports, imports or moves a stream allocates nothing here.
+// Record layout and fingerprint of this handle (ows::layout, ows::fingerprint: owwhip_state_host.h), and the device copy of the flat
+// section table.  Built by the first call that needs it: a handle that never exports, imports or moves a stream allocates nothing here.
 int state_layout(oww_ctx* h) {
     if (h->st_ready) return 0;
     h->st_flat.clear(); h->st_group.clear();
-    uint32_t off = ows::kHeaderWords;
-    auto flat = [&](void* live, size_t stride, size_t len) {
-        if (!live || len == 0) return;
-        h->st_flat.push_back(ows::FlatSection{static_cast<uint32_t*>(live), (uint32_t)stride, (uint32_t)len, off, (uint32_t)(stride % 4 == 0 && len % 4 == 0)});
-        off += (uint32_t)((len + 3) / 4 * 4);
-    };
+    auto flat = [&](void* live, size_t stride, size_t len) { h->st_flat.push_back(ows::FlatSection{static_cast<uint32_t*>(live), (uint32_t)stride, (uint32_t)len, 0, 0}); };
     const bool il = h->hx && owh::kInterleave;
     const size_t NL = (size_t)h->NL, K = (size_t)h->bank_K;
     for (int a = 0; a < N_STATE; ++a)
@@ -1701,73 +1604,27 @@ int state_layout(oww_ctx* h) {
         flat(h->d_aring, owa::ring_words(h->aud_ring), owa::ring_words(h->aud_ring));
         flat(h->d_acount, owa::kCounterWords, owa::kCounterWords);
     }
-    h->st_flat_quads = off / 4;
-    auto group = [&](float* live, int spg, int ppr, bool inter, uint32_t block_words) -> int {
-        const int R = ppr >= 4 ? 1 : 4 / ppr;
-        if (block_words % (16 * R) || (ppr != 1 && ppr != 2 && ppr != 4 && ppr != 8) || spg * ppr > 16)
-            return fail(OWW_ESTATE, "state records: a group block of %u words, %d streams and %d positions per stream is not a layout the record kernels know", block_words, spg, ppr);
-        h->st_group.push_back(oww_ctx::StateGroupSec{live, spg, ppr, inter, block_words, off});
-        off += block_words / 16 * ppr;
-        return 0;
-    };
     for (int a = 0; a < N_STATE; ++a)
         if (h->rr && kStateSpgRr[a] > 1)
-            if (int rc = group(h->d_state[a], kStateSpgRr[a], il ? 16 / kStateSpgRr[a] : kStateFposRr[a], il, (uint32_t)(h->state_len[a] * kStateSpgRr[a]))) return rc;
-    if (h->vad) if (int rc = group(h->d_vadhc, 16, 1, true, 4096)) return rc;      // (h, c): [4 arrays][16 registers][4 j][16 streams]
-    h->st_record_words = off;
-    // fingerprint: what a record's bits depend on
-    uint64_t fp = 1469598103934665603ull;
-    std::vector<int32_t> v = {(int32_t)ows::kLayoutVersion, h->cfg.use_mfma, il ? 1 : 0};
-    for (int a = 0; a < N_STATE; ++a) v.push_back(h->state_len[a]);
-    v.push_back(h->TR); v.push_back(h->NL); v.push_back(h->bank_K); v.push_back(h->vad ? 1 : 0);
-    for (int l = 0; l < 20; ++l) v.push_back(h->hx ? h->hx_e[l] : 0);
-    v.push_back(h->hx ? h->hx_efeat : 0);
-    fp = fp_mix(fp, v.data(), v.size() * sizeof(int32_t));
-    fp = fp_mix(fp, h->mel_blob.data(), h->mel_blob.size() * sizeof(float));
-    fp = fp_mix(fp, h->emb_blob.data(), h->emb_blob.size() * sizeof(float));
-    for (const auto& hh : h->heads) {
-        const int32_t hdr[6] = {hh.kind, hh.T, hh.hidden, hh.n_out, hh.has_ln, hh.n_blocks};
-        fp = fp_mix(fp, hdr, sizeof hdr);
-        fp = fp_mix(fp, hh.blob.data(), hh.blob.size() * sizeof(float));
+            h->st_group.push_back(ows::GroupSection{h->d_state[a], kStateSpgRr[a], il ? 16 / kStateSpgRr[a] : kStateFposRr[a], il, (uint32_t)(h->state_len[a] * kStateSpgRr[a]), 0});
+    if (h->vad) h->st_group.push_back(ows::GroupSection{h->d_vadhc, 16, 1, true, 4096, 0});      // (h, c): [4 arrays][16 registers][4 j][16 streams]
+    ows::Layout L;
+    if (int rc = ows::layout(h->st_flat, h->st_group, L)) return rc;
+    h->st_flat_quads = L.flat_quads; h->st_record_words = L.record_words;
+    for (int lv = 0; lv < 4; ++lv) {
+        h->st_levels[lv] = false;
+        for (const auto& g : h->st_group) h->st_levels[lv] = h->st_levels[lv] || g.spg == ows::kStateLevels[lv];
     }
-    fp = fp_mix(fp, h->vad_blob.data(), h->vad_blob.size() * sizeof(float));
+    std::vector<ows::HeadPrint> heads;
+    for (const auto& hh : h->heads) heads.push_back(ows::HeadPrint{{hh.kind, hh.T, hh.hidden, hh.n_out, hh.has_ln, hh.n_blocks}, {hh.blob.data(), hh.blob.size() * sizeof(float)}});
+    const uint64_t fp = ows::fingerprint(h->cfg.use_mfma, il, h->state_len, N_STATE, h->TR, h->NL, h->bank_K, h->vad, h->hx ? h->hx_e : nullptr, h->hx_efeat,
+                                         {h->mel_blob.data(), h->mel_blob.size() * sizeof(float)}, {h->emb_blob.data(), h->emb_blob.size() * sizeof(float)}, heads,
+                                         {h->vad_blob.data(), h->vad_blob.size() * sizeof(float)});
     h->st_fp = owa::fingerprint(owi::fingerprint(fp, ing.ready, ing.mixed, ing.tab), h->aud_ring);
     if (!h->d_st_flat) HIPCHK(herr(h->d_st_flat.alloc(h->st_flat.size())));
     HIPCHK(copy_sync(h->d_st_flat, h->st_flat.data(), h->st_flat.size() * sizeof(ows::FlatSection), hipMemcpyHostToDevice));
     h->st_ready = true;
     return 0;
-}
-
-// One list of streams as the record kernels want it: the ids in record order, and per group size (2, 4, 8, 16 streams) the touched
-// group blocks with the record index of every place -- found by one sort of the list, so that a block whose streams are all listed
-// is served by one workgroup per array as full rows.  Offsets are into the int buffer the lists are uploaded in.
-constexpr int kStateLevels[4] = {2, 4, 8, 16};
-struct StateList { int n = 0; size_t ids_at = 0; size_t items_at[4] = {}; int n_groups[4] = {}; };
-
-void state_list_build(const oww_ctx* h, const int32_t* ids, int n, std::vector<int>& buf, StateList& L) {
-    L.n = n; L.ids_at = buf.size();
-    buf.insert(buf.end(), ids, ids + n);
-    std::vector<std::pair<int, int>> order(n);
-    for (int i = 0; i < n; ++i) order[i] = {ids[i], i};
-    std::sort(order.begin(), order.end());
-    for (int lv = 0; lv < 4; ++lv) {
-        const int G = kStateLevels[lv];
-        bool used = false;
-        for (const auto& g : h->st_group) used = used || g.spg == G;
-        L.items_at[lv] = buf.size(); L.n_groups[lv] = 0;
-        if (!used) continue;
-        size_t cur = 0; int cur_g = -1;
-        for (const auto& e : order) {
-            const int g = e.first / G, place = e.first % G;
-            if (g != cur_g || buf[cur + 1 + place] >= 0) {            // a new block (or a stream listed twice: a block entry of its own)
-                cur = buf.size(); cur_g = g;
-                buf.push_back(g);
-                buf.insert(buf.end(), G, -1);
-                ++L.n_groups[lv];
-            }
-            buf[cur + 1 + place] = e.second;
-        }
-    }
 }
 
 int state_lists_upload(oww_ctx* h, const std::vector<int>& buf) {
@@ -1784,7 +1641,7 @@ int state_stage(oww_ctx* h, size_t n) {
 
 // gather (SCATTER = false: live -> rec) or scatter (rec -> live) of one uploaded list, on the handle's stream
 template <bool SCATTER>
-int state_xfer(oww_ctx* h, const StateList& L, uint32_t* rec) {
+int state_xfer(oww_ctx* h, const ows::StateList& L, uint32_t* rec) {
     if (L.n == 0) return 0;
     ows::FlatParams fp{};
     fp.ids = h->d_st_items + L.ids_at; fp.sec = h->d_st_flat; fp.n_sec = (int)h->st_flat.size(); fp.flat_quads = h->st_flat_quads;
@@ -1794,7 +1651,7 @@ int state_xfer(oww_ctx* h, const StateList& L, uint32_t* rec) {
     HIPCHK(hipGetLastError());
     for (const auto& g : h->st_group) {
         int lv = 0;
-        while (kStateLevels[lv] != g.spg) ++lv;
+        while (ows::kStateLevels[lv] != g.spg) ++lv;
         if (L.n_groups[lv] == 0) continue;
         ows::GroupParams gp{};
         const int R = g.ppr >= 4 ? 1 : 4 / g.ppr;
@@ -1837,36 +1694,6 @@ int ensure_mask(oww_ctx* h) {
     if (h->d_on) return 0;
     HIPCHK(herr(h->d_on.alloc(h->Spad)));
     HIPCHK(hipMemsetAsync(h->d_on, 0, h->Spad, h->stream));
-    return 0;
-}
-
-// ids in [0, S); unique where asked
-int state_check_ids(const oww_ctx* h, const char* fn, const char* what, const int32_t* ids, int n, bool unique) {
-    for (int i = 0; i < n; ++i)
-        if (ids[i] < 0 || ids[i] >= h->S) return fail(OWW_EINVAL, "%s: %s stream id %d out of range (0..%d)", fn, what, ids[i], h->S - 1);
-    if (unique && n > 1) {
-        std::vector<int32_t> t(ids, ids + n);
-        std::sort(t.begin(), t.end());
-        const auto dup = std::adjacent_find(t.begin(), t.end());
-        if (dup != t.end()) return fail(OWW_EINVAL, "%s: %s stream id %d is listed twice", fn, what, *dup);
-    }
-    return 0;
-}
-
-// the 32-byte headers of n records (host copy) against this handle
-int state_check_headers(const oww_ctx* h, const uint32_t* hdr /*[n][8]*/, int n) {
-    const uint32_t rb = h->st_record_words * 4;
-    for (int i = 0; i < n; ++i) {
-        const uint32_t* q = hdr + (size_t)i * ows::kHeaderWords;
-        if (q[0] != ows::kMagic) return fail(OWW_EINVAL, "oww_state_import: record %d does not start with a stream state header (magic %08x)", i, q[0]);
-        if (q[1] != ows::kLayoutVersion)
-            return fail(OWW_EINVAL, "oww_state_import: record %d has record layout version %u, this library reads version %u", i, q[1], ows::kLayoutVersion);
-        const uint64_t fp = (uint64_t)q[4] | ((uint64_t)q[5] << 32);
-        if (q[2] != rb || fp != h->st_fp)
-            return fail(OWW_EINVAL, "oww_state_import: record %d comes from another configuration: the record carries fingerprint %016llx and %u bytes, "
-                        "this handle has fingerprint %016llx and %u bytes (kernel family, ring sizes, bank slots, VAD, calibration scales or weights differ)",
-                        i, (unsigned long long)fp, q[2], (unsigned long long)h->st_fp, rb);
-    }
     return 0;
 }
 
@@ -3504,16 +3331,8 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
     if (!h->hx) return fail(OWW_ESTATE, "oww_bank_add: the head bank runs on the fp16-split heads kernels (use_mfma = 3) only");
     if (!h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_bank_add: needs oww_bank_configure before oww_commit, and a committed handle");
     const int32_t* hdr = (const int32_t*)blob;
-    const int kind = hdr[0], T = hdr[1], H = hdr[2], O = hdr[3], has_ln = hdr[4], extra = hdr[5];
-    if (kind == 1) return fail(OWW_EINVAL, "oww_bank_add: gated heads are not accepted in the bank (load them as fixed heads)");
-    if (kind == 2) return fail(OWW_EINVAL, "oww_bank_add: multiclass heads are not accepted in the bank (load them as fixed heads)");
-    if (kind == 3) return fail(OWW_EINVAL, "oww_bank_add: recurrent heads are not accepted in the bank (load them as fixed heads)");
-    if (kind != 0) return fail(OWW_EINVAL, "oww_bank_add: unknown head kind %d", kind);
-    if (O != 1) return fail(OWW_EINVAL, "oww_bank_add: a bank head has one sigmoid output (n_out = %d)", O);
-    if (extra != 0) return fail(OWW_EINVAL, "oww_bank_add: a bank head has exactly one hidden block (extra_blocks = %d)", extra);
-    if (H < 1 || H > 128) return fail(OWW_EINVAL, "oww_bank_add: hidden = %d (a bank head has 1..128 hidden units)", H);
-    if (T < 1 || T > h->TR) return fail(OWW_EINVAL, "oww_bank_add: T = %d exceeds the handle's feature ring (%d rows)", T, h->TR);
-    if (has_ln != 0 && has_ln != 1) return fail(OWW_EINVAL, "oww_bank_add: has_layernorm = %d", has_ln);
+    if (int rc = owb::add_header_check(hdr, h->TR)) return rc;
+    const int T = hdr[1], H = hdr[2], has_ln = hdr[4];
     const size_t K = (size_t)T * 96;
     HeadHost hh{};                                   // (size and finiteness: the fixed heads' parser; the header is inside its ranges)
     if (int rc = parse_head_blob("oww_bank_add", blob, nbytes, h->TR, hh)) return rc;
@@ -3560,7 +3379,7 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
         copy_sync(d_til, til.data(), til.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice) != hipSuccess ||
         copy_sync(d_hd, &dv, sizeof dv, hipMemcpyHostToDevice) != hipSuccess) return fail(OWW_EHIP, "oww_bank_add: self-test upload failed");
     const int flag_before = h->h_range ? *(volatile int*)h->h_range : 0;
-    if (int rc = bank_quiesce(h)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
     owh::BankParams bp{};
     bp.feat = d_win; bp.ext = 1; bp.TR = T; bp.tiles = d_til; bp.entries = d_ent; bp.heads = d_hd; bp.K = 1;
     bp.raw = d_out; bp.range_flag = h->d_range; bp.fscale = std::ldexp(1.0f, h->hx_efeat);
@@ -3597,9 +3416,9 @@ int oww_bank_add(oww_ctx* h, const void* blob, size_t nbytes) {
 int oww_bank_remove(oww_ctx* h, int32_t id) {
     OWW_GUARD_BEGIN
     if (!h || !h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_bank_remove: no bank on this handle");
-    if (id < 0 || id >= h->bank_cap || !h->bank[id].live) return fail(OWW_EINVAL, "oww_bank_remove: %d is not a bank head", id);
+    if (int rc = owb::head_id_check("oww_bank_remove", id, h->bank.data(), h->bank_cap)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = bank_quiesce(h)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<int> changed;
     for (int i = 0; i < h->S * h->bank_K; ++i) if (h->bank_sub[i] == id) { h->bank_sub[i] = -1; changed.push_back(i); }
     if (!changed.empty()) HIPCHK(copy_sync(h->d_bank_sub, h->bank_sub.data(), h->bank_sub.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -3613,7 +3432,7 @@ int oww_bank_remove(oww_ctx* h, int32_t id) {
 int oww_bank_set_postproc(oww_ctx* h, int32_t id, int32_t patience, float threshold) {
     OWW_GUARD_BEGIN
     if (!h || !h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_bank_set_postproc: no bank on this handle");
-    if (id < 0 || id >= h->bank_cap || !h->bank[id].live) return fail(OWW_EINVAL, "oww_bank_set_postproc: %d is not a bank head", id);
+    if (int rc = owb::head_id_check("oww_bank_set_postproc", id, h->bank.data(), h->bank_cap)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(copy_async(h->d_bank_pat + id, &patience, sizeof patience, hipMemcpyHostToDevice, h->stream));
     HIPCHK(copy_async(h->d_bank_thr + id, &threshold, sizeof threshold, hipMemcpyHostToDevice, h->stream));
@@ -3628,16 +3447,9 @@ int oww_subscribe(oww_ctx* h, const int32_t* stream_ids, int32_t n, const int32_
     if (!h || !h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_subscribe: no bank on this handle");
     if (n < 0 || (n > 0 && (!stream_ids || !bank_ids))) return fail(OWW_EINVAL, "oww_subscribe: bad argument");
     const int K = h->bank_K;
-    for (int i = 0; i < n; ++i) {
-        if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return fail(OWW_EINVAL, "oww_subscribe: stream id %d out of range (0..%d)", stream_ids[i], h->S - 1);
-        for (int k = 0; k < K; ++k) {
-            const int b = bank_ids[(size_t)i * K + k];
-            if (b != -1 && (b < 0 || b >= h->bank_cap || !h->bank[b].live))
-                return fail(OWW_EINVAL, "oww_subscribe: %d is not a bank head (stream %d, slot %d)", b, stream_ids[i], k);
-        }
-    }
+    if (int rc = owb::subscribe_check(stream_ids, n, bank_ids, h->S, K, h->bank.data(), h->bank_cap)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = bank_quiesce(h)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<int> changed;
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < K; ++k) {
@@ -3670,8 +3482,8 @@ int oww_bank_routing(oww_ctx* h, int32_t info[6], double* weight_bytes) {
     OWW_GUARD_BEGIN
     if (!h || !h->committed || h->bank_K == 0) return fail(OWW_ESTATE, "oww_bank_routing: no bank on this handle");
     if (info)
-        for (int c = 0; c < 2; ++c) { info[3 * c] = h->bank_ntiles[c]; info[3 * c + 1] = h->bank_wg[c]; info[3 * c + 2] = h->bank_entries_n[c]; }
-    if (weight_bytes) *weight_bytes = h->bank_wbytes;
+        for (int c = 0; c < 2; ++c) { info[3 * c] = h->bank_rt.ntiles[c]; info[3 * c + 1] = h->bank_rt.wg[c]; info[3 * c + 2] = h->bank_rt.entries_n[c]; }
+    if (weight_bytes) *weight_bytes = h->bank_rt.wbytes;
     return OWW_OK;
     OWW_GUARD_END
 }
@@ -3727,36 +3539,17 @@ static int assign_impl(oww_ctx* h, bool bank, int32_t col, const int32_t* stream
     if (!h || !h->committed || h->vpool_cap == 0) return fail(OWW_ESTATE, "%s: no verifier pool on this handle (oww_verifier_configure)", fn);
     if (bank && h->bank_K == 0) return fail(OWW_ESTATE, "%s: no bank on this handle", fn);
     const int ncol = bank ? h->bank_K : h->NL;
-    if (col < 0 || col >= ncol) return fail(OWW_EINVAL, "%s: %s %d outside [0,%d)", fn, bank ? "slot" : "label", col, ncol);
-    if (n < 0 || (n > 0 && (!stream_ids || !verifier_ids || !thresholds))) return fail(OWW_EINVAL, "%s: bad argument", fn);
     int colT = 0;                                      // feature rows of the column's model
     if (!bank) for (const auto& hh : h->heads) if (col >= hh.out_col && col < hh.out_col + hh.n_out) colT = hh.T;
-    for (int i = 0; i < n; ++i) {
-        const int s = stream_ids[i], v = verifier_ids[i];
-        if (s < 0 || s >= h->S) return fail(OWW_EINVAL, "%s: stream id %d out of range (0..%d)", fn, s, h->S - 1);
-        if (v < OWW_VERIFIER_NONE || v >= h->vpool_cap || (v >= 0 && h->vpool_T[v] == 0))
-            return fail(OWW_EINVAL, "%s: %d is not a pool verifier, OWW_VERIFIER_DEFAULT or OWW_VERIFIER_NONE (stream %d)", fn, v, s);
-        if (v < 0) continue;
-        int T = colT;
-        if (bank) {
-            const int b = h->bank_sub[(size_t)s * h->bank_K + col];
-            if (b < 0) return fail(OWW_EINVAL, "%s: slot %d of stream %d is empty", fn, col, s);
-            T = h->bank[b].T;
-        }
-        if (h->vpool_T[v] != T)
-            return fail(OWW_EINVAL, "%s: verifier %d has T = %d feature rows, the model of stream %d's %s %d has T = %d", fn, v, h->vpool_T[v], s,
-                        bank ? "slot" : "label", col, T);
-    }
+    auto model_T = [&](int s) {                        // ... or of the head in the stream's slot (< 0: the slot is empty)
+        if (!bank) return colT;
+        const int b = h->bank_sub[(size_t)s * h->bank_K + col];
+        return b < 0 ? -1 : h->bank[b].T;
+    };
+    if (int rc = owsv::assign_check(fn, bank, col, ncol, stream_ids, n, verifier_ids, thresholds, h->S, h->vpool_T, model_T)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipStreamSynchronize(h->stream));           // ordered behind every queued step (oww_submit)
-    std::vector<int>& tab = bank ? h->vasg_bank : h->vasg_fix;
-    std::vector<float>& thr = bank ? h->vthr_bank : h->vthr_fix;
-    for (int i = 0; i < n; ++i) {
-        const size_t at = (size_t)stream_ids[i] * ncol + col;
-        h->vasg_n += (verifier_ids[i] != OWW_VERIFIER_DEFAULT) - (tab[at] != OWW_VERIFIER_DEFAULT);
-        tab[at] = verifier_ids[i];
-        thr[at] = thresholds[i];
-    }
+    owsv::assign_apply(bank ? h->vasg_bank : h->vasg_fix, bank ? h->vthr_bank : h->vthr_fix, h->vasg_n, col, ncol, stream_ids, n, verifier_ids, thresholds);
     return sv_rebuild(h);
 }
 
@@ -3809,11 +3602,11 @@ int oww_state_export(oww_ctx* h, const int32_t* stream_ids, int32_t n, void* out
     OWW_STATE_ENTER("oww_state_export")
     if (n < 0 || (n > 0 && (!stream_ids || !out))) return fail(OWW_EINVAL, "oww_state_export: bad argument");
     if (n == 0) return OWW_OK;
-    if (int rc = state_check_ids(h, "oww_state_export", "the", stream_ids, n, false)) return rc;
+    if (int rc = ows::state_check_ids(h->S, "oww_state_export", "the", stream_ids, n, false)) return rc;
     if (out_on_device && (reinterpret_cast<uintptr_t>(out) & 15)) return fail(OWW_EINVAL, "oww_state_export: a device buffer must be 16-byte aligned");
     std::vector<int> buf;
-    StateList L;
-    state_list_build(h, stream_ids, n, buf, L);
+    ows::StateList L;
+    ows::state_list_build(h->st_levels, stream_ids, n, buf, L);
     if (!out_on_device) if (int rc = state_stage(h, n)) return rc;
     if (int rc = state_lists_upload(h, buf)) return rc;
     uint32_t* rec = out_on_device ? static_cast<uint32_t*>(out) : h->d_st_stage;
@@ -3829,7 +3622,7 @@ int oww_state_import(oww_ctx* h, const int32_t* stream_ids, int32_t n, const voi
     OWW_STATE_ENTER("oww_state_import")
     if (n < 0 || (n > 0 && (!stream_ids || !in))) return fail(OWW_EINVAL, "oww_state_import: bad argument");
     if (n == 0) return OWW_OK;
-    if (int rc = state_check_ids(h, "oww_state_import", "the", stream_ids, n, true)) return rc;
+    if (int rc = ows::state_check_ids(h->S, "oww_state_import", "the", stream_ids, n, true)) return rc;
     if (in_on_device && (reinterpret_cast<uintptr_t>(in) & 15)) return fail(OWW_EINVAL, "oww_state_import: a device buffer must be 16-byte aligned");
     // every header is checked before anything changes
     const size_t rb = (size_t)h->st_record_words * 4;
@@ -3840,10 +3633,10 @@ int oww_state_import(oww_ctx* h, const int32_t* stream_ids, int32_t n, const voi
     } else {
         for (int i = 0; i < n; ++i) memcpy(&hdr[(size_t)i * ows::kHeaderWords], static_cast<const char*>(in) + (size_t)i * rb, ows::kHeaderWords * 4);
     }
-    if (int rc = state_check_headers(h, hdr.data(), n)) return rc;
+    if (int rc = ows::state_check_headers(h->st_record_words, h->st_fp, hdr.data(), n)) return rc;
     std::vector<int> buf;
-    StateList L;
-    state_list_build(h, stream_ids, n, buf, L);
+    ows::StateList L;
+    ows::state_list_build(h->st_levels, stream_ids, n, buf, L);
     if (!in_on_device) if (int rc = state_stage(h, n)) return rc;
     if (int rc = state_lists_upload(h, buf)) return rc;
     uint32_t* rec = in_on_device ? static_cast<uint32_t*>(const_cast<void*>(in)) : h->d_st_stage;
@@ -3859,12 +3652,12 @@ int oww_move_streams(oww_ctx* h, const int32_t* src, const int32_t* dst, int32_t
     OWW_STATE_ENTER("oww_move_streams")
     if (n < 0 || (n > 0 && (!src || !dst))) return fail(OWW_EINVAL, "oww_move_streams: bad argument");
     if (n == 0) return OWW_OK;
-    if (int rc = state_check_ids(h, "oww_move_streams", "source", src, n, false)) return rc;
-    if (int rc = state_check_ids(h, "oww_move_streams", "destination", dst, n, true)) return rc;
+    if (int rc = ows::state_check_ids(h->S, "oww_move_streams", "source", src, n, false)) return rc;
+    if (int rc = ows::state_check_ids(h->S, "oww_move_streams", "destination", dst, n, true)) return rc;
     std::vector<int> buf;
-    StateList Ls, Ld;
-    state_list_build(h, src, n, buf, Ls);
-    state_list_build(h, dst, n, buf, Ld);
+    ows::StateList Ls, Ld;
+    ows::state_list_build(h->st_levels, src, n, buf, Ls);
+    ows::state_list_build(h->st_levels, dst, n, buf, Ld);
     if (int rc = state_stage(h, n)) return rc;
     if (int rc = state_lists_upload(h, buf)) return rc;
     // every read happens before any write: gather all sources into the staging records, then scatter them
@@ -3896,8 +3689,7 @@ int oww_move_streams(oww_ctx* h, const int32_t* src, const int32_t* dst, int32_t
         ch = travel(h->vasg_bank, h->bank_K, (int)OWW_VERIFIER_DEFAULT) || ch;
         ch = travel(h->vthr_bank, h->bank_K, 0.f) || ch;
         if (ch) {
-            h->vasg_n = 0;
-            for (const auto* tab : {&h->vasg_fix, &h->vasg_bank}) for (int v : *tab) h->vasg_n += v != OWW_VERIFIER_DEFAULT;
+            h->vasg_n = owsv::count_assigned(h->vasg_fix, h->vasg_bank);
             if (int rc = sv_rebuild(h)) return rc;
         }
     }

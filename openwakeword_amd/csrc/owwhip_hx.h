@@ -19,6 +19,7 @@
 #pragma once
 #include <type_traits>
 #include <utility>
+#include "owwhip_bank_host.h"      // owh::BankTile
 #include "owwhip_layout.h"
 #include "owwhip_rr.h"
 
@@ -2485,7 +2486,6 @@ __device__ __forceinline__ void wide_net_eval(const HeadHxNet& net, const f32x4 
 #ifndef OWH_BANK_PER_HEAD
 #define OWH_BANK_PER_HEAD 0    // 1: the routed launch issued as one launch per bank head (tools/bench_head_bank.py, setting d)
 #endif
-struct BankTile { int head, off, n, pad; };
 struct BankHeadDev {
     const float* w1hx;       // [T*3 ksteps][HT ct][2 part][64][8 halves]
     HeadHxNet net;

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "owwhip_layout.h"
+#include "owwhip_verifier_host.h"  // owk::SvEntry, SV_PAIRS
 
 namespace owk {
 
@@ -1558,17 +1559,8 @@ __global__ __launch_bounds__(256) void verifier_kernel(VerifierParams p) {
 // verifier (oww_set_verifier) where the pair keeps the default.  Built on the host whenever an assignment changes.  A wave takes
 // SV_PAIRS entries, ballots raw >= threshold and evaluates each hit with all 64 lanes in the arithmetic of verifier_kernel (lane-
 // strided fmaf chain, xor butterfly 32..1, sigmoid), so the scores are bit for bit the handle-wide path's.
+// (SvEntry and SV_PAIRS: owwhip_verifier_host.h, with the list's construction)
 // ------------------------------------------------------------------------------------------------
-struct SvEntry {
-    int32_t s;               // stream
-    int16_t col;             // >= 0: fixed score column; < 0: bank slot ~col
-    int16_t T;               // feature rows of the verifier (= of the column's model / the slot's head)
-    int32_t v;               // >= 0: pool verifier; < 0: the handle-wide verifier of column ~v
-    float thr;               // re-score when raw >= thr (model.py:322)
-};
-static_assert(sizeof(SvEntry) == 16, "SvEntry is one 16-byte load");
-
-constexpr int SV_PAIRS = 16;     // entries per wave
 struct StreamVerifierParams {
     const SvEntry* list; int n;
     float* raw;              // [S][NL] fixed head outputs of this step (re-scored in place)

@@ -18,19 +18,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "owwhip_state_host.h"     // kMagic, kLayoutVersion, kHeaderWords, FlatSection
+
 namespace ows {
-
-constexpr uint32_t kMagic = 0x5354574fu;          // "OWTS"
-constexpr uint32_t kLayoutVersion = 1u;
-constexpr int kHeaderWords = 8;
-
-struct FlatSection {
-    uint32_t* live;        // first stream's first word
-    uint32_t stride;       // words per stream on the live side
-    uint32_t len;          // words the stream owns
-    uint32_t off;          // word offset in the record (a multiple of 4)
-    uint32_t vec;          // 1 = the live side takes 16-byte accesses (stride and len multiples of 4)
-};
 
 struct FlatParams {
     const int* ids;                // [n] live stream of record i

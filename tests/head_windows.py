@@ -213,7 +213,7 @@ def heads_nbuf(ht, n_nets, n_rows, small_wgs_heads=SMALL_WGS_HEADS):
 
 
 def bank_waves(n_entries, n_groups):
-    """owwhip.hip::bank_route: waves per tile of one width class (the bank kernel's ring always has two slots)."""
+    """owwhip_bank_host.h::route (owb): waves per tile of one width class (the bank kernel's ring always has two slots)."""
     return 4 if n_groups > 0 and n_entries >= 96 * n_groups else 1
 
 

@@ -2,8 +2,8 @@
 poison that drives one of them out of the f16 range, which wave must report it, and the gain tables of the sweeps.
 
 Record mirror.  Only the eleven conv histories are mirrored (csrc/owwhip_layout.h: kStateLenRr words each, kStateSpgRr streams per
-group block).  owwhip.hip::state_layout puts the sections with one stream per block right behind the 8-word header, in order, and
-the grouped sections at the very end of the record, in order, followed only by the VAD's 256-word (h, c) section when the handle
+group block).  owwhip.hip::state_layout lists the sections and owwhip_state_host.h::layout (ows) places them: those with one stream
+per block right behind the 8-word header, in order, and the grouped sections at the very end of the record, in order, followed only by the VAD's 256-word (h, c) section when the handle
 has a VAD.  So every offset comes from one of the two ends and the record size (StreamEngine.state_info()[0]); nothing in the middle
 (PCM tail, feature ring, score rings, counters, bank, ingest, audio) is mirrored, and the mirror holds for any head count, ring size,
 bank or VAD.

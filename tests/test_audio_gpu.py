@@ -388,7 +388,7 @@ def test_state_records_carry_ring_and_counter():
     assert nb == nb0 + ring * 2560 + 16 and fp != fp0 and b.state_info() == (nb, fp)
     hdr = plain.export_state([0]).view(np.uint32)[0, :8]
     assert hdr[1] == 1 and hdr[2] == nb0                     # kLayoutVersion stays 1
-    assert "kLayoutVersion = 1u" in open(os.path.join(ROOT, "openwakeword_amd", "csrc", "owwhip_state.h")).read()
+    assert "kLayoutVersion = 1u" in open(os.path.join(ROOT, "openwakeword_amd", "csrc", "owwhip_state_host.h")).read()     # (the record constants' home)
     plain.close(); plain2.close()
     for e in (a, b):
         e.set_event_thresholds(thr)

@@ -115,7 +115,7 @@ def test_case_table_reaches_every_shape_of_the_k_loop():
 
 
 def test_mirror_of_the_launch_rule():
-    """The mirror restates owwhip_pack.h::pack_head_groups / owwhip.hip::run_heads / bank_route; the cases the issue names."""
+    """The mirror restates owwhip_pack.h::pack_head_groups / owwhip.hip::run_heads / owwhip_bank_host.h::route; the cases the issue names."""
     assert HW.tail_shape(16, 4) == dict(KST=48, NBUF=4, mod=0, main_groups=11, tail_groups=1, partial=0, prologue=3, kst_le_d=False,
                                         empty_main=True is False, main_then_partial=False)
     assert HW.tail_shape(1, 6)["kst_le_d"] and HW.tail_shape(1, 6)["prologue"] == 3 and HW.tail_shape(1, 4)["kst_le_d"]
@@ -129,3 +129,12 @@ def test_mirror_of_the_launch_rule():
                                     **HW.form_heads("generic130", 120), **HW.form_heads("rnn1", 2)})
     assert [(g["T"], g["ht"], g["n_nets"]) for g in groups] == [(19, 4, 3), (19, 8, 2), (7, 4, 1)]
     assert other == ["generic130_t120_0", "rnn1_t2_0"]
+
+
+def test_bank_waves_mirror_against_the_routing_planner():
+    """head_windows.bank_waves restates one line of owb::route (csrc/owwhip_bank_host.h); tests/planners_check.cpp prints what the
+    planner itself chooses at both sides of the 96-entries-per-group edge, for one group and for two."""
+    from test_planners_cpu import self_checks
+    got = self_checks()
+    for n, g in ((95, 1), (96, 1), (191, 2), (192, 2)):
+        assert HW.bank_waves(n, g) == int(got[f"bank_wg_{n}_{g}"]), (n, g)

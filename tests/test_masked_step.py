@@ -34,7 +34,7 @@ def _pcm(rng, S, T):
 def test_masked_step_equals_private_sequences(S, with_vad, frac, family, heads):
     """Random participation masks over 40 steps; every stream's k-th active step must equal, BIT FOR BIT, the k-th step of an
     unmasked engine that is fed the stream's active chunks back to back (S chosen to leave partly filled position tiles).
-    frac <= 0.5: the library launches only the groups that hold a participating stream (build_active_lists): same results."""
+    frac <= 0.5: the library launches only the groups that hold a participating stream (build_active_lists; owwhip_masked_host.h): same results."""
     rng = np.random.default_rng(5)
     T = 40 if family == 3 else 24
     pcm = _pcm(rng, S, T)

@@ -148,3 +148,21 @@ def test_feature_gain_sweep_is_admitted(form):
         if RG.HEAD_SHAPES[form]["layernorm"]:
             assert np.ptp(w64) > 0.05, f"{form}, gain {g:g}: the float64 scores no longer move"
     print(f"\n{form}: |fp32 - float64| <= {worst:.2e}, smallest span of the float64 scores {span:.3f}")
+
+
+@pytest.mark.parametrize("has_vad", [False, True])
+def test_mirror_against_the_layout_planner(has_vad):
+    """range_guard.offsets against ows::layout (csrc/owwhip_state_host.h) on the default register-resident configuration, sections in
+    the order owwhip.hip::state_layout lists them (tests/planners_check.cpp): the eleven conv histories at both ends of the record,
+    and the VAD's (h, c) section behind them when the handle has a VAD."""
+    from test_planners_cpu import record_offsets, self_checks
+    got = record_offsets(has_vad)
+    nb = int(self_checks()["record_bytes%d" % int(has_vad)])
+    assert nb == RG.DEFAULT_RECORD_BYTES + (4 * (4 + RG.VAD_HC_WORDS) if has_vad else 0)
+    want = RG.offsets(nb, has_vad)
+    assert len(want) == 11 + int(has_vad) and (RG.VAD_HC in got) == has_vad
+    for name, at in want.items():
+        assert got[name] == at, name
+    # what lies between the two ends is what the default record's table says
+    for name, words in RG.OTHER_WORDS_DEFAULT.items():
+        assert -(-got[name][1] // 4) * 4 == words, name

@@ -177,7 +177,7 @@ def _layout(S, NL, K):
 
 
 def test_pair_list_mirror():
-    """sv_list reproduces sv_rebuild's order, and the list shapes of the GPU tier put the entries where its cases say."""
+    """sv_list reproduces the order of owwhip_verifier_host.h::sv_list, and the list shapes of the GPU tier put the entries where its cases say."""
     L = VB
     for n in L.ENTRY_COUNTS:
         lay = L.count_layout(n)
@@ -206,3 +206,51 @@ def test_pair_list_mirror():
     assert len(hit_none) == 16 and all(e.thr == 1.5 for e in hit_none)
     off = L.MASK_OFF
     assert 0 < sum(e.s in off for e in wave) < 16          # the masked step switches off some entries of the mixed wave, not all
+
+
+def _case_text(name, fix, fix_thr, bank, bank_thr, pool_T, ver_T, ver_thr):
+    """One case in the format tests/planners_check.cpp reads: thresholds as bit patterns."""
+    fix, bank = np.asarray(fix), np.asarray(bank)
+    pool = [pool_T.get(i, 0) for i in range(max(pool_T, default=-1) + 1)]
+    hexes = lambda a: " ".join("%08x" % int(b) for b in np.asarray(a, np.float32).reshape(-1).view(np.uint32))      # noqa: E731
+    ints = lambda a: " ".join(str(int(v)) for v in np.asarray(a).reshape(-1))                                        # noqa: E731
+    return "\n".join([f"case {name} {fix.shape[0]} {fix.shape[1]} {bank.shape[1]} {len(pool)} {len(ver_T)}", ints(fix), hexes(fix_thr), ints(bank),
+                      hexes(bank_thr), ints(pool), ints(ver_T), hexes(ver_thr)]) + "\n"
+
+
+def test_pair_list_mirror_against_the_library_header(tmp_path):
+    """verifier_budget.sv_list against owsv::sv_list (csrc/owwhip_verifier_host.h), which the library uploads: the tables of the cases
+    above and of the GPU tier's handle HL through tests/planners_check.cpp, entries compared field by field, thresholds by bit
+    pattern.  So the GPU tier's argument about which entries share a wave rests on the list the device really walks."""
+    from test_planners_cpu import run_planners
+    cases = {}
+    fix, fthr, bank, bthr = _layout(4, 2, 1)
+    cases["all_default"] = (fix.copy(), fthr, bank, bthr, {}, [16, 0], [0.5, 0.0])
+    fix[1, 0] = VB.NONE                          # NONE on a column that has a handle-wide verifier; column 1's has T = 0 under DEFAULT
+    cases["one_none"] = (fix.copy(), fthr, bank, bthr, {}, [16, 0], [0.5, 0.0])
+    cases["no_handle_wide"] = (fix.copy(), fthr, bank, bthr, {}, [], [])
+    f0, t0, b0, bt0 = _layout(5, 2, 0)           # K = 0
+    f0[2, 1], t0[2, 1], f0[4, 0] = 1, np.float32(0.3), VB.NONE
+    cases["no_bank"] = (f0, t0, b0, bt0, {0: 16, 1: 5}, [16, 5], [0.25, np.float32(0.1)])
+    for n in VB.ENTRY_COUNTS:
+        lay = VB.count_layout(n, (0.5, 0.25, 0.75))
+        cases[f"count_{n}"] = (lay.fix, lay.fix_thr, lay.bank, lay.bank_thr, VB.HL_POOL, lay.ver_T, lay.ver_thr)
+    lay = VB.mixed_layout(0.4)
+    cases["mixed"] = (lay.fix, lay.fix_thr, lay.bank, lay.bank_thr, VB.HL_POOL, lay.ver_T, lay.ver_thr)
+    path = tmp_path / "cases.txt"
+    path.write_text("".join(_case_text(name, *c) for name, c in cases.items()))
+    got, cur = {}, None
+    for ln in run_planners("verifier", str(path)):
+        tok = ln.split()
+        if tok[0] == "case":
+            cur = got.setdefault(tok[1], [])
+            assert int(tok[2]) >= 0
+        else:
+            cur.append((int(tok[1]), int(tok[2]), int(tok[3]), int(tok[4]), int(tok[5], 16)))
+    assert list(got) == list(cases)
+    for name, c in cases.items():
+        want = [(e.s, e.col, e.T, e.v, int(np.float32(e.thr).view(np.uint32))) for e in VB.sv_list(*c)]
+        assert got[name] == want, name
+    assert got["all_default"] == [] and len(got["one_none"]) == 3 and got["no_handle_wide"] == [] and len(got["mixed"]) == 63
+    assert [len(got[f"count_{n}"]) for n in VB.ENTRY_COUNTS] == list(VB.ENTRY_COUNTS)
+    assert got["no_bank"][4:6] == [(2, 0, 16, ~0, int(np.float32(0.25).view(np.uint32))), (2, 1, 5, 1, int(np.float32(0.3).view(np.uint32)))]

@@ -315,8 +315,8 @@ class Entry(NamedTuple):
 
 
 def sv_list(fix, fix_thr, bank, bank_thr, pool_T, ver_T, ver_thr):
-    """Mirror of owwhip.hip::sv_rebuild.  fix [S, NL] / bank [S, K]: pool ids, DEFAULT or NONE; pool_T: id -> T; ver_T [NL]: T of each
-    column's handle-wide verifier (0 = none).  Stream-major; per stream the fixed columns, then the bank slots; empty while every pair
+    """Mirror of owwhip_verifier_host.h::sv_list (owsv), to which test_verifier_budget_cpu.py holds it field by field.
+    fix [S, NL] / bank [S, K]: pool ids, DEFAULT or NONE; pool_T: id -> T; ver_T [NL]: T of each column's handle-wide verifier (0 = none; empty: the handle has none at all).  Stream-major; per stream the fixed columns, then the bank slots; empty while every pair
     is at the default (verifier_kernel then serves the handle-wide verifiers)."""
     fix, bank = np.asarray(fix), np.asarray(bank)
     out = []
@@ -327,7 +327,7 @@ def sv_list(fix, fix_thr, bank, bank_thr, pool_T, ver_T, ver_thr):
             v = int(fix[s, c])
             if v >= 0:
                 out.append(Entry(s, c, pool_T[v], v, float(fix_thr[s, c])))
-            elif v == DEFAULT and ver_T[c] > 0:
+            elif v == DEFAULT and len(ver_T) and ver_T[c] > 0:
                 out.append(Entry(s, c, ver_T[c], ~c, float(ver_thr[c])))
         for k in range(bank.shape[1]):
             v = int(bank[s, k])
