@@ -155,7 +155,9 @@ int  oww_push_vad(oww_ctx* h, const float* vad_scores, int on_device);
  * float gain; float hann[256]; per conv: w[3][cin][cout], b[cout]; per LSTM layer: w[128][256] (rows x ; h, columns i | f | g | o),
  * b[256] (= b_ih + b_hh); float wd[64]; float bd.  Once loaded, every oww_step / oww_submit (n_chunks must be 1) runs the network
  * on the frame's two sub-frames of every stream and pushes the mean score into the stream's ring; oww_push_vad is then refused.
- * oww_get_vad copies the scores of the last step (host fp32 [S]); oww_reset_vad zeroes recurrent state and score history of the
+ * oww_get_vad copies the scores of the last step (host fp32 [S]) -- it waits for the handle's stream, so with submitted steps in flight
+ * "the last step" is the NEWEST submitted one, not the one the last oww_collect delivered: read it with nothing in flight when it has to
+ * belong to the collected scores; oww_reset_vad zeroes recurrent state and score history of the
  * listed streams (NULL = all) -- oww_reset does not, exactly like Model.reset() leaves Model.vad alone (model.py:226-230). */
 int  oww_load_vad(oww_ctx* h, const void* blob, size_t nbytes);
 int  oww_get_vad(oww_ctx* h, float* out);
@@ -183,10 +185,10 @@ int  oww_sync(oww_ctx* h);
  * stream sits the step out: none of its state moves (sample tail, conv histories, feature and score rings, frame counters,
  * VAD state) and its row of `scores` repeats its previous step's values; its 1280 PCM samples are not read.  A stream
  * stepped k times through any interleaving of masked steps is in the state k plain steps leave it in, bit for bit.
- * Cost: with a HOST mask of which at most half the streams take part, only the stage groups (1 / 2 / 4 / 8 streams of a wave) that
+ * Cost: with a HOST mask of which at most 7/8 of the streams take part (8 n <= 7 S), only the stage groups (1 / 2 / 4 / 8 streams of a wave) that
  * hold a participating stream are launched and the heads run on the participants alone, so the step costs roughly in proportion to
  * the participation (streams sharing a group with a participant are computed and not stored); a device-resident mask, or more than
- * half of the streams, runs the full launches.  Both register-resident kernel families take masked steps (use_mfma = 3 and the exact
+ * 7/8 of the streams, runs the full launches, whose stores skip the streams that sit out; a host mask with nobody on launches nothing.  Both register-resident kernel families take masked steps (use_mfma = 3 and the exact
  * fp32 family 1, so weights the fp16 split refuses at commit can still be served; heads of any form); the proportional cost is the
  * default family's (fused front end, heads of the [T,96] -> 64 -> 64 -> 1 form) -- every other combination runs full launches whose
  * stores skip the streams that sit out.  The LDS-tiled families (use_mfma = 2, 0) return OWW_EINVAL. */
@@ -356,7 +358,10 @@ int  oww_submit_ingest_mixed(oww_ctx* h, const void* in_host, int64_t row_bytes,
  *                       untouched.  oww_reset restarts the bank rings and counters of the streams it resets and keeps the subscriptions
  *                       (model.py:226-230).  Unknown ids or stream ids out of range: OWW_EINVAL, nothing changed.
  *   oww_bank_scores     syncs and copies the post-processed bank scores, host fp32 [S][K] (empty slot: 0.0); oww_bank_scores_dev: the
- *                       same on the device, valid until the next step.  Valid after oww_step / oww_step_masked / oww_collect.
+ *                       same on the device, valid until the next step.  They are the scores of the last step ENQUEUED on the handle: after oww_step /
+ *                       oww_step_masked that call; with oww_submit, the newest submitted step (the call waits for it), which is the one
+ *                       the last oww_collect delivered only while nothing else is in flight -- at two steps in flight collect both,
+ *                       or read the bank scores of a step before submitting the next.
  *   oww_bank_routing    info = {tiles, waves per tile, entries} of the <= 64-unit launch, then of the <= 128-unit launch;
  *                       weight_bytes = first-layer weight bytes one step streams.
  * Semantics per (stream, slot): the raw score is the head's sigmoid output on the stream's last T feature rows (max over the chunks of a
@@ -395,6 +400,8 @@ int  oww_bank_routing(oww_ctx* h, int32_t info[6], double* weight_bytes);
  *                       slot's subscribed head, or a pool verifier for an empty slot: OWW_EINVAL, nothing changed.
  *   oww_verifier_stats  out = {pairs whose assignment is not OWW_VERIFIER_DEFAULT, verifier evaluations of the last step}; the second is
  *                       counted by the per-stream kernel only (0 while no pair is assigned and oww_set_verifier's kernel serves the label).
+ *                       "The last step" is the newest one enqueued (the call waits for the handle's stream): with submitted steps in
+ *                       flight that is the newest submitted step, not the one the last oww_collect delivered.
  * Semantics per (stream, column) and (stream, slot), one verification per call: the raw head output (max over the chunks of a multi-chunk
  * call); where it is >= the threshold it is replaced by sigmoid(w . last-T-feature-rows + bias) on the newest rows, bit for bit what
  * oww_set_verifier's path computes for the same (w, bias, threshold); then first-5 zeroing, patience / threshold / debounce, the 30-deep
@@ -542,7 +549,9 @@ const float* oww_event_features_dev(const oww_ctx* h);
  *                       first, as int16 [n][n_chunks * 1280] into `out` (host, or a 16-byte aligned device pointer with out_on_device);
  *                       chunks the stream has not received since its reset read as zero.  counts (host [n], or NULL): the streams'
  *                       counters.  Like oww_state_export it runs on the handle's stream behind every queued step and returns when it is
- *                       complete.  This is the post-roll path: for "one second after the hit" ask for the stream 13 steps later.
+ *                       complete: with submitted steps in flight the rings and counters are those behind the NEWEST submitted step, not
+ *                       behind the one the last oww_collect delivered (oww_get_event_audio is the per-step view).  This is the
+ *                       post-roll path: for "one second after the hit" ask for the stream 13 steps later.
  *   oww_get_event_audio  snapshots of records [first, first + n) of the call oww_get_events refers to: int16 [n][event_chunks * 1280],
  *                       the newest event_chunks chunks of the record's stream in the detecting step, oldest first, zero where the
  *                       stream had received less since its reset.  Snapshot i belongs to stored record i (the rank, as with
@@ -690,7 +699,9 @@ int  oww_bank_score_stats(oww_ctx* h, const float* feats, int feats_on_device, i
                           int32_t* count, float* max, int32_t* argmax);
 
 /* ---- introspection ------------------------------------------------------------------------------ */
-/* AudioFeatures.get_features (utils.py:454-460): last T rows of stream sid's feature ring, oldest first */
+/* AudioFeatures.get_features (utils.py:454-460): last T rows of stream sid's feature ring, oldest first.  Waits for the handle's
+ * stream: the ring as the newest enqueued step left it -- with submitted steps in flight, the newest submitted one, not the one the
+ * last oww_collect delivered (oww_get_raw and oww_get_mel likewise). */
 int  oww_get_features(oww_ctx* h, int32_t sid, int32_t T, float* out);
 /* newest n_rows (<= 8*n_chunks of the last step) transformed mel rows (x/10+2) of stream sid from the last step */
 int  oww_get_mel(oww_ctx* h, int32_t sid, float* out, int32_t n_rows);

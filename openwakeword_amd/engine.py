@@ -403,7 +403,7 @@ class StreamEngine:
 
     def step_masked_device(self, pcm_dev_ptr: int, stream_on: np.ndarray, scores_dev_ptr: int = 0) -> None:
         """oww_step_masked on device-resident PCM / scores with the participation mask on the host (asynchronous); with at most
-        half of the streams taking part only their groups are launched."""
+        7/8 of the streams taking part only their groups are launched."""
         on = np.ascontiguousarray(stream_on, dtype=np.uint8)
         if on.shape != (self.n_streams,):
             raise ValueError(f"stream_on must be [{self.n_streams}]")
