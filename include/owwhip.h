@@ -698,6 +698,49 @@ int  oww_bank_score_stats(oww_ctx* h, const float* feats, int feats_on_device, i
                           const int32_t* bank_ids, int32_t n_ids, const float* thresholds,
                           int32_t* count, float* max, int32_t* argmax);
 
+/* ---- dense scoring: ordered hit lists with their feature windows ----------------------------------------------------------------------
+ * Between the full matrix and three numbers per head lies what the reference's users mine: Model._get_positive_prediction_frames
+ * (model.py:428-479, behind examples/mine_false_positives.py) returns, per label, the feature windows of every frame that scored at
+ * least a threshold, and train.py feeds such windows back as hard negatives.  These entries return, per column, the positions, the
+ * scores and the feature windows of the hits -- and nothing else: neither the matrix nor, in the clip entry, the embeddings leave the
+ * device.
+ *   Columns: n_cols = oww_n_labels() for oww_score_hits / oww_score_clip_hits, n_ids for oww_bank_score_hits (duplicate ids give
+ *   duplicate columns).  A HIT is a (sequence, window, column) whose entry in the matrix of oww_score_features / oww_score_clips /
+ *   oww_bank_score_features is >= thresholds[column]; thresholds NULL = 0.5 everywhere (train.py:100).  A fixed column with a NaN
+ *   threshold never reports (as oww_events_set_thresholds); a NaN threshold of the bank entry is OWW_EINVAL (as oww_bank_score_stats).
+ *   Window alignment, t_max, gating and multiclass columns are the matrix entries'; the test is applied to the value they would store.
+ *   hits      host, [n_cols][cap]: column c receives its hits in ascending (seq, window) order, the first min(n_total[c], cap) of
+ *             them, whatever the scheduling; n_stored[c] is that number, n_total[c] the number of hits the column had.  n_stored <
+ *             n_total is the overflow signal, not an error; every column has its own cap slots.  score: bit for bit the matrix entry.
+ *             Slots beyond n_stored[c] are not written.  cap is 1 .. 1 << 20.
+ *   windows   NULL, a host pointer or a 16-byte aligned device pointer: stored hit i of column c has the head's own last T_c rows of
+ *             its window, oldest first, as fp32 [T_c][96] at win_offset[c] + i * T_c * 96 floats -- bit for bit the rows of feats, or
+ *             of the embeddings oww_embed_clips would return.  oww_score_hits_layout fills win_offset[n_cols + 1] (the last entry is
+ *             the buffer's size in floats) for the fixed columns (bank_ids NULL) or a list of bank heads.
+ *   n_total[c] = the sum over b of oww_bank_score_stats' count[b][c].  A call's results depend on a window's rows alone, so chunks of a
+ *   long array that overlap by t_max - 1 rows concatenate to the whole array's list (up to cap).
+ * How: the heads launches of the matrix entries run in a hit-mask mode -- one bit per (column, sequence, window), one plain 32-bit
+ * store per wave and column (n_cols x B x ceil(n_win / 32) words: 32 MB for 1,024 heads at 2^18 rows) -- then one workgroup per column
+ * compacts its words in order (popcount, scan, carry: no atomics), and only the stored hits' windows are gathered and re-scored as
+ * external features by the kernels of the fallback path, whose bits are the sliding kernels'.  Cost model: the heads launches of the
+ * matrix entry, + 1 / 32 word per window and column written and read once, + work proportional to n_cols x min(hits, cap).
+ * Errors, live streams and accounting follow the matrix entries: OWW_ESTATE before oww_commit (or without a bank); OWW_EINVAL with
+ * nothing moved for a cap outside 1 .. 1 << 20, null hits / n_stored / n_total, n_rows < t_max, a dead bank id, a misaligned device
+ * pointer; 64-bit sizes and OWW_ENOMEM with the bytes in the message; nothing of the live streams moves, except that the clip entry
+ * parks streams [0, B) as oww_embed_clips does; the range flag behaves as oww_head's.  Heads launches (the re-score included) are
+ * timed under kernel class 6; mask compaction, gathers and slab passes under class 7. */
+typedef struct oww_dense_hit { int32_t seq; int32_t window; float score; int32_t reserved; /* 0 */ } oww_dense_hit;   /* 16 bytes */
+int  oww_score_hits_layout(oww_ctx* h, const int32_t* bank_ids, int32_t n_ids, int32_t cap, int64_t* win_offset);
+int  oww_score_hits(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows,
+                    const float* thresholds, int32_t cap,
+                    oww_dense_hit* hits, int32_t* n_stored, int64_t* n_total, float* windows, int windows_on_device);
+int  oww_score_clip_hits(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t B, int32_t n,
+                         const float* thresholds, int32_t cap,
+                         oww_dense_hit* hits, int32_t* n_stored, int64_t* n_total, float* windows, int windows_on_device);
+int  oww_bank_score_hits(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows,
+                         const int32_t* bank_ids, int32_t n_ids, const float* thresholds, int32_t cap,
+                         oww_dense_hit* hits, int32_t* n_stored, int64_t* n_total, float* windows, int windows_on_device);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 /* AudioFeatures.get_features (utils.py:454-460): last T rows of stream sid's feature ring, oldest first.  Waits for the handle's
  * stream: the ring as the newest enqueued step left it -- with submitted steps in flight, the newest submitted one, not the one the

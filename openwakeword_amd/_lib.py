@@ -85,6 +85,10 @@ SYMBOLS = {
     "oww_bank_score_shape": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "oww_bank_score_features": (C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int]),
     "oww_bank_score_stats": (C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
+    "oww_score_hits_layout": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    "oww_score_hits": (C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.c_int]),
+    "oww_score_clip_hits": (C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.c_int]),
+    "oww_bank_score_hits": (C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.c_int]),
     "oww_get_features": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "oww_get_mel": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
     "oww_debug_read": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32]),

@@ -34,6 +34,7 @@
 #include "owwhip_events.h"
 #include "owwhip_audio.h"
 #include "owwhip_dense.h"
+#include "owwhip_dense_hits_host.h"
 
 using namespace owk;
 using namespace owp;
@@ -1722,11 +1723,27 @@ int launch_dense(oww_ctx* h, const owd::Geometry& geo, dim3 grid, const P& q, vo
 }
 template <int NN, int WG>
 int launch_dense_nn(oww_ctx* h, const owd::Geometry& geo, dim3 grid, const owh::DenseParams& q) {
+    if (q.mask) return launch_dense(h, geo, grid, q, owh::heads_dense_kernel<NN, 4, WG, true>, owh::heads_dense_kernel<NN, 3, WG, true>, owh::heads_dense_kernel<NN, 2, WG, true>);
     return launch_dense(h, geo, grid, q, owh::heads_dense_kernel<NN, 4, WG>, owh::heads_dense_kernel<NN, 3, WG>, owh::heads_dense_kernel<NN, 2, WG>);
 }
 template <int WG>
 int launch_dense_bank(oww_ctx* h, const owd::Geometry& geo, dim3 grid, const owh::DenseBankParams& q) {
+    if (q.mask) return launch_dense(h, geo, grid, q, owh::heads_dense_bank_kernel<4, WG, true>, owh::heads_dense_bank_kernel<3, WG, true>, owh::heads_dense_bank_kernel<2, WG, true>);
     return launch_dense(h, geo, grid, q, owh::heads_dense_bank_kernel<4, WG>, owh::heads_dense_bank_kernel<3, WG>, owh::heads_dense_bank_kernel<2, WG>);
+}
+
+// Where the hit-list entries send a call's scores instead of the matrix: the mask [n_cols][col_stride] (owdh::col_stride; words per
+// sequence wps), against thresholds d_thr on the device and thr on the host.  The fallback forms OR their bits in (dense_hits_slab_kernel).
+struct MaskSink {
+    unsigned* mask; int64_t col_stride, wps;
+    const float* d_thr; const float* thr;
+};
+void launch_hits_slab(oww_ctx* h, const MaskSink& ms, const float* scores, int stride, int off, int col, int64_t nw, int64_t first, int64_t n) {
+    owh::HitSlabParams sp{};
+    sp.scores = scores; sp.stride = stride; sp.off = off; sp.n_win = nw; sp.first = first; sp.n = n; sp.thr = ms.thr[col];
+    sp.mask = ms.mask + (size_t)col * ms.col_stride; sp.wps = ms.wps;
+    Timed t(h, 7);
+    hipLaunchKernelGGL(owh::dense_hits_slab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, sp);
 }
 
 // the A/B aids of both dense paths: OWW_DENSE_PATH=ext = every head down the gather fallback, OWW_DENSE_SLAB_MB = the slab budget
@@ -1769,7 +1786,7 @@ struct SlabWalk {
 // -- wide and generic nets, recurrent heads, the fp32 and LDS-tiled families, a T whose rows do not fit the LDS -- has its windows
 // gathered into a bounded slab and scored by run_heads as external features, slab after slab.  OWW_DENSE_PATH=ext (A/B aid) sends
 // every head down the second path.
-int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_rows, float* d_out) {
+int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_rows, float* d_out, const MaskSink* ms = nullptr) {
     const int t_max = dense_t_max(h);
     const int64_t nw = owd::n_win(n_rows, t_max);
     const DenseEnv env = dense_env();
@@ -1793,6 +1810,7 @@ int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_
                 q.w1hx = g.d_w1hx + (size_t)n0 * 4 * 2 * 256; q.chunk_stride = g.n_nets * 4 * 2 * 256;
                 for (int i = 0; i < nn; ++i) q.net[i] = g.hx_net[n0 + i];
                 q.out = d_out; q.NL = h->NL; q.range_flag = h->d_range; q.fscale = std::ldexp(1.0f, h->hx_efeat);
+                if (ms) { q.mask = ms->mask; q.mask_col_stride = ms->col_stride; q.mask_wps = (int)ms->wps; q.thr = ms->d_thr; }
                 const dim3 grid((unsigned)((int64_t)B * q.tiles));
                 int rc = 0;
                 if (geo.waves == owd::kWavesBig) rc = nn == 1 ? launch_dense_nn<1, owd::kWavesBig>(h, geo, grid, q) : launch_dense_nn<2, owd::kWavesBig>(h, geo, grid, q);
@@ -1810,11 +1828,30 @@ int score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_
         if (!covered[hi]) sw.want(h->heads[hi].T);
     if (!sw.bytes) return 0;
     if (sw.d_slab.alloc((size_t)sw.bytes / sizeof(float))) return fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of window slab)", fn, (long long)sw.bytes);
+    DevBuf<float> d_scr;            // hit lists: a slab's scores [windows][NL] instead of the matrix's rows
+    if (ms && d_scr.alloc((size_t)sw.windows * h->NL))
+        return fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of slab scores)", fn, (long long)sw.windows * h->NL * 4);
     int rc = 0;
     for (size_t hi = 0; hi < h->heads.size() && !rc; ++hi) {
         if (covered[hi]) continue;
+        std::vector<int> launched{(int)hi};         // the heads one run_heads launch scores: hi and, on the MFMA families, its group
+        if (ms && h->mfma)
+            for (const FastGroup& g : h->groups) {
+                bool has = false;
+                for (int ni : g.nets) has |= h->nets[ni].head == (int)hi;
+                if (has) for (int ni : g.nets) if (std::find(launched.begin(), launched.end(), h->nets[ni].head) == launched.end()) launched.push_back(h->nets[ni].head);
+            }
+        if (ms)     // a fallback column's bits are ORed in, so its words start at 0 (a sliding pass overwrites every word of its own)
+            for (int lh : launched)
+                if (hipMemsetAsync(ms->mask + (size_t)h->heads[lh].out_col * ms->col_stride, 0, (size_t)h->heads[lh].n_out * ms->col_stride * 4, h->stream) != hipSuccess)
+                    return drained(h, fail(OWW_EHIP, "%s: clearing the hit mask failed", fn));
         rc = sw.each(h, h->heads[hi].T, [&](int64_t first, int64_t n) {
-            return run_heads(h, step_args(h), (int)n, false, sw.d_slab, (int)hi, d_out + (size_t)first * h->NL, 0);
+            if (!ms) return run_heads(h, step_args(h), (int)n, false, sw.d_slab, (int)hi, d_out + (size_t)first * h->NL, 0);
+            if (int r = run_heads(h, step_args(h), (int)n, false, sw.d_slab, (int)hi, d_scr, 0)) return r;
+            for (int lh : launched)
+                for (int o = 0; o < h->heads[lh].n_out; ++o)
+                    launch_hits_slab(h, *ms, d_scr, h->NL, h->heads[lh].out_col + o, h->heads[lh].out_col + o, nw, first, n);
+            return 0;
         });
         covered[hi] = 1;
         if (h->mfma)
@@ -1835,13 +1872,50 @@ std::vector<int> bank_live_T(const oww_ctx* h) {
     return t;
 }
 
+// n windows of a slab [n][T][96] through ONE bank head by heads_bank_kernel in its ext mode (the launch of oww_bank_add's self-test) ->
+// d_sc[n]: what bank_score_device's fallback and the hit lists' re-score (BankRescorer) both run.  prepare() sizes the score, entry and
+// tile lists for the largest slab; the tile list is rebuilt where a slab's window count differs from the last one's.
+struct BankExtScorer {
+    oww_ctx* h; const char* fn;
+    DevBuf<float> d_sc; DevBuf<int> d_ent; DevBuf<owh::BankTile> d_til;
+    std::vector<int> ent; std::vector<owh::BankTile> til;
+    int64_t til_n = -1;                         // the window count d_til describes
+    static int64_t bytes(int64_t max_windows) { return max_windows * 8 + (max_windows + 127) / 128 * 16; }
+    int prepare(int64_t max_windows) {
+        if (d_sc.alloc((size_t)max_windows) || d_ent.alloc((size_t)max_windows) || d_til.alloc((size_t)((max_windows + 127) / 128)))
+            return fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of slab scores and lists)", fn, (long long)bytes(max_windows));
+        ent.resize((size_t)max_windows);
+        for (int64_t k = 0; k < max_windows; ++k) ent[(size_t)k] = (int)k;
+        if (copy_async(d_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: H2D failed", fn);
+        return 0;
+    }
+    int score(int id, const float* d_slab, int64_t n) {
+        if (n != til_n) {                       // (the launches that read the old list, and the gather just enqueued, end first)
+            if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
+            til.clear();
+            for (int64_t o0 = 0; o0 < n; o0 += 128) til.push_back(owh::BankTile{0, (int)o0, (int)std::min<int64_t>(128, n - o0), 0});
+            if (copy_sync(d_til, til.data(), til.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice) != hipSuccess) return fail(OWW_EHIP, "%s: H2D failed", fn);
+            til_n = n;
+        }
+        const oww_ctx::BankHead& bh = h->bank[id];
+        owh::BankParams bp{};
+        bp.feat = d_slab; bp.ext = 1; bp.TR = bh.T; bp.tiles = d_til; bp.entries = d_ent; bp.heads = h->d_bank_heads + id; bp.K = 1;
+        bp.raw = d_sc; bp.range_flag = h->d_range; bp.fscale = std::ldexp(1.0f, h->hx_efeat);
+        Timed t(h, 6);
+        const dim3 grid((unsigned)til.size());
+        if (bh.ht == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 4>), grid, dim3(256), 0, h->stream, bp);
+        else hipLaunchKernelGGL((owh::heads_bank_kernel<4, 8>), grid, dim3(256), 0, h->stream, bp);
+        return 0;
+    }
+};
+
 // every window of d_feats [B][n_rows][96] through the listed bank heads (checked: live; t_max their largest T) -> d_out [B][n_win][n_ids]
 // or, d_out == nullptr, into the statistics d_count / d_key [B][n_ids] (cleared by the caller) against d_thr / thr [n_ids].  The narrow
 // heads (ht 4) run as ONE launch of heads_dense_bank_kernel on the slice plan; wide heads, whatever the plan refuses and, with
 // OWW_DENSE_PATH=ext, everything take the fallback head by head: windows gathered into the bounded slab, heads_bank_kernel in its ext
 // mode (the launch of oww_bank_add's self-test), dense_bank_slab_kernel from the slab's scores into the column or the statistics.
 int bank_score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_rows, const int32_t* ids, int n_ids, int t_max, float* d_out,
-                      const float* d_thr, const float* thr, int* d_count, unsigned long long* d_key) {
+                      const float* d_thr, const float* thr, int* d_count, unsigned long long* d_key, const MaskSink* ms = nullptr) {
     const int64_t nw = owd::n_win(n_rows, t_max);
     const DenseEnv env = dense_env();
     const float fscale = std::ldexp(1.0f, h->hx_efeat);
@@ -1863,6 +1937,7 @@ int bank_score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, i
         q.n_win = (int)nw; q.seq_tiles = (int)plan.seq_tiles; q.tiles = (int)plan.tiles; q.t_s = t_s;
         q.heads = h->d_bank_heads; q.items = d_items; q.n_items = (int)items.size(); q.hpw = plan.hpw;
         q.out = d_out; q.n_ids = n_ids; q.thr = d_thr; q.count = d_count; q.key = d_key; q.range_flag = h->d_range; q.fscale = fscale;
+        if (ms) { q.mask = ms->mask; q.mask_col_stride = ms->col_stride; q.mask_wps = (int)ms->wps; q.thr = ms->d_thr; }
         const dim3 grid((unsigned)plan.grid);
         if (int rc = plan.geo.waves == owd::kWavesBig ? launch_dense_bank<owd::kWavesBig>(h, plan.geo, grid, q)
                                                       : launch_dense_bank<owd::kWavesSmall>(h, plan.geo, grid, q)) return drained(h, rc);
@@ -1874,35 +1949,19 @@ int bank_score_device(oww_ctx* h, const char* fn, const float* d_feats, int B, i
     for (int i = 0; i < n_ids; ++i)
         if (!covered[i]) sw.want(h->bank[ids[i]].T);
     if (!sw.bytes) return drained(h, 0);        // (the head list is the copy's source)
-    DevBuf<float> d_sc; DevBuf<int> d_ent; DevBuf<owh::BankTile> d_til;
-    const int64_t max_tiles = (sw.windows + 127) / 128;
-    if (sw.d_slab.alloc((size_t)sw.bytes / sizeof(float)) || d_sc.alloc((size_t)sw.windows) || d_ent.alloc((size_t)sw.windows) || d_til.alloc((size_t)max_tiles))
-        return drained(h, fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of window slab)", fn, (long long)(sw.bytes + sw.windows * 8 + max_tiles * 16)));
-    std::vector<int> ent((size_t)sw.windows);
-    for (int64_t k = 0; k < sw.windows; ++k) ent[(size_t)k] = (int)k;
-    if (copy_async(d_ent, ent.data(), ent.size() * sizeof(int), hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
-    std::vector<owh::BankTile> til;
-    int64_t til_n = -1;                         // the window count d_til describes
+    if (sw.d_slab.alloc((size_t)sw.bytes / sizeof(float)))
+        return drained(h, fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of window slab)", fn, (long long)(sw.bytes + BankExtScorer::bytes(sw.windows))));
+    BankExtScorer ext{h, fn};
+    if (int rc = ext.prepare(sw.windows)) return drained(h, rc);
     for (int i = 0; i < n_ids; ++i) {
         if (covered[i]) continue;
-        const oww_ctx::BankHead& bh = h->bank[ids[i]];
-        const int rc = sw.each(h, bh.T, [&](int64_t first, int64_t n) {
-            if (n != til_n) {                   // (the launches that read the old list, and the gather just enqueued, end first)
-                if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
-                til.clear();
-                for (int64_t o0 = 0; o0 < n; o0 += 128) til.push_back(owh::BankTile{0, (int)o0, (int)std::min<int64_t>(128, n - o0), 0});
-                if (copy_sync(d_til, til.data(), til.size() * sizeof(owh::BankTile), hipMemcpyHostToDevice) != hipSuccess) return fail(OWW_EHIP, "%s: H2D failed", fn);
-                til_n = n;
-            }
-            owh::BankParams bp{};
-            bp.feat = sw.d_slab; bp.ext = 1; bp.TR = bh.T; bp.tiles = d_til; bp.entries = d_ent; bp.heads = h->d_bank_heads + ids[i]; bp.K = 1;
-            bp.raw = d_sc; bp.range_flag = h->d_range; bp.fscale = fscale;
-            {
-                Timed t(h, 6);
-                const dim3 grid((unsigned)til.size());
-                if (bh.ht == 4) hipLaunchKernelGGL((owh::heads_bank_kernel<4, 4>), grid, dim3(256), 0, h->stream, bp);
-                else hipLaunchKernelGGL((owh::heads_bank_kernel<4, 8>), grid, dim3(256), 0, h->stream, bp);
-            }
+        // hit lists: a fallback column's bits are ORed in, so its words start at 0 (the sliding launch overwrites every word of its own)
+        if (ms && hipMemsetAsync(ms->mask + (size_t)i * ms->col_stride, 0, (size_t)ms->col_stride * 4, h->stream) != hipSuccess)
+            return drained(h, fail(OWW_EHIP, "%s: clearing the hit mask failed", fn));
+        const int rc = sw.each(h, h->bank[ids[i]].T, [&](int64_t first, int64_t n) {
+            if (int r = ext.score(ids[i], sw.d_slab, n)) return r;
+            const float* d_sc = ext.d_sc;
+            if (ms) { launch_hits_slab(h, *ms, d_sc, 1, 0, i, nw, first, n); return 0; }
             owh::BankSlabParams sp{};
             sp.scores = d_sc; sp.n_win = nw; sp.first = first; sp.n = n; sp.out = d_out; sp.n_ids = n_ids; sp.col = i;
             sp.thr = thr ? thr[i] : 0.5f; sp.count = d_count; sp.key = d_key;
@@ -1945,6 +2004,140 @@ struct DenseIO {
     int settle() { return hipStreamSynchronize(h->stream) != hipSuccess ? fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError())) : range_check(h, fn); }
     int finish() { const int rc = download(); return rc ? rc : settle(); }
 };
+
+// ---- ordered hit lists (oww_score_hits, oww_score_clip_hits, oww_bank_score_hits; owwhip_dense.h, owwhip_dense_hits_host.h) -----------
+// One call: (1) the heads launches of the matrix entries in MASK mode (score_device / bank_score_device with a MaskSink) leave one bit
+// per (column, sequence, window); (2) dense_hits_compact_kernel, one workgroup per column, turns the bits into ordered records and
+// totals; (3) for the stored hits alone, slab by slab: the head's own rows gathered by record (dense_hits_gather_kernel), re-scored as
+// external features by the kernels the fallback launches -- the bits of the matrix entry -- the scores written into the records, the
+// slab copied out as the hits' windows.  A call without hits ends after (2).
+struct HitsBuf {
+    int64_t nw = 0, cap = 0, cap_dev = 0;
+    DevBuf<unsigned> d_mask; DevBuf<int4> d_hits; DevBuf<unsigned long long> d_total; DevBuf<float> d_thr;
+    MaskSink ms{};
+};
+// the call's device buffers, thresholds up.  The mask is not cleared here: a sliding launch overwrites every word of its columns, and
+// score_device / bank_score_device clear the columns that take the fallback, whose bits are ORed in.
+int hits_open(oww_ctx* h, const char* fn, int B, int64_t nw, int n_cols, int64_t cap, const std::vector<float>& thr, HitsBuf& hb) {
+    hb.nw = nw; hb.cap = cap; hb.cap_dev = owdh::cap_eff(cap, B, nw);
+    const int64_t cs = owdh::col_stride(B, nw);
+    const uint64_t mb = owdh::mask_bytes(n_cols, B, nw), rb = owdh::hits_bytes(n_cols, hb.cap_dev);
+    if (hb.d_mask.alloc((size_t)(mb / 4)) || hb.d_hits.alloc((size_t)(rb / 16)) || hb.d_total.alloc((size_t)n_cols) || hb.d_thr.alloc((size_t)n_cols))
+        return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of hit mask, %llu bytes of hit records)", fn, (unsigned long long)mb, (unsigned long long)rb);
+    if (copy_async(hb.d_thr, thr.data(), thr.size() * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
+    hb.ms = MaskSink{hb.d_mask, cs, owdh::words_per_seq(nw), hb.d_thr, thr.data()};
+    return 0;
+}
+// scores n gathered windows of column c; says where the scores are (score of window i at sc[i * stride + off])
+struct HitRescorer {
+    virtual ~HitRescorer() = default;
+    virtual int prepare(int64_t max_windows) = 0;
+    virtual int score(int c, const float* d_slab, int64_t n, const float*& sc, int& stride, int& off) = 0;
+};
+// steps (2) and (3).  T[c]: the window length of column c's head.
+int hits_finish(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_rows, int t_max, int n_cols, const std::vector<int>& T, HitsBuf& hb,
+                HitRescorer& rs, oww_dense_hit* hits, int32_t* n_stored, int64_t* n_total, float* windows, int windows_on_device) {
+    {
+        owh::HitCompactParams cp{};
+        cp.mask = hb.d_mask; cp.col_stride = hb.ms.col_stride; cp.wps = hb.ms.wps; cp.B = B; cp.cap = (int)hb.cap_dev; cp.hits = hb.d_hits; cp.total = hb.d_total;
+        Timed t(h, 7);
+        hipLaunchKernelGGL(owh::dense_hits_compact_kernel, dim3((unsigned)n_cols), dim3(256), 0, h->stream, cp);
+    }
+    std::vector<unsigned long long> total((size_t)n_cols);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = copy_async(total.data(), hb.d_total, total.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(h->stream);
+    if (err != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(err)));
+    const int64_t budget = dense_env().budget;
+    int64_t slab_bytes = 0, slab_windows = 0;
+    for (int c = 0; c < n_cols; ++c) {
+        n_total[c] = (int64_t)total[(size_t)c];
+        n_stored[c] = (int32_t)std::min<int64_t>(n_total[c], hb.cap);
+        if (!n_stored[c]) continue;
+        const owd::Slab sl = owd::slab(n_stored[c], T[(size_t)c], budget);
+        slab_bytes = std::max(slab_bytes, sl.bytes); slab_windows = std::max(slab_windows, sl.windows);
+    }
+    if (!slab_bytes) return range_check(h, fn);         // no hits: no gather, no re-score
+    DevBuf<float> d_slab;
+    if (d_slab.alloc((size_t)slab_bytes / sizeof(float))) return fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of hit-window slab)", fn, (long long)slab_bytes);
+    if (int rc = rs.prepare(slab_windows)) return drained(h, rc);
+    std::vector<int64_t> win_offset((size_t)n_cols + 1);
+    owdh::win_offsets(T.data(), n_cols, hb.cap, win_offset.data());
+    for (int c = 0; c < n_cols; ++c) {
+        if (!n_stored[c]) continue;
+        const int Tc = T[(size_t)c];
+        int4* col_hits = hb.d_hits + (size_t)c * hb.cap_dev;
+        for (const owdh::HitSlab& sl : owdh::slab_plan(n_stored[c], Tc, budget)) {
+            owh::HitGatherParams gp{};
+            gp.feats = d_feats + (size_t)owd::row_offset(t_max, Tc) * 96; gp.seq_stride = (long long)n_rows * 96;
+            gp.hits = col_hits + sl.first; gp.n = sl.n; gp.T = Tc; gp.slab = d_slab;
+            {
+                Timed t(h, 7);
+                const int64_t pieces = sl.n * Tc * 24;
+                hipLaunchKernelGGL(owh::dense_hits_gather_kernel, dim3((unsigned)std::min<int64_t>((pieces + 255) / 256, 256 * 16)), dim3(256), 0, h->stream, gp);
+            }
+            owh::HitScoreParams sp{};
+            if (int rc = rs.score(c, d_slab, sl.n, sp.scores, sp.stride, sp.off)) return drained(h, rc);
+            sp.n = sl.n; sp.hits = col_hits + sl.first;
+            {
+                Timed t(h, 7);
+                hipLaunchKernelGGL(owh::dense_hits_score_kernel, dim3((unsigned)((sl.n + 255) / 256)), dim3(256), 0, h->stream, sp);
+            }
+            if (windows && copy_async(windows + win_offset[(size_t)c] + sl.first * Tc * 96, d_slab.get(), (size_t)sl.n * Tc * 96 * sizeof(float),
+                                      windows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+                return drained(h, fail(OWW_EHIP, "%s: window copy failed", fn));
+        }
+        if (copy_async(hits + (size_t)c * hb.cap, col_hits, (size_t)n_stored[c] * sizeof(oww_dense_hit), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+            return drained(h, fail(OWW_EHIP, "%s: D2H failed", fn));
+    }
+    if (hipGetLastError() != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: a hit-list launch failed", fn));
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(OWW_EHIP, "%s: device error: %s", fn, hipGetErrorString(hipGetLastError()));
+    return range_check(h, fn);
+}
+static_assert(sizeof(oww_dense_hit) == sizeof(int4) && sizeof(oww_dense_hit) == owdh::kHitBytes, "a record is one 16-byte store");
+
+// fixed heads: run_heads on the slab for the column's head (its whole group on the MFMA families; a gated head's two nets with it)
+struct FixedRescorer : HitRescorer {
+    oww_ctx* h; const char* fn; std::vector<int> col_head; DevBuf<float> d_scr;
+    int prepare(int64_t max_windows) override {
+        return d_scr.alloc((size_t)max_windows * h->NL) ? fail(OWW_ENOMEM, "%s: out of device memory (%lld bytes of slab scores)", fn, (long long)max_windows * h->NL * 4) : 0;
+    }
+    int score(int c, const float* d_slab, int64_t n, const float*& sc, int& stride, int& off) override {
+        sc = d_scr; stride = h->NL; off = c;
+        return run_heads(h, step_args(h), (int)n, false, d_slab, col_head[(size_t)c], d_scr, 0);
+    }
+};
+// the fixed columns of a handle: T and head of every column
+void fixed_columns(const oww_ctx* h, std::vector<int>& T, std::vector<int>& head) {
+    T.assign((size_t)h->NL, 0); head.assign((size_t)h->NL, 0);
+    for (size_t hi = 0; hi < h->heads.size(); ++hi)
+        for (int o = 0; o < h->heads[hi].n_out; ++o) { T[(size_t)(h->heads[hi].out_col + o)] = h->heads[hi].T; head[(size_t)(h->heads[hi].out_col + o)] = (int)hi; }
+}
+// bank heads: bank_score_device's fallback launch (BankExtScorer) on the gathered hits
+struct BankRescorer : HitRescorer {
+    BankExtScorer ext; const int32_t* ids;
+    BankRescorer(oww_ctx* h, const char* fn, const int32_t* ids_) : ext{h, fn}, ids(ids_) {}
+    int prepare(int64_t max_windows) override { return ext.prepare(max_windows); }
+    int score(int c, const float* d_slab, int64_t n, const float*& sc, int& stride, int& off) override {
+        sc = ext.d_sc; stride = 1; off = 0;
+        return ext.score(ids[c], d_slab, n);
+    }
+};
+
+// the features half of a fixed-heads hit-list call, shared by oww_score_hits and oww_score_clip_hits: d_feats [B][n_rows][96] on the device
+int score_hits_device(oww_ctx* h, const char* fn, const float* d_feats, int B, int n_rows, const float* thresholds, int32_t cap, oww_dense_hit* hits,
+                      int32_t* n_stored, int64_t* n_total, float* windows, int windows_on_device) {
+    const int t_max = dense_t_max(h);
+    std::vector<float> thr((size_t)h->NL, 0.5f);                // train.py:100's default
+    if (thresholds) thr.assign(thresholds, thresholds + h->NL);
+    HitsBuf hb;
+    if (int rc = hits_open(h, fn, B, owd::n_win(n_rows, t_max), h->NL, cap, thr, hb)) return rc;
+    if (int rc = score_device(h, fn, d_feats, B, n_rows, nullptr, &hb.ms)) return drained(h, rc);
+    FixedRescorer rs; rs.h = h; rs.fn = fn;
+    std::vector<int> T;
+    fixed_columns(h, T, rs.col_head);
+    return hits_finish(h, fn, d_feats, B, n_rows, t_max, h->NL, T, hb, rs, hits, n_stored, n_total, windows, windows_on_device);
+}
 
 }  // namespace
 
@@ -3075,6 +3268,84 @@ int oww_bank_score_stats(oww_ctx* h, const float* feats, int feats_on_device, in
         return fail(OWW_ERANGE, "%s: an activation left the f16 range of the fp16-split kernels -- the statistics of this call are not defined (a score "
                     "that is no number takes part in neither the count nor the maximum in a defined way); clear with oww_range_status(h, 1)", fn);
     return 0;
+    OWW_GUARD_END
+}
+
+// ---- ordered hit lists of dense scoring: oww_score_hits_layout, oww_score_hits, oww_score_clip_hits, oww_bank_score_hits
+int oww_score_hits_layout(oww_ctx* h, const int32_t* bank_ids, int32_t n_ids, int32_t cap, int64_t* win_offset) {
+    OWW_GUARD_BEGIN
+    const char* fn = "oww_score_hits_layout";
+    std::vector<int> T, head;
+    if (bank_ids) {
+        if (int rc = owd::bank_ready_check(fn, h != nullptr, h && h->committed, h ? h->bank_K : 0)) return rc;
+        int t_max = 0;
+        if (int rc = owd::bank_ids_check(fn, bank_ids, n_ids, bank_live_T(h).data(), h->bank_cap, &t_max)) return rc;
+        for (int i = 0; i < n_ids; ++i) T.push_back(h->bank[bank_ids[i]].T);
+    } else {
+        if (int rc = owd::ready_check(fn, h != nullptr, h && h->committed, h ? (int)h->heads.size() : 0)) return rc;
+        fixed_columns(h, T, head);
+    }
+    if (int rc = owdh::layout_check(fn, cap, win_offset)) return rc;
+    owdh::win_offsets(T.data(), (int64_t)T.size(), cap, win_offset);
+    return 0;
+    OWW_GUARD_END
+}
+
+int oww_score_hits(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows, const float* thresholds, int32_t cap,
+                   oww_dense_hit* hits, int32_t* n_stored, int64_t* n_total, float* windows, int windows_on_device) {
+    OWW_GUARD_BEGIN
+    const char* fn = "oww_score_hits";
+    if (int rc = owd::ready_check(fn, h != nullptr, h && h->committed, h ? (int)h->heads.size() : 0)) return rc;
+    if (int rc = owdh::features_check(fn, feats, feats_on_device, B, n_rows, dense_t_max(h), h->NL, cap, hits, n_stored, n_total, windows, windows_on_device)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint64_t fb = owd::feats_bytes(B, n_rows);
+    DenseIO io{h, fn};
+    if (io.alloc_feats(feats, feats_on_device, fb)) return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features)", fn, (unsigned long long)fb);
+    if (io.upload(feats, fb) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
+    return drained(h, score_hits_device(h, fn, io.feats, B, n_rows, thresholds, cap, hits, n_stored, n_total, windows, windows_on_device));
+    OWW_GUARD_END
+}
+
+int oww_score_clip_hits(oww_ctx* h, const int16_t* pcm, int pcm_on_device, int32_t B, int32_t n, const float* thresholds, int32_t cap,
+                        oww_dense_hit* hits, int32_t* n_stored, int64_t* n_total, float* windows, int windows_on_device) {
+    OWW_GUARD_BEGIN
+    const char* fn = "oww_score_clip_hits";
+    if (int rc = owd::ready_check(fn, h != nullptr, h && h->committed, h ? (int)h->heads.size() : 0)) return rc;
+    if (int rc = owdh::clips_check(fn, pcm, B, n, h->Spad, dense_t_max(h), h->NL, cap, hits, n_stored, n_total, windows, windows_on_device)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int n_rows = (int)owd::clip_rows(n);
+    const uint64_t fb = owd::feats_bytes(B, n_rows);
+    DevBuf<float> d_emb;            // the embeddings stay here: only hits and their windows go back
+    if (d_emb.alloc((size_t)(fb / 4))) return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of embeddings)", fn, (unsigned long long)fb);
+    if (int rc = oww_embed_clips(h, pcm, pcm_on_device, B, n, d_emb, 1)) return rc;      // parks and restores streams [0, B); drained on return
+    return drained(h, score_hits_device(h, fn, d_emb, B, n_rows, thresholds, cap, hits, n_stored, n_total, windows, windows_on_device));
+    OWW_GUARD_END
+}
+
+int oww_bank_score_hits(oww_ctx* h, const float* feats, int feats_on_device, int32_t B, int32_t n_rows, const int32_t* bank_ids, int32_t n_ids,
+                        const float* thresholds, int32_t cap, oww_dense_hit* hits, int32_t* n_stored, int64_t* n_total, float* windows,
+                        int windows_on_device) {
+    OWW_GUARD_BEGIN
+    const char* fn = "oww_bank_score_hits";
+    if (int rc = owd::bank_ready_check(fn, h != nullptr, h && h->committed, h ? h->bank_K : 0)) return rc;
+    int t_max = 0;
+    if (int rc = owd::bank_ids_check(fn, bank_ids, n_ids, bank_live_T(h).data(), h->bank_cap, &t_max)) return rc;
+    if (int rc = owdh::features_check(fn, feats, feats_on_device, B, n_rows, t_max, n_ids, cap, hits, n_stored, n_total, windows, windows_on_device)) return rc;
+    if (int rc = owdh::bank_thresholds_check(fn, thresholds, n_ids)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const uint64_t fb = owd::feats_bytes(B, n_rows);
+    std::vector<float> thr((size_t)n_ids, 0.5f);                // train.py:100's default
+    if (thresholds) thr.assign(thresholds, thresholds + n_ids);
+    std::vector<int> T;
+    for (int i = 0; i < n_ids; ++i) T.push_back(h->bank[bank_ids[i]].T);
+    DenseIO io{h, fn};
+    if (io.alloc_feats(feats, feats_on_device, fb)) return fail(OWW_ENOMEM, "%s: out of device memory (%llu bytes of features)", fn, (unsigned long long)fb);
+    if (io.upload(feats, fb) != hipSuccess) return drained(h, fail(OWW_EHIP, "%s: H2D failed", fn));
+    HitsBuf hb;
+    if (int rc = hits_open(h, fn, B, owd::n_win(n_rows, t_max), n_ids, cap, thr, hb)) return drained(h, rc);
+    if (int rc = bank_score_device(h, fn, io.feats, B, n_rows, bank_ids, n_ids, t_max, nullptr, hb.d_thr, thr.data(), nullptr, nullptr, &hb.ms)) return drained(h, rc);
+    BankRescorer rs(h, fn, bank_ids);
+    return drained(h, hits_finish(h, fn, io.feats, B, n_rows, t_max, n_ids, T, hb, rs, hits, n_stored, n_total, windows, windows_on_device));
     OWW_GUARD_END
 }
 

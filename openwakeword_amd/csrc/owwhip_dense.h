@@ -105,9 +105,20 @@ struct DenseParams {
     int NL;
     int* range_flag;
     float fscale;
+    // hit-mask mode (MASK): one word per wave and column instead of the matrix -- see the hit lists further down
+    unsigned* mask;             // [NL][mask_col_stride] words; column c, sequence b, word k at c * mask_col_stride + b * mask_wps + k
+    long long mask_col_stride;
+    int mask_wps;               // words per sequence, ceil(n_win / 32)
+    const float* thr;           // [NL]
 };
 
-template <int NN, int NBUF, int WG>
+// The hit word of one wave: tile t's 16 windows sit in lanes 0 .. 15 (j == 0), so the ballots' low halves side by side are the 32
+// windows w0 + 32 wave .. + 31 in window order -- bit i = window 32 k + i of word k.  hit[t] must be false where the window does not exist.
+__device__ __forceinline__ unsigned dense_hit_word(const bool hit0, const bool hit1) {
+    return (unsigned)(__ballot(hit0) & 0xffffull) | ((unsigned)(__ballot(hit1) & 0xffffull) << 16);
+}
+
+template <int NN, int NBUF, int WG, bool MASK = false>
 __global__ __launch_bounds__(64 * WG, 1) void heads_dense_kernel(DenseParams p) {
     using namespace owr;
     constexpr int NT = 2;                       // position tiles of 16 windows per wave, as heads_hx_kernel
@@ -213,7 +224,25 @@ __global__ __launch_bounds__(64 * WG, 1) void heads_dense_kernel(DenseParams p) 
         }
     }
     // ---- gating + store (one lane group per window: j == 0)
-    if (j == 0) {
+    if constexpr (MASK) {
+        // the same gated value the matrix store would write, tested against the column's threshold: one plain store per wave and column
+        const int word = (w0 + wave * 16 * NT) >> 5;           // (TILE and 16 NT are multiples of 32)
+#pragma unroll
+        for (int n = 0; n < NN; ++n) {
+            if (p.net[n].role != 0) continue;
+            const float thr = p.thr[p.net[n].out_col];
+            bool hit[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int w = w0 + wave * 16 * NT + t * 16 + pos;
+                float sc = score[n][t];
+                if (n + 1 < NN && p.net[n + 1].role == 1 && p.net[n + 1].head == p.net[n].head && sc > 0.5f) sc = score[n + 1][t];
+                hit[t] = j == 0 && w < p.n_win && sc >= thr;
+            }
+            const unsigned bits = dense_hit_word(hit[0], hit[1]);
+            if (lane == 0 && word < p.mask_wps) p.mask[(size_t)p.net[n].out_col * p.mask_col_stride + (size_t)b * p.mask_wps + word] = bits;
+        }
+    } else if (j == 0) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const int w = w0 + wave * 16 * NT + t * 16 + pos;
@@ -281,9 +310,13 @@ struct DenseBankParams {
     unsigned long long* key;    // [B][n_ids]
     int* range_flag;
     float fscale;
+    // hit-mask mode (MASK), as DenseParams: column = it.col, thresholds = thr
+    unsigned* mask;             // [n_ids][mask_col_stride]
+    long long mask_col_stride;
+    int mask_wps;
 };
 
-template <int NBUF, int WG>
+template <int NBUF, int WG, bool MASK = false>
 __global__ __launch_bounds__(64 * WG, 1) void heads_dense_bank_kernel(DenseBankParams p) {
     using namespace owr;
     constexpr int NT = 2;
@@ -396,7 +429,15 @@ __global__ __launch_bounds__(64 * WG, 1) void heads_dense_bank_kernel(DenseBankP
             f32x4 h1[4] = {acc[0][t], acc[1][t], acc[2][t], acc[3][t]};
             score[t] = net64_score<1>(net, h1, bad, j, lane);
         }
-        if (p.out) {
+        if constexpr (MASK) {
+            const float thr = p.thr[it.col];
+            const int word = (w0 + wave * 16 * NT) >> 5;
+            bool hit[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) hit[t] = j == 0 && w0 + wave * 16 * NT + t * 16 + pos < p.n_win && score[t] >= thr;
+            const unsigned bits = dense_hit_word(hit[0], hit[1]);
+            if (lane == 0 && word < p.mask_wps) p.mask[(size_t)it.col * p.mask_col_stride + (size_t)b * p.mask_wps + word] = bits;
+        } else if (p.out) {
             if (j == 0) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
@@ -465,6 +506,126 @@ __global__ void dense_bank_slab_kernel(BankSlabParams p) {
         if (hit) atomicAdd(p.count + at, 1);
         atomicMax(p.key + at, key);
     }
+}
+
+// ---- ordered hit lists (include/owwhip.h: oww_score_hits, oww_score_clip_hits, oww_bank_score_hits) ------------------
+// The sliding kernels' MASK mode leaves one bit per (column, sequence, window) -- mask[col][seq][w / 32], bit w % 32, written with
+// plain stores, one word per wave and column -- and the kernels below turn the mask into the caller's lists
+// (owwhip_dense_hits_host.h states the geometry and, in owdh::compact, what the compaction computes):
+//  * dense_hits_slab_kernel     the fallback forms: the scores of one gathered slab -> the same bits.  A slab starts and ends anywhere
+//                               in a word, so the bits are ORed in (integer atomics commute; the column's words are cleared first).
+//  * dense_hits_compact_kernel  one workgroup per column walks the column's words in (seq, word) order, 1,024 words a turn (one
+//                               16-byte load per thread), with a running offset -- popcount, workgroup scan, carry -- writes set bit
+//                               number r as a record (seq, window, 0, 0) to slot r while r < cap, and the column's total as a 64-bit
+//                               count.  No atomics: slot r is a function of the mask alone.
+//  * dense_hits_gather_kernel   dense_gather_kernel with the window taken from the list: the head's own T rows of n stored hits ->
+//                               slab [n][T][96], one 16-byte piece per thread and turn.
+//  * dense_hits_score_kernel    the re-scored slab's scores (heads_bank_kernel / run_heads on external features, the bits of the
+//                               matrix entry) into the records.
+struct HitSlabParams {
+    const float* scores;        // score of slab window i at scores[i * stride + off]
+    int stride, off;
+    long long n_win, first, n;  // windows [first, first + n) of the flattened [B][n_win] list
+    float thr;
+    unsigned* mask;             // the column's words [B][wps]
+    long long wps;
+};
+__global__ void dense_hits_slab_kernel(HitSlabParams p) {
+    // A wave holds 64 consecutive windows of the flattened list.  The lanes of one mask word are consecutive, and the word's first lane
+    // -- the lane of bit 0, or lane 0 where the wave starts inside a word -- ORs in the whole word's share of the wave's ballot: one
+    // atomic per word instead of one per hit.  A word ends with its 32nd bit or with its sequence, whichever comes first.
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool valid = i < p.n;
+    const long long gw = p.first + (valid ? i : p.n - 1), b = gw / p.n_win, w = gw - b * p.n_win;
+    const unsigned long long hits = __ballot(valid && p.scores[(size_t)(valid ? i : p.n - 1) * p.stride + p.off] >= p.thr);
+    const int bit0 = (int)(w & 31);
+    if (!valid || (bit0 != 0 && lane != 0)) return;
+    const long long left = p.n_win - w;                            // windows of this sequence from w on
+    const int count = (int)(left < 32 - bit0 ? left : 32 - bit0);  // lanes of this word from this lane on (lanes beyond the slab voted 0)
+    const unsigned bits = ((unsigned)(hits >> lane) & (count == 32 ? 0xffffffffu : (1u << count) - 1u)) << bit0;
+    if (bits) atomicOr(p.mask + b * p.wps + (w >> 5), bits);
+}
+
+struct HitCompactParams {
+    const unsigned* mask;       // [n_cols][col_stride]; col_stride a multiple of 4 words (16-byte loads)
+    long long col_stride, wps;
+    int B, cap;                 // cap: slots per column of `hits`
+    int4* hits;                 // [n_cols][cap] records (seq, window, score bits = 0, reserved = 0)
+    unsigned long long* total;  // [n_cols]
+};
+__global__ __launch_bounds__(256) void dense_hits_compact_kernel(HitCompactParams p) {
+    __shared__ unsigned wave_sum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned* m = p.mask + (size_t)blockIdx.x * p.col_stride;
+    int4* out = p.hits + (size_t)blockIdx.x * p.cap;
+    const long long words = (long long)p.B * p.wps;
+    unsigned long long carry = 0;               // set bits of the words in front of this turn
+    for (long long base = 0; base < words; base += 1024) {
+        const long long i4 = base + tid * 4;
+        unsigned v[4] = {0u, 0u, 0u, 0u};
+        if (i4 < words) {                       // (i4 + 3 < col_stride: the column is padded to four words)
+            const uint4 q = *reinterpret_cast<const uint4*>(m + i4);
+            v[0] = q.x; v[1] = i4 + 1 < words ? q.y : 0u; v[2] = i4 + 2 < words ? q.z : 0u; v[3] = i4 + 3 < words ? q.w : 0u;
+        }
+        const unsigned cnt = __popc(v[0]) + __popc(v[1]) + __popc(v[2]) + __popc(v[3]);
+        unsigned inc = cnt;                     // inclusive scan over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned o = __shfl_up(inc, d);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) wave_sum[wave] = inc;
+        __syncthreads();
+        unsigned before = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { before += k < wave ? wave_sum[k] : 0u; all += wave_sum[k]; }
+        unsigned long long r = carry + before + (inc - cnt);
+        if (cnt && r < (unsigned long long)p.cap) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                unsigned bits = v[k];
+                const long long idx = i4 + k, seq = idx / p.wps, w32 = (idx - seq * p.wps) * 32;
+                while (bits && r < (unsigned long long)p.cap) {
+                    const int bit = __ffs(bits) - 1;
+                    out[r] = make_int4((int)seq, (int)(w32 + bit), 0, 0);
+                    bits &= bits - 1; ++r;
+                }
+                r += __popc(bits);              // (only where the cap cut the word short)
+            }
+        }
+        carry += all;
+        __syncthreads();                        // (wave_sum is rewritten in the next turn)
+    }
+    if (tid == 0) p.total[blockIdx.x] = carry;
+}
+
+struct HitGatherParams {
+    const float* feats;         // the head's row offset applied
+    long long seq_stride;       // floats
+    const int4* hits;           // [n] records of the slab's windows
+    long long n;
+    int T;
+    float* slab;                // [n][T][96]
+};
+__global__ void dense_hits_gather_kernel(HitGatherParams p) {
+    const long long per = (long long)p.T * 24, total = p.n * per;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long win = i / per, q = i - win * per;
+        const int4 hit = p.hits[win];
+        reinterpret_cast<owr::f32x4*>(p.slab)[i] = *reinterpret_cast<const owr::f32x4*>(p.feats + hit.x * p.seq_stride + (long long)hit.y * 96 + q * 4);
+    }
+}
+
+struct HitScoreParams {
+    const float* scores;        // score of slab window i at scores[i * stride + off]
+    int stride, off;
+    long long n;
+    int4* hits;                 // [n]
+};
+__global__ void dense_hits_score_kernel(HitScoreParams p) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < p.n) p.hits[i].z = __float_as_int(p.scores[(size_t)i * p.stride + p.off]);
 }
 
 }  // namespace owh

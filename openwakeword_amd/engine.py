@@ -29,6 +29,9 @@ LAYER_NEW_SHAPES = ([(8, 32, 24)] * 3 + [(4, 16, 48)] * 4 + [(4, 8, 72)] * 4 + [
 EVENT_DTYPE = np.dtype([("stream", np.int32), ("column", np.int32), ("bank_id", np.int32), ("score", np.float32),
                         ("frame", np.uint32), ("feature_index", np.int32), ("reserved", np.int32, (2,))])
 EVENT_CAPACITY_MAX = 1 << 20
+# oww_dense_hit of include/owwhip.h (16 bytes): one record of a dense hit list
+DENSE_HIT = np.dtype([("seq", np.int32), ("window", np.int32), ("score", np.float32), ("reserved", np.int32)])
+DENSE_HIT_CAP_MAX = 1 << 20
 AUDIO_RING_MAX = 1024    # oww_audio_configure: ring_chunks 1 .. 1024
 KERNEL_CLASSES = ["mel", "stageA", "stageB", "stageC", "stageD", "stageE", "heads", "postproc", "vad_front", "vad_lstm"]
 
@@ -1077,6 +1080,92 @@ class StreamEngine:
         count, mx, arg = (np.empty((B, a.size), dtype=t) for t in (np.int32, np.float32, np.int32))
         _lib.check(self._lib.oww_bank_score_stats(self._h, _ptr(f), 0, B, n_rows, _ptr(a), a.size, _ptr(thr), _ptr(count), _ptr(mx), _ptr(arg)))
         return {"count": count, "max": mx, "argmax": arg}
+
+    # ---- dense scoring: ordered hit lists (include/owwhip.h: oww_score_hits_layout / oww_score_hits / oww_score_clip_hits /
+    #      oww_bank_score_hits)
+    def score_hits_layout(self, cap: int, ids: Optional[Sequence[int]] = None) -> np.ndarray:
+        """int64 [n_cols + 1]: where each column's windows start in the flat windows buffer (floats), and the buffer's size; column
+        c holds [cap, T_c, 96].  ids None = the fixed score columns, else the listed bank heads."""
+        a = None if ids is None else self._bank_ids(ids)
+        off = np.zeros((self.n_labels if a is None else a.size) + 1, dtype=np.int64)
+        _lib.check(self._lib.oww_score_hits_layout(self._h, _ptr(a), 0 if a is None else a.size, int(cap), _ptr(off)))
+        return off
+
+    def _thresholds(self, thresholds, n_cols: int) -> Optional[np.ndarray]:
+        if thresholds is None:
+            return None
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (n_cols,)) if np.ndim(thresholds) == 0
+                                   else thresholds, dtype=np.float32).ravel()
+        if thr.shape != (n_cols,):
+            raise ValueError(f"need one threshold per column ({n_cols})")
+        return thr
+
+    def _hits_raw(self, call, n_cols: int, cap: int, off: Optional[np.ndarray], hits_buf=None, windows_buf=None) -> dict:
+        """Runs one of the three entries (call(hits_ptr, n_stored_ptr, n_total_ptr, windows_ptr)) on buffers of its own, or the
+        caller's, and returns them as they are: {"hits": DENSE_HIT [n_cols, cap], "n_stored", "n_total", "windows" flat or None,
+        "win_offset"}."""
+        hits = np.zeros((n_cols, cap), dtype=DENSE_HIT) if hits_buf is None else hits_buf
+        n_stored, n_total = np.zeros(n_cols, dtype=np.int32), np.zeros(n_cols, dtype=np.int64)
+        windows = None
+        if off is not None:
+            windows = np.empty(int(off[-1]), dtype=np.float32) if windows_buf is None else windows_buf
+        _lib.check(call(hits.ctypes.data_as(C.c_void_p), _ptr(n_stored), _ptr(n_total), _ptr(windows)))
+        return {"hits": hits, "n_stored": n_stored, "n_total": n_total, "windows": windows, "win_offset": off}
+
+    @staticmethod
+    def _hits_columns(raw: dict) -> List[dict]:
+        """The raw buffers of a hit-list call, per column and trimmed to n_stored."""
+        cols = []
+        off = raw["win_offset"]
+        for c in range(raw["hits"].shape[0]):
+            n = int(raw["n_stored"][c])
+            rec = raw["hits"][c, :n]
+            col = {"seq": rec["seq"].copy(), "window": rec["window"].copy(), "score": rec["score"].copy(), "n_total": int(raw["n_total"][c]),
+                   "windows": None}
+            if raw["windows"] is not None:
+                cap = raw["hits"].shape[1]
+                T = int(off[c + 1] - off[c]) // (cap * EMB_DIM)
+                col["windows"] = raw["windows"][off[c]: off[c] + n * T * EMB_DIM].reshape(n, T, EMB_DIM).copy()
+            cols.append(col)
+        return cols
+
+    def score_hits(self, feats: np.ndarray, thresholds=None, cap: int = 4096, return_windows: bool = True) -> List[dict]:
+        """The hits of score_features' matrix without the matrix (Model._get_positive_prediction_frames, model.py:428-479): per
+        fixed score column a dict {"seq", "window", "score", "n_total", "windows"} -- the (sequence, window) positions with
+        score >= thresholds[c] (None = 0.5; one number = every column; a NaN column never reports) in ascending order, the first
+        `cap` of them; their scores, bit for bit the matrix's; n_total, the count without the cap; and windows [n, T_c, 96], each
+        hit's own T_c feature rows."""
+        f = self._bank_feats(feats)
+        B, n_rows, _ = f.shape
+        thr = self._thresholds(thresholds, self.n_labels)
+        off = self.score_hits_layout(cap) if return_windows else None
+        raw = self._hits_raw(lambda hp, ns, nt, wp: self._lib.oww_score_hits(self._h, _ptr(f), 0, B, n_rows, _ptr(thr), int(cap), hp, ns, nt, wp, 0),
+                             self.n_labels, int(cap), off)
+        return self._hits_columns(raw)
+
+    def score_clip_hits(self, pcm: np.ndarray, thresholds=None, cap: int = 4096, return_windows: bool = True) -> List[dict]:
+        """score_hits over the clips' embed_clips embeddings [B, n] int16 -> per column the hits of score_clips' matrix.  The
+        embeddings never leave the device: only hits and their windows come back.  Borrows streams [0, B) as embed_clips does."""
+        pcm = np.ascontiguousarray(pcm)
+        if pcm.dtype != np.int16 or pcm.ndim != 2:
+            raise ValueError("score_clip_hits expects a 2-D int16 array [B, samples]")
+        B, n = pcm.shape
+        thr = self._thresholds(thresholds, self.n_labels)
+        off = self.score_hits_layout(cap) if return_windows else None
+        raw = self._hits_raw(lambda hp, ns, nt, wp: self._lib.oww_score_clip_hits(self._h, _ptr(pcm), 0, B, n, _ptr(thr), int(cap), hp, ns, nt, wp, 0),
+                             self.n_labels, int(cap), off)
+        return self._hits_columns(raw)
+
+    def bank_score_hits(self, feats: np.ndarray, ids: Sequence[int], thresholds=None, cap: int = 4096, return_windows: bool = True) -> List[dict]:
+        """score_hits over the listed bank heads: per listed id (duplicates allowed) the hits of bank_score_features' matrix, which
+        is never written.  n_total of column i is the sum over sequences of bank_score_stats' count[:, i]."""
+        f, a = self._bank_feats(feats), self._bank_ids(ids)
+        B, n_rows, _ = f.shape
+        thr = self._thresholds(thresholds, a.size)
+        off = self.score_hits_layout(cap, a) if return_windows else None
+        raw = self._hits_raw(lambda hp, ns, nt, wp: self._lib.oww_bank_score_hits(self._h, _ptr(f), 0, B, n_rows, _ptr(a), a.size, _ptr(thr), int(cap),
+                                                                                  hp, ns, nt, wp, 0), a.size, int(cap), off)
+        return self._hits_columns(raw)
 
     # ---- introspection
     def get_features(self, sid: int, T: int = 16) -> np.ndarray:

@@ -731,6 +731,52 @@ class BatchedModel:
         out = {lab: raw[:, :, c] for lab, c in zip(self.labels, self._keep)}
         return (out, np.concatenate([p[1] for p in parts], axis=0)) if return_features else out
 
+    # ---- dense scoring: ordered hit lists (include/owwhip.h: oww_score_hits, oww_score_clip_hits, oww_bank_score_hits) ----
+    def _label_thresholds(self, threshold):
+        """A number, or {label: value} (labels not named: 0.5) -> one threshold per score column of the engine."""
+        if not isinstance(threshold, dict):
+            return threshold
+        thr = np.full(self.engine.n_labels, 0.5, dtype=np.float32)
+        for lab, v in threshold.items():
+            thr[self._keep[self.labels.index(lab)]] = np.float32(v)
+        return thr
+
+    def score_hits(self, feats: np.ndarray, threshold=0.5, cap: int = 4096, return_windows: bool = True) -> Dict[str, dict]:
+        """The frames of feature sequences [B, n_rows, 96] that score at least `threshold` (a number, or {label: value}), found on the
+        device (Model._get_positive_prediction_frames, model.py:428-479) -> {label: {"seq", "window", "score", "n_total",
+        "windows"}}: positions in ascending (seq, window) order, the first `cap` of them per label; their raw scores; the count without
+        the cap; and each hit's own [T, 96] feature window.  The score matrix is never written."""
+        cols = self.engine.score_hits(feats, self._label_thresholds(threshold), cap, return_windows)
+        return {lab: cols[c] for lab, c in zip(self.labels, self._keep)}
+
+    def score_clip_hits(self, clips: np.ndarray, threshold=0.5, cap: int = 4096, return_windows: bool = True) -> Dict[str, dict]:
+        """score_hits over equally long int16 clips [B, n], as score_clips scores them: the embeddings stay on the device, only the
+        hits and their windows come back.  Batches larger than the stream count run in several calls; `seq` counts over all clips and
+        `cap` bounds the merged list of a label."""
+        clips = np.ascontiguousarray(np.atleast_2d(clips))
+        per = self.engine.n_streams_padded
+        thr = self._label_thresholds(threshold)
+        out: Dict[str, dict] = {}
+        for lo in range(0, clips.shape[0], per):
+            cols = self.engine.score_clip_hits(clips[lo:lo + per], thr, cap, return_windows)
+            for lab, c in zip(self.labels, self._keep):
+                col = cols[c]
+                col["seq"] = col["seq"] + np.int32(lo)
+                if lab not in out:
+                    out[lab] = col
+                    continue
+                acc = out[lab]
+                room = max(int(cap) - acc["seq"].size, 0)
+                for k in ("seq", "window", "score") + (("windows",) if return_windows else ()):
+                    acc[k] = np.concatenate([acc[k], col[k][:room]], axis=0)
+                acc["n_total"] += col["n_total"]
+        return out
+
+    def bank_score_hits(self, feats: np.ndarray, ids: Sequence[int], thresholds=None, cap: int = 4096, return_windows: bool = True) -> List[dict]:
+        """score_hits over the listed bank heads: one dict per listed id, in the list's order (None thresholds = 0.5, train.py:100).
+        Says where a head false-accepts and on what, where bank_score_stats says how often."""
+        return self.engine.bank_score_hits(feats, ids, thresholds, cap, return_windows)
+
     # ---- head bank: per-stream subscriptions to wake-word heads (include/owwhip.h: oww_bank_*) ----
     def bank_add(self, model: Union[str, dict], weights: Union[str, dict, None] = None) -> int:
         """Add a head to the bank while the streams run -> bank id.  `model` is resolved like an entry of `wakeword_models`: a

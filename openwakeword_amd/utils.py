@@ -250,6 +250,59 @@ def mine_windows(clips, wakeword_models, threshold: float = 0.5, **kw) -> dict:
             bm.close()
 
 
+def mine_clip_hits(clips, wakeword_models, threshold: float = 0.5, cap: int = 4096, **kw) -> dict:
+    """`mine_windows` with the search on the device: the feature windows of equally long clips `int16 [B, n]` that score at least
+    `threshold` -> {label: [N, T, 96]}, at most `cap` per label (the first in (clip, window) order).  Neither the score matrix nor the
+    embeddings come to the host: `BatchedModel.score_clip_hits` returns the hits and their windows alone.  Where nothing overflows the
+    result is bit for bit `mine_windows`'."""
+    clips = np.ascontiguousarray(np.atleast_2d(clips))
+    bm, own = _dense_model(wakeword_models, min(clips.shape[0], 64), **kw)
+    try:
+        return {lab: col["windows"] for lab, col in bm.score_clip_hits(clips, threshold, cap).items()}
+    finally:
+        if own:
+            bm.close()
+
+
+def mine_feature_file(path_or_array, model, threshold=0.5, ids=None, cap: int = 4096, chunk_rows: int = 1 << 18) -> dict:
+    """The chunked scan of `score_feature_file` / `validate_bank` that returns hits instead of scores or counts: every T-row window
+    (stride 1) of precomputed features `[N, 96]` -- a `.npy` path, read through a memmap, or an array -- through the fixed models of
+    `model` (a `BatchedModel`; `threshold` a number or {label: value}) or, with `ids`, through its bank heads (`threshold` a number or
+    one per id) -> {label or id: {"window", "score", "windows", "n_total"}}: the windows (counted over the whole array) that score at
+    least the threshold, in ascending order and at most `cap` of them, their scores, their own [T, 96] feature rows, and the number
+    of hits without the cap.  Chunks overlap by t_max - 1 rows and a window's score depends on its rows alone, so the result does not
+    depend on `chunk_rows`."""
+    feats = np.load(path_or_array, mmap_mode="r") if isinstance(path_or_array, (str, os.PathLike)) else np.asarray(path_or_array)
+    if feats.ndim != 2 or feats.shape[1] != EMB_DIM:
+        raise ValueError(f"features must be [N, 96], got {feats.shape}")
+    if ids is None:
+        _, t_max = model.engine.score_shape(feats.shape[0])
+        keys = list(model.labels)
+    else:
+        ids = [int(i) for i in ids]
+        _, t_max = model.bank_score_shape(ids, feats.shape[0])
+        keys = ids
+        thr = None if threshold is None else np.broadcast_to(np.asarray(threshold, dtype=np.float32), (len(ids),))
+    acc = [None] * len(keys)
+    for w0, _, r0, r1 in dense_chunks(feats.shape[0], t_max, chunk_rows):
+        chunk = np.ascontiguousarray(feats[r0:r1], dtype=np.float32)[None]
+        if ids is None:
+            got = model.score_hits(chunk, threshold, cap)
+            cols = [got[lab] for lab in keys]
+        else:
+            cols = model.bank_score_hits(chunk, ids, thr, cap)
+        for k, col in enumerate(cols):
+            col = {"window": col["window"].astype(np.int64) + w0, "score": col["score"], "windows": col["windows"], "n_total": col["n_total"]}
+            if acc[k] is None:
+                acc[k] = col
+                continue
+            room = max(int(cap) - acc[k]["window"].size, 0)
+            for f in ("window", "score", "windows"):
+                acc[k][f] = np.concatenate([acc[k][f], col[f][:room]], axis=0)
+            acc[k]["n_total"] += col["n_total"]
+    return dict(zip(keys, acc)) if ids is None else {i: acc[k] for k, i in enumerate(ids)}
+
+
 def validate_bank(path_or_array, model, ids, thresholds=None, chunk_rows: int = 1 << 18, hours: float = None) -> dict:
     """The scan of train.py:225-258 (`_select_best_model`) for bank heads: every T-row window (stride 1) of precomputed negative
     features `[N, 96]` -- a `.npy` path, read through a memmap, or an array -- through the bank heads `ids` of `model` (a `BatchedModel`
