@@ -25,6 +25,7 @@
 #include "owwhip_bank_host.h"
 #include "owwhip_verifier_host.h"
 #include "owwhip_state_host.h"
+#include "owwhip_postproc.h"
 #include "owwhip_kernels.h"
 #include "owwhip_rr.h"
 #include "owwhip_hx.h"
@@ -571,6 +572,12 @@ int run_cnn(oww_ctx* h, const StepArgs& a, int n_active, int mel_stride, int mel
     return h->mfma ? run_cnn_t<true>(h, a, n_active, mel_stride, mel_off) : run_cnn_t<false>(h, a, n_active, mel_stride, mel_off);
 }
 
+// what every post-processing launch site takes from the handle (owwhip_postproc.h): the rules of the fixed labels or of the bank's heads,
+// and the streams' VAD gate
+owq::Rules post_rules(const oww_ctx* h) { return {h->d_patience, h->d_threshold, h->debounce_frames}; }
+owq::Rules bank_post_rules(const oww_ctx* h) { return {h->d_bank_pat, h->d_bank_thr, h->debounce_frames}; }
+owq::Gate post_gate(const oww_ctx* h) { return {h->d_vadring, h->d_nvad, h->vad_threshold}; }
+
 int heads_lds_bytes(int NH) { return (HD_SB * 100 + 2 * HD_SB * (NH + 4) + HD_SB * HD_MAXNETS) * 4; }
 
 // heads over streams [0,n_active): ring mode (ext == nullptr) or external features
@@ -610,8 +617,7 @@ int run_heads(oww_ctx* h, const StepArgs& a, int n_active, bool accumulate_max, 
                 if (a.post_in_heads) {
                     owh::HeadHxPost& pp = q.post;
                     pp.enabled = 1; pp.scores = h->d_scores; pp.ring = h->d_ring; pp.npred = h->d_npred; pp.nfeat = h->d_nfeat;
-                    pp.patience = h->d_patience; pp.threshold = h->d_threshold; pp.debounce_frames = h->debounce_frames;
-                    pp.vad_ring = h->d_vadring; pp.n_vad = h->d_nvad; pp.vad_threshold = h->vad_threshold;
+                    pp.rules = post_rules(h); pp.gate = post_gate(h);
                 }
                 for (int i = 0; i < g.n_nets; ++i) q.net[i] = g.hx_net[i];
                 q.fscale = std::ldexp(1.0f, h->hx_efeat);
@@ -811,9 +817,8 @@ int launch_bank_post(oww_ctx* h, const StepArgs& a) {
     if (!bank_active(h)) return 0;
     owh::BankPostParams pp{};
     pp.raw = h->d_bank_raw; pp.scores = h->d_bank_scores; pp.ring = h->d_bank_ring; pp.npred = h->d_bank_npred; pp.sub = h->d_bank_sub;
-    pp.patience = h->d_bank_pat; pp.threshold = h->d_bank_thr; pp.debounce_frames = h->debounce_frames;
     pp.S = h->S; pp.K = h->bank_K;
-    pp.vad_ring = h->d_vadring; pp.n_vad = h->d_nvad; pp.vad_threshold = h->vad_threshold; pp.stream_on = a.on;
+    pp.rules = bank_post_rules(h); pp.gate = post_gate(h); pp.stream_on = a.on;
     {
         Timed t(h, 7);
         hipLaunchKernelGGL(owh::bank_post_kernel, dim3((h->S * h->bank_K + 255) / 256), dim3(256), 0, h->stream, pp);
@@ -961,9 +966,8 @@ int launch_step_long(oww_ctx* h, const StepArgs& a, const int16_t* d_pcm, int K)
 int launch_postproc(oww_ctx* h, const StepArgs& a) {
     PostParams pp{};
     pp.raw = h->d_raw; pp.scores = h->d_scores; pp.ring = h->d_ring; pp.npred = h->d_npred;
-    pp.patience = h->d_patience; pp.threshold = h->d_threshold; pp.debounce_frames = h->debounce_frames;
     pp.NL = h->NL; pp.S = h->Spad;
-    pp.vad_ring = h->d_vadring; pp.n_vad = h->d_nvad; pp.vad_threshold = h->vad_threshold; pp.stream_on = a.on;
+    pp.rules = post_rules(h); pp.gate = post_gate(h); pp.stream_on = a.on;
     {
         Timed t(h, 7);
         hipLaunchKernelGGL(postproc_kernel, dim3((h->Spad + 127) / 128), dim3(128), 0, h->stream, pp);
@@ -1468,7 +1472,7 @@ int alloc_state(oww_ctx* h) {
     if (int rc = dalloc(h->stream, h->d_featinit, (size_t)h->TR * 96)) return rc;
     if (int rc = dalloc(h->stream, h->d_nfeat, SP)) return rc;
     if (int rc = dalloc(h->stream, h->d_npred, SP)) return rc;
-    if (int rc = dalloc(h->stream, h->d_vadring, SP * 8)) return rc;
+    if (int rc = dalloc(h->stream, h->d_vadring, SP * owq::kVadRing)) return rc;
     if (int rc = dalloc(h->stream, h->d_nvad, SP)) return rc;
     if (int rc = dalloc(h->stream, h->d_vadin, SP)) return rc;
     if (h->vad) {
@@ -1595,7 +1599,7 @@ int state_layout(oww_ctx* h) {
     flat(h->d_ring, NL * OWW_SCORE_RING, NL * OWW_SCORE_RING);
     flat(h->d_raw, NL, NL); flat(h->d_scores, NL, NL);
     flat(h->d_nfeat, 1, 1); flat(h->d_npred, 1, 1);
-    flat(h->d_vadring, 8, 8); flat(h->d_nvad, 1, 1);
+    flat(h->d_vadring, owq::kVadRing, owq::kVadRing); flat(h->d_nvad, 1, 1);
     if (h->vad) flat(h->d_vadlast, 1, 1);
     if (K) { flat(h->d_bank_raw, K, K); flat(h->d_bank_scores, K, K); flat(h->d_bank_npred, K, K); flat(h->d_bank_ring, K * OWW_SCORE_RING, K * OWW_SCORE_RING); }
     const oww_ctx::Ingest& ing = h->ing;

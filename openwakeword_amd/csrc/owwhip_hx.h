@@ -21,6 +21,7 @@
 #include <utility>
 #include "owwhip_bank_host.h"      // owh::BankTile
 #include "owwhip_layout.h"
+#include "owwhip_postproc.h"       // owq: the post-processing rule and the VAD gate
 #include "owwhip_rr.h"
 
 namespace owh {
@@ -1715,22 +1716,18 @@ struct HeadHxNet {
     float u3;                                // 2^-e_w3
     int n_out, final_act;                    // final_act 0: sigmoid per output; 1: ReLU + softmax over the n_out outputs (train.py:79,152-165)
 };
-// Optional tail of the heads kernel: Model.predict's post-processing (model.py:330-381 -- first-5 zeroing, patience / debounce
-// over the 30-deep score ring, ring append, VAD gate) and the step's frame-counter advance for the same streams, instead of two
+// Optional tail of the heads kernel: Model.predict's post-processing (model.py:330-381 -- owq::score_rule per label, then the stream's
+// owq::gate_closed: owwhip_postproc.h) and the step's frame-counter advance for the same streams, instead of two
 // more launches (owk::postproc_kernel, owk::advance_kernel).  Valid when every label of the handle is produced by THIS launch
 // (one group of sigmoid heads) and the step carries one chunk; otherwise the separate kernels run.
 struct HeadHxPost {
     int enabled;
     float* scores;           // [S][NL]
-    float* ring;             // [S][NL][30]
+    float* ring;             // [S][NL][owq::kScoreRing]
     uint32_t* npred;         // [S]
     uint32_t* nfeat;         // [S] (advanced here)
-    const int* patience;     // [NL]
-    const float* threshold;  // [NL] (NaN = none)
-    int debounce_frames;
-    const float* vad_ring;   // [S][8]
-    const uint32_t* n_vad;   // [S]
-    float vad_threshold;     // <= 0: gate off
+    owq::Rules rules;        // per label
+    owq::Gate gate;
 };
 struct HeadHxParams {
     const float* feat;      // ring [S][TR][96] or external [B][T][96] when ext != 0
@@ -2189,7 +2186,6 @@ __global__ __launch_bounds__(64 * WG, (NBUF > 2 ? 1 : 2)) void heads_hx_kernel(H
             const int st = p.ids ? p.ids[idx] : idx + p.s_base;
             if (p.stream_on && !p.stream_on[st]) continue;          // sits this step out: scores, rings and counters stay as they are
             const uint32_t cnt = p.post.enabled ? p.post.npred[st] : 0u;
-            const int have = cnt < 30u ? (int)cnt : 30;
             float fin[NN];
 #pragma unroll
             for (int n = 0; n < NN; ++n) {
@@ -2201,41 +2197,13 @@ __global__ __launch_bounds__(64 * WG, (NBUF > 2 ? 1 : 2)) void heads_hx_kernel(H
                 float* o = p.raw + (size_t)st * p.NL + l;
                 sc = p.accumulate_max ? fmaxf(*o, sc) : sc;
                 *o = sc;
-                if (p.post.enabled) {                                       // the rules of owk::postproc_kernel, same order
-                    float* ring = p.post.ring + ((size_t)st * p.NL + l) * 30;
-                    if (cnt < 5u) sc = 0.0f;                                // model.py:331-333
-                    if (sc != 0.0f) {
-                        const int pat = p.post.patience[l];
-                        const float thr = p.post.threshold[l];
-                        if (pat > 0) {                                      // model.py:349-352
-                            const int look = pat < have ? pat : have;
-                            int n_ok = 0;
-                            for (int i = 1; i <= look; ++i) n_ok += ring[(cnt - i) % 30u] >= thr ? 1 : 0;
-                            if (n_ok < pat) sc = 0.0f;
-                        } else if (p.post.debounce_frames > 0 && thr == thr) {   // model.py:353-359
-                            const int look = p.post.debounce_frames < have ? p.post.debounce_frames : have;
-                            int n_hit = 0;
-                            for (int i = 1; i <= look; ++i) n_hit += ring[(cnt - i) % 30u] >= thr ? 1 : 0;
-                            if (sc >= thr && n_hit > 0) sc = 0.0f;
-                        }
-                    }
-                    ring[cnt % 30u] = sc;                                   // model.py:362-363
-                    fin[n] = sc;
-                }
+                if (p.post.enabled)
+                    fin[n] = owq::score_rule(sc, cnt, p.post.ring + ((size_t)st * p.NL + l) * owq::kScoreRing, p.post.rules, l);
             }
             if (p.post.enabled) {
                 p.post.npred[st] = cnt + 1u;
                 p.post.nfeat[st] += 1u;                                     // (this stream's ring slot was read at kernel start)
-                bool gate = false;
-                if (p.post.vad_threshold > 0.0f) {                          // model.py:375-381
-                    const uint32_t L = p.post.n_vad[st];
-                    float vmax = 0.0f;
-                    if (L >= 5u) {
-                        vmax = -INFINITY;
-                        for (uint32_t i = (L >= 7u ? L - 7u : 0u); i + 5u <= L; ++i) vmax = fmaxf(vmax, p.post.vad_ring[(size_t)st * 8 + (i & 7u)]);
-                    }
-                    gate = vmax < p.post.vad_threshold;
-                }
+                const bool gate = owq::gate_closed(p.post.gate, st);
 #pragma unroll
                 for (int n = 0; n < NN; ++n)
                     if (p.net[n].role == 0) p.post.scores[(size_t)st * p.NL + p.net[n].out_col] = gate ? 0.0f : fin[n];
@@ -2572,15 +2540,15 @@ __global__ __launch_bounds__(64 * WG, 2) void heads_bank_kernel(BankParams p) {
     raise_range_flag(bad, p.range_flag);
 }
 
-// Model.predict's post-processing (model.py:330-381) per (stream, slot) of the bank, the rules of owk::postproc_kernel in the same
-// order: first-5 zeroing on the slot's own prediction count, patience / debounce over the slot's 30-deep ring (per bank head; debounce
-// frames shared with the handle), ring append, the stream's VAD gate.  An empty slot (head -1) scores 0.
+// Model.predict's post-processing (model.py:330-381) per (stream, slot) of the bank: owq::score_rule on the slot's own prediction count
+// and ring, with the patience and threshold of the slot's bank head (debounce frames shared with the handle), then the stream's VAD
+// gate.  An empty slot (head -1) scores 0.
 struct BankPostParams {
     const float* raw; float* scores; float* ring; uint32_t* npred;
     const int* sub;                   // [S][K] bank head of each slot, -1 = empty
-    const int* patience; const float* threshold; int debounce_frames;
     int S, K;
-    const float* vad_ring; const uint32_t* n_vad; float vad_threshold;
+    owq::Rules rules;                 // per bank head
+    owq::Gate gate;
     const uint8_t* stream_on;
 };
 __global__ void bank_post_kernel(BankPostParams p) {
@@ -2591,37 +2559,9 @@ __global__ void bank_post_kernel(BankPostParams p) {
     const int hd = p.sub[i];
     if (hd < 0) { p.scores[i] = 0.0f; return; }
     const uint32_t cnt = p.npred[i];
-    const int have = cnt < 30u ? (int)cnt : 30;
-    float sc = p.raw[i];
-    float* ring = p.ring + (size_t)i * 30;
-    if (cnt < 5u) sc = 0.0f;                                                // model.py:331-333
-    if (sc != 0.0f) {
-        const int pat = p.patience[hd];
-        const float thr = p.threshold[hd];
-        if (pat > 0) {                                                      // model.py:349-352
-            const int look = pat < have ? pat : have;
-            int n_ok = 0;
-            for (int k = 1; k <= look; ++k) n_ok += ring[(cnt - k) % 30u] >= thr ? 1 : 0;
-            if (n_ok < pat) sc = 0.0f;
-        } else if (p.debounce_frames > 0 && thr == thr) {                   // model.py:353-359
-            const int look = p.debounce_frames < have ? p.debounce_frames : have;
-            int n_hit = 0;
-            for (int k = 1; k <= look; ++k) n_hit += ring[(cnt - k) % 30u] >= thr ? 1 : 0;
-            if (sc >= thr && n_hit > 0) sc = 0.0f;
-        }
-    }
-    ring[cnt % 30u] = sc;                                                   // model.py:362-363
+    const float sc = owq::score_rule(p.raw[i], cnt, p.ring + (size_t)i * owq::kScoreRing, p.rules, hd);
     p.npred[i] = cnt + 1u;
-    if (p.vad_threshold > 0.0f) {                                           // model.py:375-381
-        const uint32_t L = p.n_vad[s];
-        float vmax = 0.0f;
-        if (L >= 5u) {
-            vmax = -INFINITY;
-            for (uint32_t k = (L >= 7u ? L - 7u : 0u); k + 5u <= L; ++k) vmax = fmaxf(vmax, p.vad_ring[(size_t)s * 8 + (k & 7u)]);
-        }
-        if (vmax < p.vad_threshold) sc = 0.0f;
-    }
-    p.scores[i] = sc;
+    p.scores[i] = owq::gate_closed(p.gate, s) ? 0.0f : sc;
 }
 // restart of bank slots (a new head subscribed, oww_reset): prediction count, ring, raw and final score of each listed slot index
 __global__ void bank_clear_kernel(const int* idx, int n, float* raw, float* scores, float* ring, uint32_t* npred) {
@@ -2629,7 +2569,7 @@ __global__ void bank_clear_kernel(const int* idx, int n, float* raw, float* scor
     if (i >= n) return;
     const int k = idx[i];
     raw[k] = 0.0f; scores[k] = 0.0f; npred[k] = 0u;
-    for (int r = 0; r < 30; ++r) ring[(size_t)k * 30 + r] = 0.0f;
+    for (int r = 0; r < owq::kScoreRing; ++r) ring[(size_t)k * owq::kScoreRing + r] = 0.0f;
 }
 
 }  // namespace owh

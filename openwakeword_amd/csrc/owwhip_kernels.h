@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "owwhip_layout.h"
+#include "owwhip_postproc.h"       // owq: the post-processing rule and the VAD gate
 #include "owwhip_verifier_host.h"  // owk::SvEntry, SV_PAIRS
 
 namespace owk {
@@ -1444,21 +1445,16 @@ __global__ __launch_bounds__(HD_NT) void heads64_kernel(HeadParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// post-processing (model.py:330-363): one thread per stream
+// post-processing (model.py:330-381; the rule and the gate: owwhip_postproc.h): one thread per stream
 // ------------------------------------------------------------------------------------------------
 struct PostParams {
     const float* raw;        // [S][NL]
     float* scores;           // [S][NL]
-    float* ring;             // [S][NL][30]
+    float* ring;             // [S][NL][owq::kScoreRing]
     uint32_t* npred;         // [S]
-    const int* patience;     // [NL]
-    const float* threshold;  // [NL]  (NaN = no threshold for this label)
-    int debounce_frames;
     int NL, S;
-    // VAD gate (model.py:366-381): per-stream ring of the caller-supplied voice-activity scores, 8 deep
-    const float* vad_ring;   // [S][8]
-    const uint32_t* n_vad;   // [S] scores pushed so far
-    float vad_threshold;     // <= 0: gate off
+    owq::Rules rules;        // per label
+    owq::Gate gate;          // the caller-supplied or on-device voice-activity scores of each stream
     const uint8_t* stream_on;    // oww_step_masked: [S] 1 = the stream takes part in this step; nullptr = all do
 };
 
@@ -1467,50 +1463,18 @@ __global__ void postproc_kernel(PostParams p) {
     if (s >= p.S) return;
     if (p.stream_on && !p.stream_on[s]) return;
     const uint32_t cnt = p.npred[s];
-    const int have = cnt < 30u ? (int)cnt : 30;
     for (int l = 0; l < p.NL; ++l) {
-        float sc = p.raw[(size_t)s * p.NL + l];
-        float* ring = p.ring + ((size_t)s * p.NL + l) * 30;
-        if (cnt < 5u) sc = 0.0f;                                            // model.py:331-333
-        if (sc != 0.0f) {
-            const int pat = p.patience[l];
-            const float thr = p.threshold[l];
-            if (pat > 0) {                                                  // model.py:349-352
-                const int look = pat < have ? pat : have;
-                int n_ok = 0;
-                for (int i = 1; i <= look; ++i) n_ok += ring[(cnt - i) % 30u] >= thr ? 1 : 0;
-                if (n_ok < pat) sc = 0.0f;
-            } else if (p.debounce_frames > 0 && thr == thr) {               // model.py:353-359
-                const int look = p.debounce_frames < have ? p.debounce_frames : have;
-                int n_hit = 0;
-                for (int i = 1; i <= look; ++i) n_hit += ring[(cnt - i) % 30u] >= thr ? 1 : 0;
-                if (sc >= thr && n_hit > 0) sc = 0.0f;
-            }
-        }
-        ring[cnt % 30u] = sc;                                               // model.py:362-363
-        p.scores[(size_t)s * p.NL + l] = sc;
+        const size_t i = (size_t)s * p.NL + l;
+        p.scores[i] = owq::score_rule(p.raw[i], cnt, p.ring + i * owq::kScoreRing, p.rules, l);
     }
     p.npred[s] = cnt + 1u;
-    if (p.vad_threshold > 0.0f) {
-        // model.py:375-381: the score ring above keeps the ungated values; the returned scores of this step are zeroed when the
-        // largest VAD score of ring[-7:-4] (entries L-7 .. L-5 of the L pushed so far; none while L < 5) is below the threshold
-        const uint32_t L = p.n_vad[s];
-        float vmax = 0.0f;
-        if (L >= 5u) {
-            vmax = -INFINITY;
-            for (uint32_t i = (L >= 7u ? L - 7u : 0u); i + 5u <= L; ++i) vmax = fmaxf(vmax, p.vad_ring[(size_t)s * 8 + (i & 7u)]);
-        }
-        if (vmax < p.vad_threshold)
-            for (int l = 0; l < p.NL; ++l) p.scores[(size_t)s * p.NL + l] = 0.0f;
-    }
+    if (owq::gate_closed(p.gate, s))
+        for (int l = 0; l < p.NL; ++l) p.scores[(size_t)s * p.NL + l] = 0.0f;
 }
 
 __global__ void push_vad_kernel(float* ring, uint32_t* n_vad, const float* scores, int S) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    const uint32_t L = n_vad[s];
-    ring[(size_t)s * 8 + (L & 7u)] = scores[s];
-    n_vad[s] = L + 1u;
+    if (s < S) owq::vad_push(ring, n_vad, s, scores[s]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1881,9 +1845,7 @@ __global__ void ingest_hist_reset_kernel(int16_t* hist, int Hpad, const int* ids
 __global__ void vad_ring_reset_kernel(float* ring, uint32_t* n_vad, const int* ids, int n) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
-    const int s = ids ? ids[k] : k;
-    for (int i = 0; i < 8; ++i) ring[(size_t)s * 8 + i] = 0.f;
-    n_vad[s] = 0u;
+    owq::vad_clear(ring, n_vad, ids ? ids[k] : k);
 }
 
 __global__ void advance_kernel(uint32_t* nfeat, int S, const uint8_t* stream_on) {

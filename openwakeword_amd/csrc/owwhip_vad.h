@@ -14,8 +14,8 @@
 //                      16-stream tiles the LSTM kernel consumes.  Encoder weights (72 KB) stay in LDS for the persistent launch.
 //   vad_lstm_kernel    per 16 streams: 2-layer LSTM(64) over the 4 time steps of the step (state h, c in HBM, register-dump
 //                      order), gates as fp16-split MFMAs with the weights streamed L2 -> LDS in 16 KB chunks shared by the
-//                      workgroup (same scheme as the CNN stages), sigmoid decoder, mean -> the stream's VAD ring (postproc_kernel
-//                      applies the gate).
+//                      workgroup (same scheme as the CNN stages), sigmoid decoder, mean -> the stream's VAD ring (owq::vad_push; the
+//                      post-processing launch applies owq::gate_closed: owwhip_postproc.h).
 #pragma once
 #include "owwhip_hx.h"
 
@@ -284,7 +284,7 @@ struct VadLstmParams {
     const float* bias;      // [2][256], PyTorch gate order
     const float* wd;        // [64] decoder
     float bd;
-    float* ring;            // [S][8] VAD score ring (postproc_kernel)
+    float* ring;            // [S][owq::kVadRing] VAD score ring (owq::vad_push; read by owq::gate_closed)
     uint32_t* n_vad;        // [S]
     float* last;            // [S] the score just pushed
     int S, n_groups;
@@ -405,9 +405,7 @@ __global__ __launch_bounds__(64 * L_WG, 2) void vad_lstm_kernel(VadLstmParams p)
         }
         if (j == 0) {
             const float score = yacc * 0.25f;                  // mean over the 2 sub-frames x 2 time steps (vad.py:127)
-            const uint32_t L = p.n_vad[s];
-            p.ring[(size_t)s * 8 + (L & 7u)] = score;
-            p.n_vad[s] = L + 1u;
+            owq::vad_push(p.ring, p.n_vad, s, score);
             p.last[s] = score;
         }
     }
@@ -425,8 +423,7 @@ __global__ void vad_reset_kernel(float* hc, float* ring, uint32_t* n_vad, float*
         const int a = i >> 6, r = (i >> 2) & 15, jj = i & 3;
         base[a * 1024 + r * 64 + jj * 16 + (s & 15)] = 0.f;
     }
-    if (threadIdx.x < 8) ring[(size_t)s * 8 + threadIdx.x] = 0.f;
-    if (threadIdx.x == 0) { n_vad[s] = 0u; last[s] = 0.f; }
+    if (threadIdx.x == 0) { owq::vad_clear(ring, n_vad, s); last[s] = 0.f; }
 }
 
 }  // namespace owv

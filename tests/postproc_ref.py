@@ -2,8 +2,8 @@
 post-processing tests drive through them and through the device.
 
 `reference_rules` is the literal form: one `collections.deque(maxlen=30)` per (stream, label) or (stream, slot), one Python list of
-voice-activity scores per stream, sliced as `[-patience:]`, `[-n_frames:]` and `[-7:-4]`.  `device_rules` is the form the three device
-copies take (owk::postproc_kernel, the epilogue of owh::heads_hx_kernel, owh::bank_post_kernel): a uint32 count, `ring[cnt % 30]`,
+voice-activity scores per stream, sliced as `[-patience:]`, `[-n_frames:]` and `[-7:-4]`.  `device_rules` is the form the device code takes
+(csrc/owwhip_postproc.h, called by owk::postproc_kernel, the epilogue of owh::heads_hx_kernel, owh::bank_post_kernel): a uint32 count, `ring[cnt % 30]`,
 `have = min(cnt, 30)`, a VAD ring of 8 indexed by `L & 7` -- vectorised over streams and labels -- and it takes a named FAULT, one
 plausible slip of such a kernel each.  The rules are discrete (a final score is the raw score's bits or 0.0), so the two forms, and the
 device, are compared by np.array_equal on the float32 bits; the faults say whether a comparison could have noticed anything.

@@ -1,13 +1,26 @@
 """The post-processing rules without a device (tests/postproc_ref.py): the literal restatement equals the oracle's Model.predict (which
 tests/test_oracle_golden.py pins to vectors the reference produced), the device-form mirror equals the literal restatement bit for bit on
 the schedule the GPU tests run, and every fault of the catalogue moves at least one final score there -- on scripted score tables that
-hold exact 0.0 and 1.0, values equal to the thresholds and values one float32 step either side of them."""
+hold exact 0.0 and 1.0, values equal to the thresholds and values one float32 step either side of them.  And the code the kernels run:
+csrc/owwhip_postproc.h as a plain host program (tests/postproc_check.cpp) under AddressSanitizer / UBSan, held to the device-form mirror
+bit for bit on every state the full schedule visits."""
+import atexit
+import functools
+import os
+import shutil
+import subprocess
+import tempfile
+
 import numpy as np
 import pytest
 
 import postproc_ref as P
 from oracle import oww_oracle as O
+from openwakeword_amd import _build
 from openwakeword_amd import weights as W
+
+from test_abi_cpu import ROOT
+from test_pack_host_cpu import _host_clangxx
 
 F32 = np.float32
 NAMES = ["alexa", "hey_mycroft", "hey_rhasspy"]
@@ -157,3 +170,139 @@ def test_each_gpu_path_schedule_lets_every_applicable_fault_show(path, S):
             break
     silent = [f for f, n in total.items() if n == 0]
     assert not silent, silent
+
+
+# ---- the code the kernels run: csrc/owwhip_postproc.h through tests/postproc_check.cpp ----------------------------------------------
+@functools.lru_cache(maxsize=None)
+def postproc_exe():
+    """Path of the built check program (one build per test run)."""
+    cxx = _host_clangxx()
+    if cxx is None or not os.path.exists(cxx):
+        pytest.skip("ROCm's host clang++ (lib/llvm/bin/clang++ next to hipcc) is not installed")
+    import torch
+    d = tempfile.mkdtemp(prefix="postproc_check")
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    exe = os.path.join(d, "postproc_check")
+    sanitize = [] if torch.cuda.is_available() else ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", *sanitize, os.path.join(ROOT, "tests", "postproc_check.cpp"),
+                    "-I" + os.path.join(ROOT, "openwakeword_amd", "csrc"), "-I" + os.path.join(ROOT, "include"), "-o", exe], check=True)
+    return exe
+
+
+def run_postproc(*args):
+    """stdout of one run; the run must end clean and silent."""
+    run = subprocess.run([postproc_exe(), *args], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stderr == "", f"exit {run.returncode}:\n{run.stderr[-4000:]}"
+    return run.stdout
+
+
+@functools.lru_cache(maxsize=None)
+def recorded():
+    """Every pair postproc_ref._rules and every stream postproc_ref._gate_closed is invoked on while device_rules(fault=None) runs the full
+    schedule (fixed labels and the bank) at S = 37 and S = 1: inputs as they went in, and what the mirror made of them.  The pushes are
+    read off the gate's successive views of a stream's VAD ring (one more score than the call before)."""
+    rule, gate, push = [], [], []
+    real_rules, real_gate = P._rules, P._gate_closed
+
+    def spy_rules(raw, cnt, ring, pat, thr, frames, live, gated, fault):
+        before = ring.copy()
+        fin = real_rules(raw, cnt, ring, pat, thr, frames, live, gated, fault)
+        at = np.nonzero(live)
+        rule.append((np.asarray(cnt)[at], np.asarray(raw, F32)[at], np.asarray(pat)[at], np.asarray(thr, F32)[at],
+                     np.full(len(at[0]), frames), before[at], ring[at], fin[at], gated[at[0]]))
+        return fin
+
+    def spy_gate(vring, nv, thr, fault):
+        closed = real_gate(vring, nv, thr, fault)
+        views.append((nv.copy(), np.full(len(nv), thr, F32), vring.copy(), closed))
+        return closed
+
+    P._rules, P._gate_closed = spy_rules, spy_gate
+    try:
+        for S in (37, 1):
+            views = []
+            raw, head_raw = _tables(S, 12, 2)
+            P.device_rules(_full(S, P.picker(raw, head_raw)), raw, head_raw)
+            gate += views
+            for (n0, _, v0, _), (n1, _, v1, _) in zip(views, views[1:]):
+                s = np.nonzero(n1 == n0 + 1)[0]
+                push.append((n0[s], v1[s, n0[s] & 7], v0[s], n1[s], v1[s]))
+    finally:
+        P._rules, P._gate_closed = real_rules, real_gate
+    names = (("cnt", "raw", "pat", "thr", "frames", "ring", "ring_after", "fin", "gated"), ("L", "thr", "ring", "closed"),
+             ("L", "value", "ring", "L_after", "ring_after"))
+    return tuple({k: np.concatenate(col) for k, col in zip(ks, zip(*rows))} for ks, rows in zip(names, (rule, gate, push)))
+
+
+def _words(*cols):
+    """uint32 rows: integer columns as they are (two's complement), float32 columns as their bits."""
+    out = []
+    for c in cols:
+        c = np.asarray(c)
+        c = P.bits(c) if c.dtype == F32 else c.astype(np.int64).astype(np.uint32)
+        out.append(c.reshape(len(c), -1))
+    return np.ascontiguousarray(np.concatenate(out, 1))
+
+
+def test_header_self_checks_under_the_sanitizers():
+    """Counts at the uint32 wrap (0xFFFFFFFF, then 0), the VAD push there, the per-stream clear, the gate's window: worked by hand in
+    the program."""
+    assert run_postproc() == "done 1\n"
+
+
+def test_header_is_a_build_input_free_of_hip_and_the_only_copy_of_the_rule():
+    csrc = os.path.join(ROOT, "openwakeword_amd", "csrc")
+    with open(os.path.join(csrc, "owwhip_postproc.h")) as f:
+        src = f.read()
+    assert "#pragma once" in src and "hip/" not in src and "__global__" not in src
+    assert "owwhip_postproc.h" in [os.path.basename(d) for d in _build.DEPS]
+    for name in ("owwhip_kernels.h", "owwhip_hx.h", "owwhip.hip"):
+        with open(os.path.join(csrc, name)) as f:
+            text = f.read()
+        assert '#include "owwhip_postproc.h"' in text, name
+        assert "n_ok" not in text and "n_hit" not in text and "% 30u" not in text and "& 7u)]" not in text, name     # (the copies' own text)
+
+
+def test_header_equals_the_device_form_on_every_state_of_the_full_schedule(tmp_path):
+    r, g, p = recorded()
+    n = [len(r["cnt"]), len(g["L"]), len(p["L"])]
+    D = P.DEPTH
+    have = np.minimum(r["cnt"], D)
+    reached = (r["cnt"] >= 5) & (r["raw"] != 0)                   # the pair's rule is consulted
+    # ---- not vacuous: the classes the schedule was built to contain really went in
+    assert (reached & (r["pat"] > 0) & (have < r["pat"])).any()                                     # patience with look < pat
+    look = np.minimum(r["frames"], have)
+    back = (r["cnt"][:, None] - np.arange(1, D + 1)[None, :]) % D                                   # slot of the i-th entry back
+    seen = np.take_along_axis(r["ring"], back, 1)
+    in_look = np.arange(1, D + 1)[None, :] <= look[:, None]
+    deb = reached & (r["pat"] <= 0) & (r["frames"] > 0) & ~np.isnan(r["thr"])
+    assert (deb & (in_look & (seen == r["thr"][:, None])).any(1)).any()                             # debounce meets an entry equal to the threshold
+    assert (reached & np.isnan(r["thr"]) & (r["pat"] <= 0) & (r["frames"] > 0)).any()               # a NaN threshold where debounce is on
+    assert {4, 5, 29, 30, 31} <= set(r["cnt"].tolist())
+    gated = g["thr"] > 0
+    assert {4, 5, 6, 7, 8} <= set(g["L"][gated].tolist())
+    win = np.stack([g["ring"][np.arange(n[1]), (g["L"] - j) & 7] for j in (7, 6, 5)], 1)
+    in_win = np.stack([g["L"] >= j for j in (7, 6, 5)], 1)
+    assert (gated & (in_win & (win == g["thr"][:, None])).any(1)).any()                             # a VAD score equal to the gate's threshold
+    assert (~gated).any() and g["closed"][gated].any() and (~g["closed"][gated]).any() and n[2] > 1000
+    # ---- the program's answers
+    src, dst = str(tmp_path / "cases.u32"), str(tmp_path / "answers.u32")
+    with open(src, "wb") as f:
+        np.array(n, np.uint32).tofile(f)
+        _words(r["cnt"], r["raw"], r["pat"], r["thr"], r["frames"], r["ring"]).tofile(f)
+        _words(g["L"], g["thr"], g["ring"]).tofile(f)
+        _words(p["L"], p["value"], p["ring"]).tofile(f)
+    assert run_postproc(src, dst) == ""
+    got = np.fromfile(dst, np.uint32)
+    assert got.size == n[0] * (1 + D) + n[1] + n[2] * 9
+    got_rule = got[:n[0] * (1 + D)].reshape(n[0], 1 + D)
+    got_gate = got[n[0] * (1 + D):n[0] * (1 + D) + n[1]]
+    got_push = got[n[0] * (1 + D) + n[1]:].reshape(n[2], 9)
+    # the mirror appends the ungated score to the ring and returns the gated one
+    ungated = np.take_along_axis(r["ring_after"], (r["cnt"] % D)[:, None], 1)[:, 0]
+    assert np.array_equal(P.bits(np.where(r["gated"], F32(0.0), ungated)), P.bits(r["fin"]))
+    assert np.array_equal(got_rule[:, 0], P.bits(ungated))
+    assert np.array_equal(got_rule[:, 1:], P.bits(r["ring_after"]))
+    assert np.array_equal(got_gate, g["closed"].astype(np.uint32))
+    assert np.array_equal(got_push, _words(p["L_after"], p["ring_after"]))
+    assert (ungated != 0).sum() > 1000 and ((ungated == 0) & reached).sum() > 1000                 # the rules let through, and refused

@@ -1,5 +1,5 @@
-"""The three device copies of Model.predict's post-processing -- owk::postproc_kernel, the epilogue of owh::heads_hx_kernel and
-owh::bank_post_kernel -- held to tests/postproc_ref.py's reference_rules BIT FOR BIT (np.array_equal on uint32 views).
+"""The three launch sites of Model.predict's post-processing (csrc/owwhip_postproc.h) -- owk::postproc_kernel, the epilogue of
+owh::heads_hx_kernel and owh::bank_post_kernel -- held to tests/postproc_ref.py's reference_rules BIT FOR BIT (np.array_equal on uint32 views).
 
 Method.  A twin handle runs the identical call sequence (audio, resets, masks, subscriptions, chunk counts) with no rules and no gate.
 Heads, verifier and post-processing never feed back into raw scores, so the twin's raw table is the subject's (read from the subject
