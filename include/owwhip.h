@@ -421,6 +421,38 @@ int  oww_assign_verifiers(oww_ctx* h, int32_t label, const int32_t* stream_ids, 
 int  oww_bank_assign_verifiers(oww_ctx* h, int32_t slot, const int32_t* stream_ids, int32_t n, const int32_t* verifier_ids, const float* thresholds);
 int  oww_verifier_stats(oww_ctx* h, int64_t out[2]);
 
+/* ---- fitting custom verifiers on the device (custom_verifier_model.py:95-113) ------------------------------------------------------
+ * custom_verifier_model.train_verifier_model (custom_verifier_model.py:95-113) fits flatten -> StandardScaler ->
+ * LogisticRegression(C = 0.001) to one user's feature windows.  oww_verifier_fit fits U such problems in one call and leaves each
+ * result in the pool, folded, as oww_verifier_add would have: for problem u, windows offsets[u] .. offsets[u + 1] - 1 of `windows`
+ * ([offsets[U]][T][96] fp32; a window flattened row-major as flatten_features does; on the device when windows_on_device, e.g.
+ * oww_event_features_dev or the `windows` buffer of a hit list) with labels[i] in {0, 1} (host):
+ *   mu, s = column mean and standard deviation (ddof = 0; s = 1 where a column is exactly constant), z = (x - mu) / s;
+ *   (w~, b) = argmin C sum_i logloss(y_i, z_i . w~ + b) + 1/2 |w~|^2 (the intercept not penalised: scikit-learn's objective);
+ *   w = w~ / s, bias = b - sum_j w_j mu_j  -> pool slot out[u].id, T recorded.
+ * It is the optimum of that objective, not scikit-learn's iterate at its default tol = 1e-4, which sits up to 1e-3 in score from it.
+ * Solved in the dual (an N x N Gram matrix per problem on f16-split MFMAs, then a Newton iteration in one workgroup); N = 2 ..
+ * OWW_FIT_MAX_N windows per problem.  A problem's result does not depend on what else is in the call.
+ * Per problem out[u].status: OWW_FIT_OK (id >= 0: the verifier is live in the pool); OWW_FIT_ONE_CLASS (scikit-learn raises there);
+ * OWW_FIT_BAD_N (N < 2 or > OWW_FIT_MAX_N); OWW_FIT_NONFINITE (a window holds a NaN or an infinity); OWW_FIT_NOT_CONVERGED (the
+ * iteration cap was reached).  Every status but OK gives id = -1, and the other problems of the call proceed.  iterations = Newton
+ * steps, residual = max_i |a_i + C (p_i - y_i)| / C, the stationarity residual in score units.
+ * Whole-call refusals (nothing changed): no pool or handle not committed (OWW_ESTATE); T outside 1 .. feature ring, offsets not
+ * ascending, a label other than 0 or 1, C not finite or <= 0, fewer free pool slots than problems that pass the host-side checks
+ * (OWW_EINVAL).  The work is enqueued on the handle's stream behind every submitted step and the call returns when it is done; the
+ * step path of a handle that never calls it is unchanged.
+ *   oww_verifier_get    reads pool verifier `id` back: w[n_w] (n_w = its T x 96) and *bias; waits for the handle's stream. */
+#define OWW_FIT_MAX_N          1024
+#define OWW_FIT_OK             0
+#define OWW_FIT_ONE_CLASS      1
+#define OWW_FIT_BAD_N          2
+#define OWW_FIT_NONFINITE      3
+#define OWW_FIT_NOT_CONVERGED  4
+typedef struct { int32_t status, id, n_pos, n_neg, iterations; float residual; } oww_fit_result;
+int  oww_verifier_fit(oww_ctx* h, const float* windows, int windows_on_device, const int64_t* offsets, const uint8_t* labels,
+                      int32_t U, int32_t T, float C, oww_fit_result* out);      /* custom_verifier_model.py:95-113 */
+int  oww_verifier_get(oww_ctx* h, int32_t id, float* w, int32_t n_w, float* bias);      /* custom_verifier_model.py:95-113: the fitted (coef / scale, folded intercept) */
+
 /* ---- stream state records: take a live stream's state out, put it in, move it ---------------------------------------------------------
  * In the reference a stream's state IS its Model object (prediction_buffer model.py:198, reset model.py:226-230; the AudioFeatures
  * buffers utils.py:163-171): a caller keeps it, hands it to another thread or pickles it.  Here that state lives in HBM in layouts only

@@ -22,6 +22,16 @@ class Config(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class FitResult(C.Structure):
+    """oww_fit_result (include/owwhip.h)"""
+    _fields_ = [("status", C.c_int32), ("id", C.c_int32), ("n_pos", C.c_int32), ("n_neg", C.c_int32), ("iterations", C.c_int32),
+                ("residual", C.c_float)]
+
+
+FIT_MAX_N = 1024         # OWW_FIT_MAX_N
+FIT_STATUS = ("OK", "ONE_CLASS", "BAD_N", "NONFINITE", "NOT_CONVERGED")      # OWW_FIT_*
+
+
 class IngestClass(C.Structure):
     """oww_ingest_class (include/owwhip.h)"""
     _fields_ = [("encoding", C.c_int32), ("p", C.c_int32), ("q", C.c_int32), ("n_taps", C.c_int32), ("taps", C.c_void_p)]
@@ -110,6 +120,8 @@ SYMBOLS = {
     "oww_assign_verifiers": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
     "oww_bank_assign_verifiers": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
     "oww_verifier_stats": (C.c_int, [_P, _P]),
+    "oww_verifier_fit": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_float, C.POINTER(FitResult)]),
+    "oww_verifier_get": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.POINTER(C.c_float)]),
     "oww_state_info": (C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "oww_state_export": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),
     "oww_state_import": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),

@@ -36,6 +36,7 @@
 #include "owwhip_audio.h"
 #include "owwhip_dense.h"
 #include "owwhip_dense_hits_host.h"
+#include "owwhip_fit.h"
 
 using namespace owk;
 using namespace owp;
@@ -351,6 +352,17 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
     std::vector<float> ver_thr;                  // host copy of d_verthr (the handle-wide verifiers' thresholds)
     DevBuf<SvEntry> d_svlist; int sv_n = 0;      // [S * (NL + K)] capacity; sv_n entries in use
     DevBuf<unsigned long long> d_sv_eval;        // evaluations of the last step
+    // oww_verifier_fit's scratch (owwhip_fit.h), grown by the first call that needs it: nothing before that
+    struct FitScratch {
+        DevBuf<float> x, K, a, b;
+        DevBuf<uint16_t> zh, zl;                 // (f16 bits)
+        DevBuf<double> mu, sd;
+        DevBuf<unsigned char> y;
+        DevBuf<int> flag;
+        DevBuf<owf::Record> rec;
+        DevBuf<owf::Problem> prob;
+        DevBuf<owf::Tile> tiles;
+    } fit;
     // stream state records (oww_state_*, oww_move_streams; owwhip_state.h): built by the first of those calls, nothing before it
     bool st_ready = false;
     std::vector<ows::FlatSection> st_flat;       // host copy of d_st_flat
@@ -3804,6 +3816,91 @@ int oww_verifier_remove(oww_ctx* h, int32_t id) {
         for (int& v : *tab) if (v == id) { v = OWW_VERIFIER_DEFAULT; --h->vasg_n; }
     h->vpool_T[id] = 0;
     return sv_rebuild(h);
+    OWW_GUARD_END
+}
+
+// ---- fitting custom verifiers on the device (owwhip_fit.h; host side: owwhip_fit_host.h) ---------------------------------------------
+int oww_verifier_fit(oww_ctx* h, const float* windows, int windows_on_device, const int64_t* offsets, const uint8_t* labels, int32_t U, int32_t T, float C,
+                     oww_fit_result* out) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    if (int rc = owf::check_args(h->committed, h->vpool_cap, windows, offsets, labels, U, T, h->TR, C, out)) return rc;
+    if (U == 0) return OWW_OK;
+    std::vector<oww_fit_result> res((size_t)U);
+    owf::classify(offsets, labels, U, res.data());
+    if (int rc = owf::assign_ids(h->vpool_T, U, res.data())) return rc;
+    std::vector<int> run, Ns;                          // the problems that go to the device, and their N
+    for (int u = 0; u < U; ++u) if (res[u].status == OWW_FIT_OK) { run.push_back(u); Ns.push_back((int)(offsets[u + 1] - offsets[u])); }
+    const long long D = (long long)T * OWW_EMB_DIM;
+    long long budget = owf::kDefaultBudget;
+    if (const char* e = getenv("OWW_FIT_SCRATCH_BYTES")) budget = std::max(1ll, atoll(e));
+    const std::vector<owf::Slab> slabs = owf::slab_plan(Ns, D, budget, windows_on_device != 0);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    auto& F = h->fit;
+    std::vector<owf::Record> recs;
+    for (const owf::Slab& sl : slabs) {
+        const int np = sl.last - sl.first;
+        std::vector<owf::Problem> prob((size_t)np);
+        std::vector<unsigned char> y((size_t)sl.rows);
+        long long row = 0, koff = 0;
+        for (int i = 0; i < np; ++i) {
+            const int u = run[sl.first + i], N = Ns[sl.first + i];
+            prob[i] = owf::Problem{windows_on_device ? (long long)offsets[u] * D : row * D, row, koff, row, N, res[u].id, u, 0};
+            memcpy(y.data() + row, labels + offsets[u], (size_t)N);
+            row += N; koff += (long long)N * N;
+        }
+        const std::vector<owf::Tile> tiles = owf::tile_map(Ns, sl.first, sl.last);
+        const size_t zn = (size_t)sl.rows * D;
+        bool ok = grow(h, F.zh, zn) == hipSuccess && grow(h, F.zl, zn) == hipSuccess && grow(h, F.K, (size_t)sl.k_floats) == hipSuccess &&
+                  grow(h, F.a, (size_t)sl.rows) == hipSuccess && grow(h, F.b, (size_t)np) == hipSuccess && grow(h, F.mu, (size_t)np * D) == hipSuccess &&
+                  grow(h, F.sd, (size_t)np * D) == hipSuccess && grow(h, F.y, (size_t)sl.rows) == hipSuccess && grow(h, F.flag, (size_t)np) == hipSuccess &&
+                  grow(h, F.rec, (size_t)np) == hipSuccess && grow(h, F.prob, (size_t)np) == hipSuccess && grow(h, F.tiles, tiles.size()) == hipSuccess;
+        if (ok && !windows_on_device) ok = grow(h, F.x, zn) == hipSuccess;
+        if (!ok) return fail(OWW_ENOMEM, "oww_verifier_fit: out of device memory for a slab of %d problems (%lld windows)", np, sl.rows);
+        if (!windows_on_device)                         // the slab's windows, problem after problem (skipped problems leave gaps in the call's)
+            for (int i = 0; i < np; ++i)
+                HIPCHK(copy_async(F.x + prob[i].x_off, windows + (size_t)offsets[prob[i].u] * D, (size_t)prob[i].N * D * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(copy_async(F.prob, prob.data(), prob.size() * sizeof(owf::Problem), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(copy_async(F.tiles, tiles.data(), tiles.size() * sizeof(owf::Tile), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(copy_async(F.y, y.data(), y.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemsetAsync(F.flag, 0, (size_t)np * sizeof(int), h->stream));
+        owfk::FitParams p{};
+        p.prob = F.prob; p.x = windows_on_device ? windows : F.x.get(); p.y = F.y;
+        p.zh = reinterpret_cast<_Float16*>(F.zh.get()); p.zl = reinterpret_cast<_Float16*>(F.zl.get());
+        p.mu = F.mu; p.sd = F.sd; p.K = F.K; p.a = F.a; p.b = F.b; p.flag = F.flag; p.rec = F.rec; p.tiles = F.tiles;
+        p.n_tiles = (int)tiles.size(); p.n_prob = np; p.D = (int)D; p.C = C;
+        p.pool_w = h->d_vpool_w; p.pool_b = h->d_vpool_b; p.pool_stride = h->vpool_stride;
+        hipLaunchKernelGGL(owfk::fit_stats_kernel, dim3((unsigned)((D + 255) / 256), np), dim3(256), 0, h->stream, p);
+        hipLaunchKernelGGL(owfk::fit_gram_kernel, dim3((unsigned)((tiles.size() + 3) / 4)), dim3(256), 0, h->stream, p);
+        hipLaunchKernelGGL(owfk::fit_solve_kernel, dim3(np), dim3(owfk::kSolveThreads), 0, h->stream, p);
+        hipLaunchKernelGGL(owfk::fit_fold_kernel, dim3(np), dim3(256), 0, h->stream, p);
+        HIPCHK(hipGetLastError());
+        recs.resize((size_t)np);
+        HIPCHK(copy_async(recs.data(), F.rec, (size_t)np * sizeof(owf::Record), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));       // the slab's scratch and host staging are free again; its records are here
+        for (int i = 0; i < np; ++i) {
+            oww_fit_result& r = res[prob[i].u];
+            r.status = recs[i].status; r.iterations = recs[i].iterations; r.residual = recs[i].residual;
+            if (r.status == OWW_FIT_OK) h->vpool_T[r.id] = T;     // live, exactly as after oww_verifier_add
+            else r.id = -1;
+        }
+    }
+    for (int u = 0; u < U; ++u) out[u] = res[u];
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_verifier_get(oww_ctx* h, int32_t id, float* w, int32_t n_w, float* bias) {
+    OWW_GUARD_BEGIN
+    if (!h || !h->committed || h->vpool_cap == 0) return fail(OWW_ESTATE, "oww_verifier_get: no verifier pool on this handle");
+    if (id < 0 || id >= h->vpool_cap || h->vpool_T[id] == 0) return fail(OWW_EINVAL, "oww_verifier_get: %d is not a pool verifier", id);
+    if (!w || !bias || n_w != h->vpool_T[id] * OWW_EMB_DIM)
+        return fail(OWW_EINVAL, "oww_verifier_get: room for %d weights, verifier %d has %d x 96", n_w, id, h->vpool_T[id]);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(copy_sync(w, h->d_vpool_w + (size_t)id * h->vpool_stride, (size_t)n_w * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(copy_sync(bias, h->d_vpool_b + id, sizeof(float), hipMemcpyDeviceToHost));
+    return OWW_OK;
     OWW_GUARD_END
 }
 

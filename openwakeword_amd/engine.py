@@ -193,6 +193,11 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def C_void(address) -> C.c_void_p:
+    """a device address (int, or anything with data_ptr(), e.g. a torch tensor) as a pointer argument"""
+    return C.c_void_p(int(address.data_ptr()) if hasattr(address, "data_ptr") else int(address))
+
+
 _CAL_CLIPS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "resources", "calibration_clips.npz")
 
 
@@ -705,6 +710,34 @@ class StreamEngine:
         t = np.ascontiguousarray(thresholds, dtype=np.float32).ravel()
         fn = self._lib.oww_bank_assign_verifiers if bank else self._lib.oww_assign_verifiers
         _lib.check(fn(self._h, int(label), _ptr(ids), ids.size, _ptr(v), _ptr(t)))
+
+    def verifier_fit(self, windows, offsets, labels, T: int, C: float = 0.001, on_device: bool = False) -> List[dict]:
+        """oww_verifier_fit: problem u = windows offsets[u] .. offsets[u+1]-1 of `windows` ([n, T, 96] fp32 on the host, or a device
+        address of such a buffer with on_device) with `labels` [n] in {0, 1} -> one dict per problem (status, id, n_pos, n_neg,
+        iterations, residual); an OK problem's verifier is live in the pool under its id."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+        lab = np.ascontiguousarray(labels, dtype=np.uint8).ravel()
+        U = off.size - 1
+        if U < 0 or (U >= 0 and lab.size < int(off[-1])):
+            raise ValueError(f"offsets [U+1] and {int(off[-1]) if off.size else 0} labels expected, got {off.size} offsets and {lab.size} labels")
+        if on_device:
+            wp = C_void(windows)
+        else:
+            w = np.ascontiguousarray(windows, dtype=np.float32)
+            if w.size < int(off[-1]) * int(T) * 96:
+                raise ValueError(f"{int(off[-1])} windows of {T} x 96 floats expected, got {w.size} floats")
+            wp = _ptr(w)
+        out = (_lib.FitResult * max(U, 1))()
+        _lib.check(self._lib.oww_verifier_fit(self._h, wp, int(bool(on_device)), _ptr(off), _ptr(lab), U, int(T), float(C), out))
+        return [dict(status=int(r.status), id=int(r.id), n_pos=int(r.n_pos), n_neg=int(r.n_neg), iterations=int(r.iterations),
+                     residual=float(r.residual)) for r in out[:U]]
+
+    def verifier_get(self, verifier_id: int, T: int) -> Tuple[np.ndarray, float]:
+        """Pool verifier `verifier_id` (of T feature rows) read back: (w [T*96] fp32, bias)."""
+        w = np.empty(int(T) * 96, dtype=np.float32)
+        b = C.c_float(0.0)
+        _lib.check(self._lib.oww_verifier_get(self._h, int(verifier_id), _ptr(w), int(w.size), C.byref(b)))
+        return w, float(b.value)
 
     def verifier_stats(self) -> Tuple[int, int]:
         """(pairs with a per-stream assignment, verifier evaluations of the last step)."""

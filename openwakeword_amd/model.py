@@ -29,6 +29,7 @@ from typing import Callable, DefaultDict, Dict, List, Optional, Sequence, Tuple,
 import numpy as np
 
 from . import weights as W
+from ._lib import FIT_STATUS
 from .engine import CHUNK, EMB_DIM, StreamEngine, check_audio_config, check_event_config
 
 # openwakeword/__init__.py:26-60 (names only; the files are release assets that are not in the checkout)
@@ -1019,6 +1020,53 @@ class BatchedModel:
         vid = self.engine.verifier_add(w, b)
         self._verifier_T[vid] = T
         return vid
+
+    def fit_verifiers(self, features, labels, C: float = 0.001) -> List[int]:
+        """custom_verifier_model.train_verifier_model (custom_verifier_model.py:95-113: flatten -> StandardScaler ->
+        LogisticRegression(C)) on the device, for one user or many in one call: `features` one [N, T, 96] array with `labels` [N] in
+        {0, 1}, or lists of them -> the pool ids of the fitted verifiers, ready for assign_verifiers.  What is fitted is the optimum
+        of scikit-learn's objective, N = 2 .. 1024 windows per user.  Raises ValueError with scikit-learn's wording
+        where it would raise (one class; NaN or infinity); any other failure names the status."""
+        if self.verifier_capacity <= 0:
+            raise ValueError("this BatchedModel has no verifier pool (verifier_capacity = 0)")
+        single = isinstance(features, np.ndarray) and features.ndim == 3
+        feats = [features] if single else list(features)
+        labs = [labels] if single else list(labels)
+        if len(feats) != len(labs) or not feats:
+            raise ValueError(f"{len(feats)} feature arrays and {len(labs)} label arrays")
+        feats = [np.ascontiguousarray(f, dtype=np.float32) for f in feats]
+        labs = [np.asarray(y).ravel() for y in labs]
+        T = feats[0].shape[1] if feats[0].ndim == 3 else 0
+        for f, y in zip(feats, labs):
+            if f.ndim != 3 or f.shape[1] != T or f.shape[2] != 96 or y.size != f.shape[0]:
+                raise ValueError(f"features must be [N, {T}, 96] with N labels each, got {f.shape} and {y.size} labels")
+            if y.size and not np.isin(y, (0, 1)).all():
+                raise ValueError("labels must be 0 or 1")
+        if not 1 <= T <= self.engine.feature_ring:
+            raise ValueError(f"the verifiers read T = {T} feature rows, the feature ring holds {self.engine.feature_ring}")
+        off = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int64)
+        res = self.engine.verifier_fit(np.concatenate(feats, axis=0), off, np.concatenate(labs).astype(np.uint8), T, C)
+        bad = [(u, r) for u, r in enumerate(res) if r["status"] != 0]
+        for r in res:
+            if r["status"] == 0:
+                self._verifier_T[r["id"]] = T
+        if bad:
+            u, r = bad[0]
+            name = FIT_STATUS[r["status"]]
+            if name == "ONE_CLASS":
+                cls = 1 if r["n_pos"] else 0
+                raise ValueError(f"This solver needs samples of at least 2 classes in the data, but the data contains only one class: {cls} (problem {u})")
+            if name == "NONFINITE":
+                raise ValueError(f"Input X contains NaN or infinity. (problem {u})")
+            raise ValueError(f"verifier fit of problem {u} failed: {name} (N = {int(off[u + 1] - off[u])}, {r['iterations']} iterations, residual {r['residual']:.3g}); "
+                             f"{len(res) - len(bad)} of {len(res)} problems were fitted")
+        return [r["id"] for r in res]
+
+    def get_verifier(self, verifier_id: int) -> Tuple[np.ndarray, float]:
+        """Pool verifier read back from the device: the folded (w [T*96] fp32, bias) pair add_verifier takes."""
+        if int(verifier_id) not in self._verifier_T:
+            raise ValueError(f"{verifier_id} is not a verifier of this BatchedModel's pool")
+        return self.engine.verifier_get(int(verifier_id), self._verifier_T[int(verifier_id)])
 
     def remove_verifier(self, verifier_id: int) -> None:
         """Drop a pool verifier; every stream assigned to it falls back to the default (the handle-wide set_custom_verifier)."""
