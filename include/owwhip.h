@@ -453,6 +453,46 @@ int  oww_verifier_fit(oww_ctx* h, const float* windows, int windows_on_device, c
                       int32_t U, int32_t T, float C, oww_fit_result* out);      /* custom_verifier_model.py:95-113 */
 int  oww_verifier_get(oww_ctx* h, int32_t id, float* w, int32_t n_w, float* bias);      /* custom_verifier_model.py:95-113: the fitted (coef / scale, folded intercept) */
 
+/* ---- training bank heads on the device (train.py:434-510) ---------------------------------------------------------------------------
+ * One step of train.Model.train_model for the network a bank head is (train.py:66-83 with n_blocks = 1, n_classes = 1: Linear ->
+ * LayerNorm -> ReLU -> Linear -> LayerNorm -> ReLU -> Linear -> Sigmoid), U independent problems side by side, each with its own
+ * parameters, Adam moments and counters, all drawing their batches from one pool of feature windows.  One session per handle.
+ * The flat parameter record of a problem, oww_train_param_count(T, hidden) floats, holds the bank head's own fields in its order
+ * and orientation (D = hidden):  w1 [96 T][D] | b1 [D] | ln1 gamma [D] | ln1 beta [D] | w2 [D][D] | b2 [D] | ln2 gamma [D] |
+ * ln2 beta [D] | w3 [D] | b3 [1]   (w[in][out], as a head dict's "net" carries them).
+ *   oww_train_begin     opens a session: U problems (1 .. 65535), T feature rows (1 .. the handle's feature ring), hidden a multiple
+ *                       of 16 in 16 .. 128, params [U][oww_train_param_count] the initial records.  Moments start at zero, the
+ *                       accumulation counters at (steps 1, samples 0), as train.py:443-444.
+ *   oww_train_set_pool  the window pool [P][T][96] fp32, host memory or (pool_on_device) device memory; copied.
+ *   oww_train_steps     K steps (1 .. OWW_TRAIN_MAX_STEPS) of n_batch slots (1 .. OWW_TRAIN_MAX_BATCH) for every problem, enqueued back
+ *                       to back on the handle's stream behind every submitted step; returns when they are done.  idx / y are
+ *                       [U][K][n_batch] (or [K][n_batch] with shared_tables, one table for all problems), host memory or
+ *                       (tables_on_device) device memory: idx a pool row or -1 for an empty slot, y in {0, 1}.  Step k of the call,
+ *                       per problem (train.py:447-510): forward; keep a sample iff (y = 0 and p >= 0.001) or (y = 1 and p < 0.999), m
+ *                       kept; m = 0: nothing happens.  Otherwise acc_samples += m, and while acc_samples < 128: acc_steps += 1, no
+ *                       update (the samples' gradients are dropped, as in the reference); else loss = (sum_kept w bce / m) /
+ *                       acc_steps with w = neg_weight[k] for y = 0 and 1 for y = 1, one torch.optim.Adam step (betas 0.9 / 0.999,
+ *                       eps 1e-8, bias correction by the count of optimizer steps taken) at learning rate lr[k], then acc_steps = 1,
+ *                       acc_samples = 0.  The gradient at the logit is binary_cross_entropy's and Sigmoid's in fp32:
+ *                       (p - y) / max(p (1 - p), 1e-12) * w * p (1 - p), zero where p rounds to exactly 0 or 1.
+ *                       out [U][K]: loss as history["loss"] has it (NaN where no optimizer step was taken) and m.
+ *   oww_train_get       the current record of problem u (waits for the handle's stream).
+ *   oww_train_end       closes the session and releases its memory.
+ * A problem's parameters have the same bits alone or among any other problems, with pool and tables in host or device memory, and
+ * in one call of K steps or several calls that add up to them.  Refusals leave the session as it was: no session, or a second
+ * oww_train_begin (OWW_ESTATE); U, hidden, T, n_batch or K outside their ranges, an index >= P or < -1, a label above 1, a
+ * non-finite or negative lr or neg_weight (OWW_EINVAL).  A handle that never trains launches exactly what it did. */
+#define OWW_TRAIN_MAX_BATCH 4096
+#define OWW_TRAIN_MAX_STEPS 4096
+typedef struct { float loss; int32_t m; } oww_train_record;
+int64_t oww_train_param_count(int32_t T, int32_t hidden);      /* 0 for a form oww_train_begin refuses */
+int  oww_train_begin(oww_ctx* h, int32_t U, int32_t T, int32_t hidden, const float* params);      /* train.py:66-83, 443-444 */
+int  oww_train_set_pool(oww_ctx* h, const float* pool, int pool_on_device, int64_t P);
+int  oww_train_steps(oww_ctx* h, int32_t K, int32_t n_batch, const int32_t* idx, const uint8_t* y, int shared_tables, int tables_on_device,
+                     const double* lr, const float* neg_weight, oww_train_record* out);      /* train.py:447-510 */
+int  oww_train_get(oww_ctx* h, int32_t u, float* params, int64_t n_params);
+int  oww_train_end(oww_ctx* h);
+
 /* ---- stream state records: take a live stream's state out, put it in, move it ---------------------------------------------------------
  * In the reference a stream's state IS its Model object (prediction_buffer model.py:198, reset model.py:226-230; the AudioFeatures
  * buffers utils.py:163-171): a caller keeps it, hands it to another thread or pickles it.  Here that state lives in HBM in layouts only

@@ -32,6 +32,15 @@ FIT_MAX_N = 1024         # OWW_FIT_MAX_N
 FIT_STATUS = ("OK", "ONE_CLASS", "BAD_N", "NONFINITE", "NOT_CONVERGED")      # OWW_FIT_*
 
 
+class TrainRecord(C.Structure):
+    """oww_train_record (include/owwhip.h)"""
+    _fields_ = [("loss", C.c_float), ("m", C.c_int32)]
+
+
+TRAIN_MAX_BATCH = 4096   # OWW_TRAIN_MAX_BATCH
+TRAIN_MAX_STEPS = 4096   # OWW_TRAIN_MAX_STEPS
+
+
 class IngestClass(C.Structure):
     """oww_ingest_class (include/owwhip.h)"""
     _fields_ = [("encoding", C.c_int32), ("p", C.c_int32), ("q", C.c_int32), ("n_taps", C.c_int32), ("taps", C.c_void_p)]
@@ -122,6 +131,12 @@ SYMBOLS = {
     "oww_verifier_stats": (C.c_int, [_P, _P]),
     "oww_verifier_fit": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_float, C.POINTER(FitResult)]),
     "oww_verifier_get": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.POINTER(C.c_float)]),
+    "oww_train_param_count": (C.c_int64, [C.c_int32, C.c_int32]),
+    "oww_train_begin": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "oww_train_set_pool": (C.c_int, [_P, _P, C.c_int, C.c_int64]),
+    "oww_train_steps": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "oww_train_get": (C.c_int, [_P, C.c_int32, _P, C.c_int64]),
+    "oww_train_end": (C.c_int, [_P]),
     "oww_state_info": (C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "oww_state_export": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),
     "oww_state_import": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),

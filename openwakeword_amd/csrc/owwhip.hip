@@ -37,6 +37,7 @@
 #include "owwhip_dense.h"
 #include "owwhip_dense_hits_host.h"
 #include "owwhip_fit.h"
+#include "owwhip_train.h"
 
 using namespace owk;
 using namespace owp;
@@ -363,6 +364,19 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
         DevBuf<owf::Problem> prob;
         DevBuf<owf::Tile> tiles;
     } fit;
+    // the head-training session (oww_train_*; owwhip_train.h): allocated by oww_train_begin, released by oww_train_end
+    struct TrainSession {
+        bool open = false;
+        int U = 0, T = 0, D = 0;
+        int64_t P = 0;
+        owt::Layout L{};
+        DevBuf<float> par, am, av, pool, dz1, part, tloss, nw;
+        DevBuf<double> lr;
+        DevBuf<owt::Counters> cnt;
+        DevBuf<int> idx, tcount;
+        DevBuf<unsigned char> y;
+        DevBuf<owt::StepRecord> rec;
+    } train;
     // stream state records (oww_state_*, oww_move_streams; owwhip_state.h): built by the first of those calls, nothing before it
     bool st_ready = false;
     std::vector<ows::FlatSection> st_flat;       // host copy of d_st_flat
@@ -3900,6 +3914,152 @@ int oww_verifier_get(oww_ctx* h, int32_t id, float* w, int32_t n_w, float* bias)
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(copy_sync(w, h->d_vpool_w + (size_t)id * h->vpool_stride, (size_t)n_w * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(copy_sync(bias, h->d_vpool_b + id, sizeof(float), hipMemcpyDeviceToHost));
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+// ---- training bank heads on the device (owwhip_train.h; host side: owwhip_train_host.h) ---------------------------------------------
+int64_t oww_train_param_count(int32_t T, int32_t hidden) {
+    if (T < 1 || hidden < 16 || hidden > 128 || hidden % 16) return 0;
+    return owt::layout(T, hidden).n;
+}
+
+extern "C++" {
+template <int NT>
+static int train_launch_step(oww_ctx* h, const owtk::TrainParams& p, const owt::Plan& pl, int U) {
+    const size_t lds = (size_t)owtk::fwd_lds_floats(NT) * sizeof(float);
+    hipLaunchKernelGGL(owtk::train_fwd_kernel<NT>, dim3(pl.n_tiles, U), dim3(256), lds, h->stream, p);
+    hipLaunchKernelGGL(owtk::train_w1_kernel<NT>, dim3(pl.w1_groups, U), dim3(256), 0, h->stream, p);
+    hipLaunchKernelGGL(owtk::train_small_kernel, dim3(U), dim3(256), 0, h->stream, p);
+    return 0;
+}
+template <int NT>
+static hipError_t train_set_lds() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(owtk::train_fwd_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               owtk::fwd_lds_floats(NT) * (int)sizeof(float));
+}
+}  // extern "C++"
+#define OWW_TRAIN_NT(nt, CALL)                                                                                                        \
+    switch (nt) {                                                                                                                     \
+        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;                               \
+        case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break;                              \
+    }
+
+int oww_train_begin(oww_ctx* h, int32_t U, int32_t T, int32_t hidden, const float* params) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    if (int rc = owt::check_begin(h->committed, h->train.open, U, T, hidden, h->TR, params)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    auto& S = h->train;
+    const owt::Layout L = owt::layout(T, hidden);
+    const size_t n = (size_t)U * L.stride;
+    if (grow(h, S.par, n) != hipSuccess || grow(h, S.am, n) != hipSuccess || grow(h, S.av, n) != hipSuccess || grow(h, S.cnt, (size_t)U) != hipSuccess)
+        return fail(OWW_ENOMEM, "oww_train_begin: out of device memory for %d problems of %lld parameters", U, L.n);
+#define OWW_TRAIN_LDS(NT) HIPCHK(train_set_lds<NT>())
+    OWW_TRAIN_NT(hidden / 16, OWW_TRAIN_LDS)
+#undef OWW_TRAIN_LDS
+    std::vector<float> stage(n, 0.f);
+    for (int u = 0; u < U; ++u) memcpy(stage.data() + (size_t)u * L.stride, params + (size_t)u * L.n, (size_t)L.n * sizeof(float));
+    const std::vector<owt::Counters> cnt((size_t)U, owt::Counters{1, 0, 0, 0});
+    HIPCHK(copy_async(S.par, stage.data(), n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(copy_async(S.cnt, cnt.data(), cnt.size() * sizeof(owt::Counters), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(S.am, 0, n * sizeof(float), h->stream));
+    HIPCHK(hipMemsetAsync(S.av, 0, n * sizeof(float), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    S.U = U; S.T = T; S.D = hidden; S.L = L; S.P = 0; S.open = true;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_set_pool(oww_ctx* h, const float* pool, int pool_on_device, int64_t P) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (int rc = owt::check_pool(S.open, pool, P, S.T)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t n = (size_t)P * S.L.F;
+    if (grow(h, S.pool, n) != hipSuccess) { S.P = 0; return fail(OWW_ENOMEM, "oww_train_set_pool: out of device memory for %lld windows", (long long)P); }
+    HIPCHK(copy_async(S.pool, pool, n * sizeof(float), pool_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    S.P = P;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_steps(oww_ctx* h, int32_t K, int32_t n_batch, const int32_t* idx, const uint8_t* y, int shared_tables, int tables_on_device,
+                    const double* lr, const float* neg_weight, oww_train_record* out) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (!S.open) return fail(OWW_ESTATE, "oww_train_steps: no training session on this handle");
+    if (K < 1 || K > owt::kMaxSteps || n_batch < 1 || n_batch > owt::kMaxBatch || !idx || !y)      // (the sizes below rest on these)
+        return owt::check_steps(true, S.P, S.U, K, n_batch, idx, y, shared_tables, lr, neg_weight, out);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t total = (size_t)(shared_tables ? 1 : S.U) * K * n_batch;
+    std::vector<int32_t> idx_h;
+    std::vector<uint8_t> y_h;
+    if (tables_on_device) {                      // checked on the host like host tables: a copy back, behind whatever wrote them on this stream
+        idx_h.resize(total); y_h.resize(total);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(copy_sync(idx_h.data(), idx, total * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(copy_sync(y_h.data(), y, total, hipMemcpyDeviceToHost));
+    }
+    const int32_t* idx_c = tables_on_device ? idx_h.data() : idx;
+    const uint8_t* y_c = tables_on_device ? y_h.data() : y;
+    if (int rc = owt::check_steps(true, S.P, S.U, K, n_batch, idx_c, y_c, shared_tables, lr, neg_weight, out)) return rc;
+    const owt::Plan pl = owt::plan(S.U, S.T, S.D, n_batch);
+    const size_t nrec = (size_t)S.U * K;
+    if (grow(h, S.idx, total) != hipSuccess || grow(h, S.y, total) != hipSuccess || grow(h, S.lr, (size_t)K) != hipSuccess || grow(h, S.nw, (size_t)K) != hipSuccess ||
+        grow(h, S.dz1, (size_t)pl.dz1) != hipSuccess || grow(h, S.part, (size_t)pl.part) != hipSuccess || grow(h, S.tcount, (size_t)pl.tile_words) != hipSuccess ||
+        grow(h, S.tloss, (size_t)pl.tile_words) != hipSuccess || grow(h, S.rec, nrec) != hipSuccess)
+        return fail(OWW_ENOMEM, "oww_train_steps: out of device memory for %d problems x %d rows", S.U, pl.n_pad);
+    HIPCHK(copy_async(S.idx, idx_c, total * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(copy_async(S.y, y_c, total, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(copy_async(S.lr, lr, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(copy_async(S.nw, neg_weight, (size_t)K * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    owtk::TrainParams p{};
+    p.par = S.par; p.am = S.am; p.av = S.av; p.cnt = S.cnt; p.pool = S.pool; p.idx = S.idx; p.y = S.y; p.lr = S.lr; p.nw = S.nw;
+    p.dz1 = S.dz1; p.part = S.part; p.tcount = S.tcount; p.tloss = S.tloss; p.rec = S.rec;
+    p.tab_stride = shared_tables ? 0 : (long long)K * n_batch;
+    p.stride = S.L.stride; p.small = S.L.small;
+    p.P = (int)S.P; p.F = (int)S.L.F; p.D = S.D; p.K = K; p.n_batch = n_batch; p.n_tiles = pl.n_tiles; p.n_pad = pl.n_pad;
+    for (int k = 0; k < K; ++k) {                // the K steps back to back on the handle's stream: no host round trip between them
+        p.k = k;
+#define OWW_TRAIN_STEP(NT) train_launch_step<NT>(h, p, pl, S.U)
+        OWW_TRAIN_NT(S.D / 16, OWW_TRAIN_STEP)
+#undef OWW_TRAIN_STEP
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<owt::StepRecord> recs(nrec);
+    HIPCHK(copy_async(recs.data(), S.rec, nrec * sizeof(owt::StepRecord), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < nrec; ++i) { out[i].loss = recs[i].loss; out[i].m = recs[i].m; }
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_get(oww_ctx* h, int32_t u, float* params, int64_t n_params) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (!S.open) return fail(OWW_ESTATE, "oww_train_get: no training session on this handle");
+    if (u < 0 || u >= S.U) return fail(OWW_EINVAL, "oww_train_get: problem %d of %d", u, S.U);
+    if (!params || n_params != S.L.n) return fail(OWW_EINVAL, "oww_train_get: room for %lld floats, a record has %lld", (long long)n_params, S.L.n);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(copy_sync(params, S.par + (size_t)u * S.L.stride, (size_t)S.L.n * sizeof(float), hipMemcpyDeviceToHost));
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_end(oww_ctx* h) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (!S.open) return fail(OWW_ESTATE, "oww_train_end: no training session on this handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    S = oww_ctx::TrainSession{};
     return OWW_OK;
     OWW_GUARD_END
 }

@@ -739,6 +739,66 @@ class StreamEngine:
         _lib.check(self._lib.oww_verifier_get(self._h, int(verifier_id), _ptr(w), int(w.size), C.byref(b)))
         return w, float(b.value)
 
+    # ---- training bank heads (include/owwhip.h: oww_train_*) ----
+    def train_param_count(self, T: int, hidden: int) -> int:
+        return int(self._lib.oww_train_param_count(int(T), int(hidden)))
+
+    def train_begin(self, params: np.ndarray, T: int, hidden: int) -> None:
+        """oww_train_begin: params [U, oww_train_param_count(T, hidden)] fp32, the initial flat records."""
+        p = np.ascontiguousarray(params, dtype=np.float32)
+        n = self.train_param_count(T, hidden)
+        if p.ndim != 2 or (n and p.shape[1] != n):
+            raise ValueError(f"params must be [U, {n}] for T = {T}, hidden = {hidden}, got {p.shape}")
+        _lib.check(self._lib.oww_train_begin(self._h, p.shape[0], int(T), int(hidden), _ptr(p)))
+        self._train_U = int(p.shape[0])              # the session's problems: what train_steps sizes its tables and records by
+
+    def train_set_pool(self, pool, n_windows: Optional[int] = None, on_device: bool = False) -> None:
+        """oww_train_set_pool: `pool` [P, T, 96] fp32 on the host, or a device address of such a buffer of n_windows windows."""
+        if on_device:
+            _lib.check(self._lib.oww_train_set_pool(self._h, C_void(pool), 1, int(n_windows)))
+            return
+        w = np.ascontiguousarray(pool, dtype=np.float32)
+        _lib.check(self._lib.oww_train_set_pool(self._h, _ptr(w), 0, int(w.shape[0]) if n_windows is None else int(n_windows)))
+
+    def train_steps(self, n_problems: int, idx, y, lr, neg_weight, on_device: bool = False, shape=None) -> Tuple[np.ndarray, np.ndarray]:
+        """oww_train_steps: idx / y [U, K, n] (or [K, n]: one table for all problems) on the host, or device addresses with
+        on_device and shape = their shape; lr, neg_weight [K] -> (loss [U, K] fp32, NaN where no optimizer step was taken; m [U, K]).
+        n_problems must be the open session's U: the library reads U tables and writes U x K records."""
+        U = getattr(self, "_train_U", None)
+        if U is None:
+            raise ValueError("train_steps: no training session on this engine (train_begin first)")
+        if int(n_problems) != U:
+            raise ValueError(f"train_steps: n_problems = {n_problems}, the open session trains {U} problems")
+        if on_device:
+            shp = tuple(int(s) for s in shape)
+            ip, yp = C_void(idx), C_void(y)
+        else:
+            i = np.ascontiguousarray(idx, dtype=np.int32)
+            yy = np.ascontiguousarray(y, dtype=np.uint8)
+            if i.shape != yy.shape:
+                raise ValueError(f"idx {i.shape} and y {yy.shape} differ in shape")
+            shp, ip, yp = i.shape, _ptr(i), _ptr(yy)
+        if len(shp) not in (2, 3) or (len(shp) == 3 and shp[0] != int(n_problems)):
+            raise ValueError(f"tables must be [K, n] or [{n_problems}, K, n], got {shp}")
+        K, n = shp[-2], shp[-1]
+        l = np.ascontiguousarray(lr, dtype=np.float64).ravel()
+        w = np.ascontiguousarray(neg_weight, dtype=np.float32).ravel()
+        if l.size != K or w.size != K:
+            raise ValueError(f"lr and neg_weight must have one entry per step ({K}), got {l.size} and {w.size}")
+        out = (_lib.TrainRecord * (int(n_problems) * max(K, 1)))()
+        _lib.check(self._lib.oww_train_steps(self._h, K, n, ip, yp, int(len(shp) == 2), int(bool(on_device)), _ptr(l), _ptr(w), out))
+        rec = np.frombuffer(out, dtype=np.dtype([("loss", np.float32), ("m", np.int32)])).reshape(int(n_problems), K)
+        return rec["loss"].copy(), rec["m"].copy()
+
+    def train_get(self, u: int, n_params: int) -> np.ndarray:
+        p = np.empty(int(n_params), dtype=np.float32)
+        _lib.check(self._lib.oww_train_get(self._h, int(u), _ptr(p), int(p.size)))
+        return p
+
+    def train_end(self) -> None:
+        _lib.check(self._lib.oww_train_end(self._h))
+        self._train_U = None
+
     def verifier_stats(self) -> Tuple[int, int]:
         """(pairs with a per-stream assignment, verifier evaluations of the last step)."""
         out = np.zeros(2, dtype=np.int64)

@@ -792,6 +792,13 @@ class BatchedModel:
         check_bank_head(head, self.engine.feature_ring)
         return self.engine.bank_add(head)
 
+    def head_trainer(self, T: int, hidden: int, n_problems: int, init: Optional[Sequence[dict]] = None, seed: int = 0):
+        """A training session for `n_problems` bank heads of T feature rows and `hidden` units on this model's device (train.HeadTrainer:
+        set_pool, steps(idx, y, lr, neg_weight), history, heads() -> dicts for bank_add, close()): the step of train.py:434-510, many
+        heads per call.  `init`: one head dict per problem (default: train.init_head(T, hidden, seed + u)).  One session per model."""
+        from .train import HeadTrainer
+        return HeadTrainer(self.engine, T, hidden, n_problems, init=init, seed=seed)
+
     def bank_remove(self, bank_id: int) -> None:
         """Drop a bank head; the slots subscribed to it become empty (score 0)."""
         self.engine.bank_remove(bank_id)
