@@ -493,6 +493,46 @@ int  oww_train_steps(oww_ctx* h, int32_t K, int32_t n_batch, const int32_t* idx,
 int  oww_train_get(oww_ctx* h, int32_t u, float* params, int64_t n_params);
 int  oww_train_end(oww_ctx* h);
 
+/* ---- validating, checkpointing and merging the heads of a session (train.py:261-366) --------------------------------------------------
+ * What Model.auto_train does around the step, for all problems of the open session at once, in the step's exact fp32 arithmetic; the
+ * policy (when to validate, which checkpoint to keep, which to merge) stays with the caller (openwakeword_amd/train.py: auto_train).
+ *   oww_train_new_sequence   a new train_model call on the same optimizer: for every problem acc_steps = 1, acc_samples = 0
+ *                            (train.py:443-444); moments, the optimizer's step count and the parameters stay (train.py:135).
+ *   oww_train_set_eval_pool  a second window pool [P][T][96] fp32 for validation, independent of the training pool; copied.
+ *                            A pool larger than any before is allocated before the old one is released, so a refusal
+ *                            (OWW_ENOMEM) leaves the old pool in use.
+ *   oww_train_eval           the forward pass of train.py:66-83 for every problem over n slots (1 .. OWW_TRAIN_EVAL_MAX_ROWS) of the
+ *                            eval pool, in the operation order of the training step's forward.  idx / y are [U][n] (or [n] with
+ *                            shared_tables), host or (tables_on_device) device memory, idx an eval-pool row or -1 for an empty slot,
+ *                            y in {0, 1}.  source = -1 reads the live parameters, 0 .. C - 1 a checkpoint slot.  counts [U]: n_pos,
+ *                            n_neg, pos_gt (y = 1 and p > 0.5), neg_gt (y = 0 and p > 0.5), neg_ge (y = 0 and p >= 0.5), from which
+ *                            the reference's metrics follow: self.fp (train.py:100, y - p <= -0.5) = neg_ge; binary Recall = pos_gt /
+ *                            n_pos; binary Accuracy = (pos_gt + n_neg - neg_gt) / (n_pos + n_neg) (train.py:101-102, 544-553).
+ *                            scores, if not null: [U][n] fp32 on the host, NaN in empty slots.  Runs behind every submitted step.
+ *   oww_train_checkpoints    reserves C parameter slots (1 .. 65535) per problem, zero-filled; a second call replaces them.  Nothing
+ *                            is allocated before this call; oww_train_end releases them.
+ *   oww_train_snapshot       slot [U]: problem u's live parameters are copied to its slot slot[u] (-1: none), in stream order behind
+ *                            the steps submitted before it (train.py:561, copy.deepcopy(self.model)).
+ *   oww_train_average        sel [U][C] uint8.  A problem with at least one selected slot: slot dst receives average_models' result
+ *                            (train.py:198-223) in its arithmetic: fp32, 0 * (the first selected slot), += every selected slot in slot
+ *                            order, one division by their count.  A problem with none: dst receives its live parameters
+ *                            (train.py:340-343).  dst may be among the selected.
+ *   oww_train_get_slot       oww_train_get for checkpoint slot `slot` of problem u.
+ * Counts are integers (integer atomics); a problem's scores and counts do not depend on what else is in the call, on where the
+ * tables live, or on how a table is cut into calls.  Refusals leave the session as it was: no session, no eval pool or no slots
+ * (OWW_ESTATE); a slot, source or n out of range, an index >= P or < -1, a label above 1 (OWW_EINVAL); slots whose size overflows 64
+ * bits (OWW_EINVAL) or that cannot be allocated (OWW_ENOMEM).  A session that calls none of these allocates and launches what it did. */
+#define OWW_TRAIN_EVAL_MAX_ROWS 1048576
+typedef struct { int32_t n_pos, n_neg, pos_gt, neg_gt, neg_ge; } oww_train_counts;
+int  oww_train_new_sequence(oww_ctx* h);      /* train.py:443-444 against train.py:135 */
+int  oww_train_set_eval_pool(oww_ctx* h, const float* pool, int pool_on_device, int64_t P);
+int  oww_train_eval(oww_ctx* h, int32_t source, int32_t n, const int32_t* idx, const uint8_t* y, int shared_tables, int tables_on_device,
+                    float* scores, oww_train_counts* counts);      /* train.py:512-553 */
+int  oww_train_checkpoints(oww_ctx* h, int32_t C);
+int  oww_train_snapshot(oww_ctx* h, const int32_t* slot);      /* train.py:557-567 */
+int  oww_train_average(oww_ctx* h, const uint8_t* sel, int32_t dst);      /* train.py:198-223, 326-343 */
+int  oww_train_get_slot(oww_ctx* h, int32_t u, int32_t slot, float* params, int64_t n_params);
+
 /* ---- stream state records: take a live stream's state out, put it in, move it ---------------------------------------------------------
  * In the reference a stream's state IS its Model object (prediction_buffer model.py:198, reset model.py:226-230; the AudioFeatures
  * buffers utils.py:163-171): a caller keeps it, hands it to another thread or pickles it.  Here that state lives in HBM in layouts only

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "owwhip.hip")
 DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("owwhip_layout.h", "owwhip_pack.h", "owwhip_ingest.h", "owwhip_mem.h", "owwhip_kernels.h", "owwhip_rr.h", "owwhip_hx.h", "owwhip_vad.h",
-                                                           "owwhip_fused.h", "owwhip_state.h", "owwhip_events.h", "owwhip_audio.h", "owwhip_audio_host.h", "owwhip_dense.h", "owwhip_dense_host.h", "owwhip_dense_bank_host.h", "owwhip_dense_hits_host.h", "owwhip_fit.h", "owwhip_fit_host.h", "owwhip_train.h", "owwhip_train_host.h",
+                                                           "owwhip_fused.h", "owwhip_state.h", "owwhip_events.h", "owwhip_audio.h", "owwhip_audio_host.h", "owwhip_dense.h", "owwhip_dense_host.h", "owwhip_dense_bank_host.h", "owwhip_dense_hits_host.h", "owwhip_fit.h", "owwhip_fit_host.h", "owwhip_train.h", "owwhip_train_host.h", "owwhip_autotrain.h", "owwhip_autotrain_host.h",
                                                            "owwhip_masked_host.h", "owwhip_bank_host.h", "owwhip_verifier_host.h", "owwhip_state_host.h", "owwhip_postproc.h")] + \
        [os.path.join(ROOT, "include", "owwhip.h")]
 LIB = os.path.join(HERE, "libowwhip.so")

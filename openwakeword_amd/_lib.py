@@ -39,6 +39,7 @@ class TrainRecord(C.Structure):
 
 TRAIN_MAX_BATCH = 4096   # OWW_TRAIN_MAX_BATCH
 TRAIN_MAX_STEPS = 4096   # OWW_TRAIN_MAX_STEPS
+TRAIN_EVAL_MAX_ROWS = 1 << 20   # OWW_TRAIN_EVAL_MAX_ROWS
 
 
 class IngestClass(C.Structure):
@@ -137,6 +138,13 @@ SYMBOLS = {
     "oww_train_steps": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "oww_train_get": (C.c_int, [_P, C.c_int32, _P, C.c_int64]),
     "oww_train_end": (C.c_int, [_P]),
+    "oww_train_new_sequence": (C.c_int, [_P]),
+    "oww_train_set_eval_pool": (C.c_int, [_P, _P, C.c_int, C.c_int64]),
+    "oww_train_eval": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "oww_train_checkpoints": (C.c_int, [_P, C.c_int32]),
+    "oww_train_snapshot": (C.c_int, [_P, _P]),
+    "oww_train_average": (C.c_int, [_P, _P, C.c_int32]),
+    "oww_train_get_slot": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64]),
     "oww_state_info": (C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "oww_state_export": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),
     "oww_state_import": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int]),

@@ -38,6 +38,7 @@
 #include "owwhip_dense_hits_host.h"
 #include "owwhip_fit.h"
 #include "owwhip_train.h"
+#include "owwhip_autotrain.h"
 
 using namespace owk;
 using namespace owp;
@@ -376,6 +377,12 @@ struct oww_ctx : PackIn {                 // (PackIn: the weights as loaded, the
         DevBuf<int> idx, tcount;
         DevBuf<unsigned char> y;
         DevBuf<owt::StepRecord> rec;
+        // validation, checkpoints and merge (oww_train_eval ..; owwhip_autotrain.h): nothing of this before the entries are called
+        int64_t EP = 0;
+        int C = 0;
+        DevBuf<float> epool, ckpt, escores;
+        DevBuf<int> eidx, ecounts, slot;
+        DevBuf<unsigned char> ey, sel;
     } train;
     // stream state records (oww_state_*, oww_move_streams; owwhip_state.h): built by the first of those calls, nothing before it
     bool st_ready = false;
@@ -4060,6 +4067,173 @@ int oww_train_end(oww_ctx* h) {
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipStreamSynchronize(h->stream));
     S = oww_ctx::TrainSession{};
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+// ---- validating, checkpointing and merging the heads of a session (owwhip_autotrain.h; host side: owwhip_autotrain_host.h) ------------
+extern "C++" {
+template <int NT>
+static int train_launch_eval(oww_ctx* h, const owak::EvalParams& p, int n_tiles, int U) {
+    const size_t lds = (size_t)owak::eval_lds_floats(NT) * sizeof(float);
+    hipLaunchKernelGGL(owak::train_eval_kernel<NT>, dim3(U, n_tiles), dim3(256), lds, h->stream, p);
+    return 0;
+}
+}  // extern "C++"
+
+int oww_train_new_sequence(oww_ctx* h) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (int rc = owa::check_new_sequence(S.open)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    // the counters of every problem, behind the steps that wrote them: the optimizer's step count is read back and kept
+    std::vector<owt::Counters> cnt((size_t)S.U);
+    HIPCHK(copy_async(cnt.data(), S.cnt, cnt.size() * sizeof(owt::Counters), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (auto& c : cnt) { c.acc_steps = 1; c.acc_samples = 0; }
+    HIPCHK(copy_async(S.cnt, cnt.data(), cnt.size() * sizeof(owt::Counters), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_set_eval_pool(oww_ctx* h, const float* pool, int pool_on_device, int64_t P) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (int rc = owa::check_eval_pool(S.open, pool, P, S.T)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t n = (size_t)P * S.L.F;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (n > S.epool.capacity()) {                // a larger pool: the old one stays until the new one exists, so a refusal leaves it
+        DevBuf<float> fresh;
+        if (fresh.alloc(n) != 0) {
+            (void)hipGetLastError();
+            return fail(OWW_ENOMEM, "oww_train_set_eval_pool: out of device memory for %lld windows", (long long)P);
+        }
+        S.epool = std::move(fresh);
+        S.EP = 0;                                // (the old windows are gone from here on; the copy below fills the new ones)
+    }
+    HIPCHK(copy_async(S.epool, pool, n * sizeof(float), pool_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    S.EP = P;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_eval(oww_ctx* h, int32_t source, int32_t n, const int32_t* idx, const uint8_t* y, int shared_tables, int tables_on_device,
+                   float* scores, oww_train_counts* counts) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (int rc = owa::check_eval_head(S.open, S.EP, S.C, source, n, idx, y, counts)) return rc;      // (the sizes below rest on these)
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const owa::EvalPlan pl = owa::eval_plan(S.U, n, shared_tables, scores != nullptr);
+    const size_t total = (size_t)pl.table;
+    std::vector<int32_t> idx_h;
+    std::vector<uint8_t> y_h;
+    if (tables_on_device) {                      // checked on the host like host tables, as oww_train_steps does
+        idx_h.resize(total); y_h.resize(total);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(copy_sync(idx_h.data(), idx, total * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(copy_sync(y_h.data(), y, total, hipMemcpyDeviceToHost));
+    }
+    const int32_t* idx_c = tables_on_device ? idx_h.data() : idx;
+    const uint8_t* y_c = tables_on_device ? y_h.data() : y;
+    if (int rc = owa::check_eval(true, S.EP, S.C, S.U, source, n, idx_c, y_c, shared_tables, counts)) return rc;
+    const size_t ncnt = (size_t)S.U * owa::kCounts;
+    if (grow(h, S.eidx, total) != hipSuccess || grow(h, S.ey, total) != hipSuccess || grow(h, S.ecounts, ncnt) != hipSuccess ||
+        (scores && grow(h, S.escores, (size_t)pl.scores) != hipSuccess))
+        return fail(OWW_ENOMEM, "oww_train_eval: out of device memory for %d problems x %d slots", S.U, n);
+    HIPCHK(copy_async(S.eidx, idx_c, total * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(copy_async(S.ey, y_c, total, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(S.ecounts, 0, ncnt * sizeof(int), h->stream));
+    owak::EvalParams p{};
+    p.par = source < 0 ? (const float*)S.par : (const float*)S.ckpt + (size_t)source * S.U * S.L.stride;
+    p.pool = S.epool; p.idx = S.eidx; p.y = S.ey; p.scores = scores ? (float*)S.escores : nullptr; p.counts = S.ecounts;
+    p.tab_stride = shared_tables ? 0 : (long long)n;
+    p.stride = S.L.stride; p.P = (int)S.EP; p.F = (int)S.L.F; p.n = n;
+#define OWW_TRAIN_EVAL(NT) train_launch_eval<NT>(h, p, pl.n_tiles, S.U)
+    OWW_TRAIN_NT(S.D / 16, OWW_TRAIN_EVAL)
+#undef OWW_TRAIN_EVAL
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> cnt_h(ncnt);
+    HIPCHK(copy_async(cnt_h.data(), S.ecounts, ncnt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (scores) HIPCHK(copy_async(scores, S.escores, (size_t)pl.scores * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int u = 0; u < S.U; ++u) {
+        const int32_t* c = cnt_h.data() + (size_t)u * owa::kCounts;
+        counts[u] = oww_train_counts{c[0], c[1], c[2], c[3], c[4]};
+    }
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_checkpoints(oww_ctx* h, int32_t C) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    long long floats = 0;
+    if (int rc = owa::check_checkpoints(S.open, C, S.U, S.L.stride, &floats)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    DevBuf<float> slots;                         // the old slots stay until the new ones exist
+    if (slots.alloc((size_t)floats) != 0) {
+        (void)hipGetLastError();
+        return fail(OWW_ENOMEM, "oww_train_checkpoints: out of device memory for %d slots x %d problems of %lld parameters", C, S.U, S.L.n);
+    }
+    HIPCHK(hipMemsetAsync(slots, 0, (size_t)floats * sizeof(float), h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    S.ckpt = std::move(slots);
+    S.C = C;
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_snapshot(oww_ctx* h, const int32_t* slot) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (int rc = owa::check_snapshot(S.open, S.C, S.U, slot)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (grow(h, S.slot, (size_t)S.U) != hipSuccess) return fail(OWW_ENOMEM, "oww_train_snapshot: out of device memory for %d slot numbers", S.U);
+    HIPCHK(copy_async(S.slot, slot, (size_t)S.U * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    const unsigned groups = (unsigned)((S.L.stride / 4 + 255) / 256);
+    hipLaunchKernelGGL(owak::train_snapshot_kernel, dim3(groups, S.U), dim3(256), 0, h->stream, (const float*)S.par, (float*)S.ckpt, (const int*)S.slot,
+                       S.L.stride, S.U);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));     // `slot` is the caller's memory
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_average(oww_ctx* h, const uint8_t* sel, int32_t dst) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (int rc = owa::check_average(S.open, S.C, sel, dst)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t n = (size_t)S.U * S.C;
+    if (grow(h, S.sel, n) != hipSuccess) return fail(OWW_ENOMEM, "oww_train_average: out of device memory for %d x %d selections", S.U, S.C);
+    HIPCHK(copy_async(S.sel, sel, n, hipMemcpyHostToDevice, h->stream));
+    const unsigned groups = (unsigned)((S.L.stride / 4 + 255) / 256);
+    hipLaunchKernelGGL(owak::train_average_kernel, dim3(groups, S.U), dim3(256), 0, h->stream, (const float*)S.par, (float*)S.ckpt,
+                       (const unsigned char*)S.sel, S.L.stride, S.U, S.C, dst);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return OWW_OK;
+    OWW_GUARD_END
+}
+
+int oww_train_get_slot(oww_ctx* h, int32_t u, int32_t slot, float* params, int64_t n_params) {
+    OWW_GUARD_BEGIN
+    if (!h) return fail(OWW_EINVAL, "null handle");
+    auto& S = h->train;
+    if (int rc = owa::check_get_slot(S.open, S.C, S.U, u, slot, params, n_params, S.L.n)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(copy_sync(params, S.ckpt + ((size_t)slot * S.U + u) * S.L.stride, (size_t)S.L.n * sizeof(float), hipMemcpyDeviceToHost));
     return OWW_OK;
     OWW_GUARD_END
 }

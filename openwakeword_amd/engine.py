@@ -798,6 +798,73 @@ class StreamEngine:
     def train_end(self) -> None:
         _lib.check(self._lib.oww_train_end(self._h))
         self._train_U = None
+        self._train_C = 0
+
+    # ---- validation, checkpoints and merge of a session's heads (include/owwhip.h: oww_train_new_sequence ..) ----
+    def _train_open_U(self, what: str) -> int:
+        U = getattr(self, "_train_U", None)
+        if U is None:
+            raise ValueError(f"{what}: no training session on this engine (train_begin first)")
+        return U
+
+    def train_new_sequence(self) -> None:
+        _lib.check(self._lib.oww_train_new_sequence(self._h))
+
+    def train_set_eval_pool(self, pool, n_windows: Optional[int] = None, on_device: bool = False) -> None:
+        """oww_train_set_eval_pool: `pool` [P, T, 96] fp32 on the host, or a device address of such a buffer of n_windows windows."""
+        if on_device:
+            _lib.check(self._lib.oww_train_set_eval_pool(self._h, C_void(pool), 1, int(n_windows)))
+            return
+        w = np.ascontiguousarray(pool, dtype=np.float32)
+        _lib.check(self._lib.oww_train_set_eval_pool(self._h, _ptr(w), 0, int(w.shape[0]) if n_windows is None else int(n_windows)))
+
+    def train_eval(self, idx, y, source: int = -1, scores: bool = False, on_device: bool = False, shape=None):
+        """oww_train_eval: idx / y [U, n] (or [n]: one table for all problems) on the host, or device addresses with on_device and
+        shape = their shape -> (counts [U, 5] int32: n_pos, n_neg, pos_gt, neg_gt, neg_ge; scores [U, n] fp32 or None)."""
+        U = self._train_open_U("train_eval")
+        if on_device:
+            shp = tuple(int(s) for s in shape)
+            ip, yp = C_void(idx), C_void(y)
+        else:
+            i = np.ascontiguousarray(idx, dtype=np.int32)
+            yy = np.ascontiguousarray(y, dtype=np.uint8)
+            if i.shape != yy.shape:
+                raise ValueError(f"idx {i.shape} and y {yy.shape} differ in shape")
+            shp, ip, yp = i.shape, _ptr(i), _ptr(yy)
+        if len(shp) not in (1, 2) or (len(shp) == 2 and shp[0] != U):
+            raise ValueError(f"tables must be [n] or [{U}, n], got {shp}")
+        n = shp[-1]
+        counts = np.zeros((U, 5), dtype=np.int32)
+        sc = np.empty((U, max(n, 1)), dtype=np.float32) if scores else None
+        _lib.check(self._lib.oww_train_eval(self._h, int(source), n, ip, yp, int(len(shp) == 1), int(bool(on_device)),
+                                            _ptr(sc) if scores else None, _ptr(counts)))
+        return counts, sc
+
+    def train_checkpoints(self, C_: int) -> None:
+        _lib.check(self._lib.oww_train_checkpoints(self._h, int(C_)))
+        self._train_C = int(C_)
+
+    def train_snapshot(self, slots) -> None:
+        """oww_train_snapshot: slots [U] int32, -1 = none."""
+        U = self._train_open_U("train_snapshot")
+        s = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        if s.size != U:
+            raise ValueError(f"train_snapshot: {s.size} slot numbers for {U} problems")
+        _lib.check(self._lib.oww_train_snapshot(self._h, _ptr(s)))
+
+    def train_average(self, sel, dst: int) -> None:
+        """oww_train_average: sel [U, C] (nonzero = selected), dst the slot that receives the result."""
+        U = self._train_open_U("train_average")
+        Cn = getattr(self, "_train_C", 0)
+        s = np.ascontiguousarray(np.asarray(sel) != 0, dtype=np.uint8)
+        if Cn and s.shape != (U, Cn):
+            raise ValueError(f"train_average: sel must be [{U}, {Cn}], got {s.shape}")
+        _lib.check(self._lib.oww_train_average(self._h, _ptr(s), int(dst)))
+
+    def train_get_slot(self, u: int, slot: int, n_params: int) -> np.ndarray:
+        p = np.empty(int(n_params), dtype=np.float32)
+        _lib.check(self._lib.oww_train_get_slot(self._h, int(u), int(slot), _ptr(p), int(p.size)))
+        return p
 
     def verifier_stats(self) -> Tuple[int, int]:
         """(pairs with a per-stream assignment, verifier evaluations of the last step)."""

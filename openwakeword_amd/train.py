@@ -1,8 +1,10 @@
 """Training bank heads on the device: the step of the reference's train.Model.train_model (train.py:434-510) for the network a bank
 head is (train.py:66-83 with n_blocks = 1, n_classes = 1), many heads per call (include/owwhip.h: oww_train_*).
-What stays on the host is policy: auto_train's three sequences, checkpoint selection and averaging (train.py:198-366) sit on top
-of the step, and validate_bank already gives their false-accepts-per-hour gate.  Batches are index tables into one shared window
-pool, drawn here with a seeded generator, so a run can be replayed against the reference on the same batches."""
+Model.auto_train (train.py:261-366) sits on top of it here: its validation pass (train.py:512-553), its checkpoints and its merge
+(average_models, train.py:198-223) run on the device in the step's arithmetic (oww_train_eval, oww_train_snapshot,
+oww_train_average), and what stays on the host is policy: when to validate, which checkpoint to keep, which to
+merge.  Batches are index tables into one shared window pool, drawn here with a seeded generator, so a run can be replayed against
+the reference on the same batches."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -81,6 +83,24 @@ def init_head(T: int, hidden: int, seed: int) -> dict:
             "net": {"w1": w1, "b1": b1, "ln1": (one.copy(), zero.copy()), "w2": w2, "b2": b2, "ln2": (one.copy(), zero.copy()), "w3": w3, "b3": b3}}
 
 
+COUNT_FIELDS = ("n_pos", "n_neg", "pos_gt", "neg_gt", "neg_ge")      # oww_train_counts (include/owwhip.h)
+
+
+def metrics_from_counts(counts: np.ndarray) -> Dict[str, np.ndarray]:
+    """counts [U, 5] -> the five count arrays plus what the reference reports from them, in its number formats: "n_fp" (self.fp,
+    train.py:100: y - p <= -0.5, i.e. y = 0 and p >= 0.5) = neg_ge, int64; "recall" (binary Recall: pos_gt / n_pos, 0 without
+    positives) and "accuracy" (binary Accuracy: (pos_gt + n_neg - neg_gt) / (n_pos + n_neg)), fp32 quotients of the integers as
+    torch divides them."""
+    c = np.asarray(counts, dtype=np.int64)
+    out = {f: c[:, i].astype(np.int32) for i, f in enumerate(COUNT_FIELDS)}
+    out["n_fp"] = c[:, 4].copy()
+    out["recall"] = np.where(c[:, 0] > 0, c[:, 2].astype(np.float32) / np.maximum(c[:, 0], 1).astype(np.float32), np.float32(0)).astype(np.float32)
+    tot = c[:, 0] + c[:, 1]
+    out["accuracy"] = np.where(tot > 0, (c[:, 2] + c[:, 1] - c[:, 3]).astype(np.float32) / np.maximum(tot, 1).astype(np.float32),
+                               np.float32(0)).astype(np.float32)
+    return out
+
+
 class HeadTrainer:
     """One training session on a BatchedModel's handle (BatchedModel.head_trainer): n_problems heads of one shape side by side."""
 
@@ -124,6 +144,49 @@ class HeadTrainer:
 
     def records(self) -> np.ndarray:
         return np.stack([self.engine.train_get(u, self.n_params) for u in range(self.n_problems)])
+
+    # ---- what auto_train needs around the step (include/owwhip.h: oww_train_new_sequence .. oww_train_get_slot) ----
+    def new_sequence(self) -> None:
+        """A new train_model call on the same optimizer: the accumulation counters restart (train.py:443-444); Adam's moments and
+        step count, which live in the reference's self.optimizer (train.py:135), stay."""
+        self.engine.train_new_sequence()
+
+    def set_eval_pool(self, pool, n_windows: Optional[int] = None, on_device: bool = False) -> None:
+        """The validation window pool [P, T, 96] fp32, independent of the training pool."""
+        if not on_device:
+            pool = np.asarray(pool)
+            if pool.ndim != 3 or pool.shape[1:] != (self.T, EMB_DIM):
+                raise ValueError(f"eval pool must be [P, {self.T}, 96], got {pool.shape}")
+        self.engine.train_set_eval_pool(pool, n_windows, on_device)
+
+    def evaluate(self, idx, y, source: int = -1, scores: bool = False, on_device: bool = False, shape=None) -> Dict[str, np.ndarray]:
+        """The forward pass of every problem over the eval-pool rows idx [n_problems, n] or [n] (shared; -1 = empty slot) with labels
+        y, on the live parameters (source = -1) or on checkpoint slot `source` -> the five counts n_pos, n_neg, pos_gt, neg_gt,
+        neg_ge [n_problems] and what the reference reports from them (metrics_from_counts); "scores" [n_problems, n] if asked."""
+        counts, sc = self.engine.train_eval(idx, y, source, scores, on_device, shape)
+        out = metrics_from_counts(counts)
+        if scores:
+            out["scores"] = sc
+        return out
+
+    def reserve_checkpoints(self, n_slots: int) -> None:
+        self.engine.train_checkpoints(n_slots)
+
+    def snapshot(self, slots) -> None:
+        """Problem u's live parameters -> its checkpoint slot slots[u] (-1: none), behind the steps submitted so far."""
+        self.engine.train_snapshot(slots)
+
+    def average(self, sel, dst: int) -> None:
+        """average_models (train.py:198-223) per problem over the slots sel [n_problems, C] marks, into slot dst; a problem with none
+        marked gets its live parameters there (train.py:340-343)."""
+        self.engine.train_average(sel, dst)
+
+    def checkpoint_records(self, slot: int) -> np.ndarray:
+        return np.stack([self.engine.train_get_slot(u, slot, self.n_params) for u in range(self.n_problems)])
+
+    def checkpoint_heads(self, slot: int) -> List[dict]:
+        """Checkpoint slot `slot` of every problem, as dicts bank_add takes unchanged."""
+        return [record_to_head(self.engine.train_get_slot(u, slot, self.n_params), self.T, self.hidden) for u in range(self.n_problems)]
 
     def heads(self) -> List[dict]:
         """The current heads, as dicts bank_add takes unchanged."""
@@ -195,3 +258,172 @@ def train_heads(bm, pool: np.ndarray, problems: Sequence[Tuple[np.ndarray, np.nd
             b = a + idx.shape[1]
             tr.steps(idx, y, lrs[a:b], nws[a:b])
         return tr.heads(), tr.history
+
+
+# ------------------------------------------------------------------------------------------------------------------ auto_train
+BEST_VAL_FP = 1000       # train.py: self.best_val_fp is initialised to this and never written (see auto_train's docstring)
+
+
+def auto_train_plan(steps: int, max_negative_weight: float = 1000, target_fp_per_hour: float = 0.2) -> List[dict]:
+    """The three sequences of train.py:261-324 as data: per sequence dict(n_steps, lr [n_steps] float64, neg_weight [n_steps] fp32,
+    val_steps: the sorted step indices after which a validation runs, max_negative_weight).  See auto_train for the quirks kept."""
+    if int(steps) != steps or steps < 50 or int(steps) % 10:
+        raise ValueError("auto_train: steps must be a multiple of 10, at least 50 (train.py:288 runs sequences 2 and 3 for steps / 10 "
+                         "steps as a float: any other value walks off the end of its weight list, and under 50 the warm-up is 0 steps long)")
+    out = []
+    lr, w, n = 0.0001, max_negative_weight, int(steps)
+    for seq in range(3):
+        if seq == 0:
+            val = np.linspace(n - int(n * 0.25), n, 20).astype(np.int64)
+            total = n                                          # an int
+        else:
+            lr = lr / 10
+            if seq == 1:
+                n = n / 10                                     # train.py:288: a float from here on
+            if BEST_VAL_FP > target_fp_per_hour:               # train.py:291 / 311
+                w = w * 2
+            val = np.linspace(1, n, 20).astype(np.int16)       # train.py:296: int16, wraps above 32,767
+            total = n
+        ni = int(n)
+        k = np.arange(ni)
+        lrs = np.asarray(lr_warmup_cosine_decay(k, warmup_steps=total // 5, hold=total // 3, total_steps=total, target_lr=lr), dtype=np.float64)
+        nws = np.asarray(np.linspace(1, w, ni).tolist(), dtype=np.float32)
+        vs = sorted({int(v) for v in val if 1 < int(v) <= ni - 1})      # train.py:513: step_ndx in val_steps and step_ndx > 1
+        out.append(dict(n_steps=ni, lr=lrs, neg_weight=nws, val_steps=vs, max_negative_weight=w))
+    return out
+
+
+def keep_checkpoint(val_n_fp: list, val_recall: list) -> bool:
+    """train.py:557-559, the current value already in both histories."""
+    return bool(val_n_fp[-1] <= np.percentile(val_n_fp, 50) and val_recall[-1] >= np.percentile(val_recall, 5))
+
+
+def select_checkpoints(hist: dict, scores: List[dict]) -> List[int]:
+    """train.py:326-338: the checkpoints (positions in `scores`) at or above the 90th percentile of accuracy and recall and at or
+    below the 10th of false positives per hour, the percentiles taken over the whole histories."""
+    if not hist["val_accuracy"]:
+        return []
+    a, r, f = np.percentile(hist["val_accuracy"], 90), np.percentile(hist["val_recall"], 90), np.percentile(hist["val_fp_per_hr"], 10)
+    return [i for i, s in enumerate(scores) if s["val_accuracy"] >= a and s["val_recall"] >= r and s["val_fp_per_hr"] <= f]
+
+
+class _TableFeed:
+    """iter_tables' chunks handed out a few steps at a time, across chunk boundaries"""
+
+    def __init__(self, it):
+        self.it, self.idx, self.y, self.at = it, None, None, 0
+
+    def take(self, k: int):
+        while k > 0:
+            if self.idx is None or self.at == self.idx.shape[1]:
+                _, self.idx, self.y = next(self.it)
+                self.at = 0
+            b = min(self.idx.shape[1], self.at + k)
+            yield self.idx[:, self.at:b], self.y[:, self.at:b]
+            k -= b - self.at
+            self.at = b
+
+
+def _eval_table(t, U: int, what: str):
+    """(idx, y) or idx alone (labels 0) -> int32 / uint8 arrays [n] or [U, n]"""
+    if isinstance(t, tuple):
+        idx, y = np.asarray(t[0], np.int32), np.asarray(t[1], np.uint8)
+    else:
+        idx = np.asarray(t, np.int32)
+        y = np.zeros(idx.shape, np.uint8)
+    if idx.shape != y.shape or idx.ndim not in (1, 2) or (idx.ndim == 2 and idx.shape[0] != U) or idx.shape[-1] < 1:
+        raise ValueError(f"auto_train: {what} must be index and label tables [n] or [{U}, n], got {idx.shape} and {y.shape}")
+    return idx, y
+
+
+def auto_train(bm, pool: np.ndarray, problems: Sequence[Tuple[np.ndarray, np.ndarray]], val_pool: np.ndarray, val, fp_val, steps: int = 50000,
+               max_negative_weight: float = 1000, target_fp_per_hour: float = 0.2, val_set_hrs: float = 11.3, hidden: int = 32,
+               n_batch: int = 128, seed: int = 0, init: Optional[Sequence[dict]] = None) -> Tuple[List[dict], dict]:
+    """Model.auto_train (train.py:261-366) for len(problems) heads side by side on `bm`'s device -> (heads for bank_add, report).
+    `pool` [P, T, 96] and problems[u] = (positive rows, negative rows) are train_heads'; `val_pool` [Pv, T, 96] holds the validation
+    windows; `val` = (idx, y) tables into it, [n] shared or [U, n] (-1 pads), the reference's X_val as ONE batch (the reference keeps
+    the last batch's metrics only); `fp_val` the false-positive table (idx, or (idx, y) with y all 0), any length up to 2^20.
+    Steps, validation, checkpoints and merge run on the device; decisions are taken here, per problem, each with its own histories,
+    checkpoint list and selection.  The tables of all three sequences come from ONE iter_tables generator.
+
+    What the reference does, reproduced as it is:
+      * sequence 1: `steps` steps at lr 1e-4, validated after the steps np.linspace(steps - int(0.25 steps), steps, 20).astype(int64);
+        the last value, `steps`, is never reached.
+      * sequences 2 and 3: steps / 10 steps (a float in the reference) at lr / 10 and lr / 100, validated after the steps
+        np.linspace(1, steps / 10, 20).astype(np.int16) (int16: wraps above 32,767 steps) that are > 1 (train.py:513).
+      * every sequence: warm-up n // 5, hold n // 3 of its own length n, negative weight np.linspace(1, w, int(n)); a new sequence
+        restarts the accumulation counters and keeps Adam's moments and step count (HeadTrainer.new_sequence).
+      * a validation runs after the step of its index; a checkpoint is kept when val_n_fp[-1] <= percentile(val_n_fp, 50) and
+        val_recall[-1] >= percentile(val_recall, 5), the current values already in the histories, which run on across sequences.
+      * best_val_fp is initialised to 1000 and never written, so max_negative_weight doubles before sequence 2 and again before
+        sequence 3 whenever target_fp_per_hour < 1000: sequence 3 ramps to 4 x the argument.
+      * merge: checkpoints with val_accuracy >= p90, val_recall >= p90 and val_fp_per_hr <= p10 of the histories are averaged
+        (average_models: 0 x the first, += in order, one division); with none, the live model is returned.
+    report["problems"][u]: the histories (val_recall, val_accuracy, val_n_fp, val_fp_per_hr), counts / fp_counts per validation,
+    checkpoint_steps ((sequence, step) pairs), selected (positions in the checkpoint list), combined (the returned model's three
+    metrics), live_record (the model as training left it: what is returned, bit for bit, where nothing is selected), loss, kept.
+    Not here: _select_best_model (auto_train does not call it), positive_test_clips recall, multiclass and recurrent heads."""
+    pool = np.asarray(pool, dtype=np.float32)
+    T, U = pool.shape[1], len(problems)
+    plan = auto_train_plan(steps, max_negative_weight, target_fp_per_hour)
+    v_idx, v_y = _eval_table(val, U, "val")
+    f_idx, f_y = _eval_table(fp_val, U, "fp_val")
+    if f_y.any():
+        raise ValueError("auto_train: the false-positive table's labels are all 0")
+    n_val = sum(len(s["val_steps"]) for s in plan)
+    hrs = np.float32(val_set_hrs)
+    hist = [dict(val_recall=[], val_accuracy=[], val_n_fp=[], val_fp_per_hr=[]) for _ in range(U)]
+    counts: List[list] = [[] for _ in range(U)]          # per validation: the five counts of `val`, and fp_val's neg_ge
+    fp_counts: List[list] = [[] for _ in range(U)]
+    ckpt: List[List[dict]] = [[] for _ in range(U)]
+    feed = _TableFeed(iter_tables(problems, sum(s["n_steps"] for s in plan), n_batch, seed))
+    with bm.head_trainer(T, hidden, U, init=init, seed=seed) as tr:
+        tr.set_pool(pool)
+        tr.set_eval_pool(val_pool)
+        tr.reserve_checkpoints(max(n_val, 1))
+        for si, seq in enumerate(plan):
+            if si:
+                tr.new_sequence()
+            k = 0
+            last = seq["n_steps"] - 1
+            for v in seq["val_steps"] + ([] if last in seq["val_steps"] else [last]):
+                for idx, y in feed.take(v + 1 - k):
+                    b = k + idx.shape[1]
+                    tr.steps(idx, y, seq["lr"][k:b], seq["neg_weight"][k:b])
+                    k = b
+                if v not in seq["val_steps"]:
+                    continue
+                fp, mv = tr.evaluate(f_idx, f_y), tr.evaluate(v_idx, v_y)
+                slots = np.full(U, -1, np.int32)
+                for u in range(U):
+                    h = hist[u]
+                    h["val_fp_per_hr"].append(np.float32(fp["n_fp"][u]) / hrs)      # an int64 tensor / a float: fp32 in torch
+                    h["val_accuracy"].append(mv["accuracy"][u])
+                    h["val_recall"].append(mv["recall"][u])
+                    h["val_n_fp"].append(np.int64(mv["n_fp"][u]))
+                    counts[u].append([int(mv[f][u]) for f in COUNT_FIELDS])
+                    fp_counts[u].append(int(fp["neg_ge"][u]))
+                    if keep_checkpoint(h["val_n_fp"], h["val_recall"]):
+                        slots[u] = len(ckpt[u])
+                        ckpt[u].append(dict(sequence=si, training_step_ndx=v, val_n_fp=h["val_n_fp"][-1], val_recall=h["val_recall"][-1],
+                                            val_accuracy=h["val_accuracy"][-1], val_fp_per_hr=h["val_fp_per_hr"][-1]))
+                if (slots >= 0).any():
+                    tr.snapshot(slots)
+        selected = [select_checkpoints(hist[u], ckpt[u]) for u in range(U)]
+        sel = np.zeros((U, max(n_val, 1)), np.uint8)
+        for u, s in enumerate(selected):
+            sel[u, s] = 1
+        live = tr.records()                        # the model as training left it: what a problem with nothing selected gets back
+        tr.average(sel, 0)
+        fp, mv = tr.evaluate(f_idx, f_y, source=0), tr.evaluate(v_idx, v_y, source=0)
+        heads = tr.checkpoint_heads(0)
+        history = tr.history
+    report = []
+    for u in range(U):
+        h = hist[u]
+        report.append(dict({k_: np.asarray(v_) for k_, v_ in h.items()},
+                           checkpoint_steps=[(c["sequence"], c["training_step_ndx"]) for c in ckpt[u]], checkpoints=ckpt[u], selected=selected[u],
+                           counts=np.asarray(counts[u], np.int32).reshape(-1, 5), fp_counts=np.asarray(fp_counts[u], np.int32),
+                           combined=dict(recall=mv["recall"][u], accuracy=mv["accuracy"][u], fp_per_hr=np.float32(fp["n_fp"][u]) / hrs),
+                           live_record=live[u], loss=history["loss"][u], kept=history["kept"][u]))
+    return heads, {"problems": report, "plan": plan}
